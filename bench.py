@@ -167,6 +167,45 @@ def log(msg):
     print("[bench] " + msg, file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 20        # parameter / gradient values sampled at fixed, seeded positions
+
+
+def capture_outputs(preds, losses, model):
+    """What the last timed step handed its caller, copied on the device before anything else runs: the logits, the two losses, and the
+    parameters Adam wrote and the gradients it read, both as a sample at DUMP_SAMPLE fixed positions (seeded, so the same positions
+    in every run of the same workload).  float32, one array per name."""
+    out = {k: v.detach().float().clone() for k, v in preds.items() if torch.is_tensor(v)}
+    for k, v in losses.items():
+        out[k] = v.detach().float().reshape(1).clone()
+    params = [p for p in model.parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    idx = torch.randint(0, flat_p.numel(), (min(DUMP_SAMPLE, flat_p.numel()),), generator=torch.Generator().manual_seed(0))
+    idx = idx.sort().values.to(flat_p.device)
+    out["param_sample"] = flat_p[idx].float()
+    out["grad_sample"] = flat_g[idx].float()
+    return out
+
+
+def dump_outputs(outputs, path):
+    """Writes every captured array as path/<name>.npy.  If they come to more than DUMP_BYTES, every array larger than an equal share of
+    it is reduced to a seeded sample of its rows (the row indices are written next to it as <name>_rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: t.cpu().numpy() for name, t in outputs.items()}
+    share = DUMP_BYTES // (2 * max(len(arrays), 1)) if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES else None
+    written = 0
+    for name, a in sorted(arrays.items()):
+        if share is not None and a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(share * a.shape[0] // a.nbytes, 1), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            written += rows.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(outputs), written / 2**20, path))
+
+
 def cpu_baseline(cfg, np_batch):
     """The CPU restatement of the reference (oracle/), forward+backward on ONE frame of the same
     synthetic workload: 1 untimed warm-up + timed passes until ~12 s of CPU work."""
@@ -308,7 +347,12 @@ def main():
                     help="N = 1 only: create a one-rank RCCL communicator and run the gradient exchange of the N > 1 path (bucketed async all-reduces "
                          "issued from the autograd hooks) inside every step; the result is the identity, the code path is the multi-GPU one")
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the graphed-vs-eager bit-identity check after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (logits, losses, a fixed sample of the updated "
+                         "parameters and of the gradients) as DIR/<name>.npy, float32/float64, at most 64 MB; rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (the reference's counterpart is torchpack_run.sh:3)
@@ -391,7 +435,7 @@ def main():
             launch_log = spf.LAUNCH_LOG = []
             model.overlap_branches = False
         j = args.warmup + i            # continue the warm-up's alternation: the batch of step j was prepared by step j - 1
-        step(datas[j % len(datas)], nxt(datas, j))
+        preds = step(datas[j % len(datas)], nxt(datas, j))
         if i == 0:
             loss_first = step.last          # device tensors: read after the timed region
         loss_last = step.last
@@ -403,6 +447,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # before anything else touches the model: the exchange below overwrites the gradients and the selfcheck runs one more step
+    captured = capture_outputs(preds, loss_last, model) if (args.dump_outputs and rank == 0) else None
 
     allreduce_ms = None
     if reducer is not None and rank == 0:
@@ -539,6 +585,9 @@ def main():
                                                         "image": "%dx%d" % (SHAPES["nuscenes"]["H"], SHAPES["nuscenes"]["W"])}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, np_batch)
+        if captured is not None:
+            dump_outputs(captured, args.dump_outputs)
+            out["dump_outputs"] = os.path.abspath(args.dump_outputs)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if args.tune_gemm and rank == 0:

@@ -178,6 +178,29 @@ def test_bench_self_launch_command_is_the_drivers_launcher_line():
     assert 1024 < int(auto[auto.index("--master-port") + 1]) < 65536
 
 
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: one float .npy per array; the parameter / gradient sample sits at the same positions in every run; over the
+    size budget, large arrays are cut to a seeded sample of rows and the whole stays within it."""
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Linear(64, 32)
+    m(torch.randn(4, 64)).sum().backward()
+    preds = {"lidar_seg_logit": torch.randn(5000, 20), "img_seg_logit": torch.randn(5000, 20)}
+    losses = {"loss_2d": torch.tensor(1.5), "loss_3d": torch.tensor(2.5)}
+    a, b = bench.capture_outputs(preds, losses, m), bench.capture_outputs(preds, losses, m)
+    assert set(a) == {"lidar_seg_logit", "img_seg_logit", "loss_2d", "loss_3d", "param_sample", "grad_sample"}
+    assert all(torch.equal(a[k], b[k]) for k in a)
+    bench.dump_outputs(a, str(tmp_path / "whole"))
+    for k, v in a.items():
+        arr = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert arr.dtype == np.float32 and np.array_equal(arr, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 256 << 10)
+    bench.dump_outputs(a, str(tmp_path / "cut"))
+    assert sum(f.stat().st_size for f in (tmp_path / "cut").iterdir()) <= (256 << 10) + 4096     # + the .npy headers
+    rows = np.load(tmp_path / "cut" / "lidar_seg_logit_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "cut" / "lidar_seg_logit.npy"), a["lidar_seg_logit"].numpy()[rows])
+
+
 def test_carve_refuses_to_run_under_stream_capture(monkeypatch):
     """functional._carve returns raw addresses into the stream's scratch buffer; under HIP-graph capture that buffer would be a
     fresh pool allocation freed on return, so the call must fail loudly instead."""
