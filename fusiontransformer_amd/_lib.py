@@ -69,6 +69,7 @@ SIGNATURES = {
     "ftx_spconv_ostat_blocks": (_i32, [_i64]),
     "ftx_spconv_ostat": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "ftx_rows_gemm": (C.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "ftx_spconv_gemm_block_cols": (_i32, [_i32, _i64, _i32]),
     "ftx_spconv_reduce": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "ftx_spconv_reduce_stats_blocks": (_i32, [_i64, _i32]),
     "ftx_spconv_reduce_stats": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),

@@ -376,6 +376,14 @@ static int gemm_nt(int co, int64_t row_tiles) {
   return nt;
 }
 
+// Column-block width (32 * nt) that the launches below pick, for tests that must know which tile shape they reach:
+// kvol >= 1 is a pair list of n_pairs pairs (ftx_spconv_pairs_gemm / _scatter), kvol == 0 dense rows (ftx_rows_gemm, n_pairs rows).
+extern "C" int32_t ftx_spconv_gemm_block_cols(int32_t co, int64_t n_pairs, int32_t kvol) {
+  if (co < 4 || co % 4 != 0 || n_pairs < 0 || kvol < 0) return -1;
+  const int64_t row_tiles = ceil_div(n_pairs, TILE_P) + kvol;
+  return 32 * gemm_nt(co, row_tiles);
+}
+
 // Measured on MI355X (profiles/r01_spconv_layer_micro.txt workload): 256-pair tiles (RT = 2) are 5-30 % SLOWER than 128-pair tiles on every
 // layer -- the extra accumulators cut occupancy to 1-2 waves per SIMD and the kernel is latency-, not W-traffic-bound: RT = 1 everywhere.
 

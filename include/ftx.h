@@ -225,6 +225,9 @@ int ftx_spconv_ostat(const float *A, int64_t rows_a, const int32_t *nbr, int64_t
  * bias (co) may be NULL.  Replaces the point-branch nn.Linear layers (models/spvcnn.py:164-180,
  * models/middle_fusion.py:18-29) and the kernel_size=1 spnn.Conv3d (spvcnn.py:71-75). */
 int ftx_rows_gemm(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co, float *out, void *stream);
+/* Host-only: the output columns per block (32, 64, 96 or 128) that ftx_spconv_pairs_gemm / _scatter (kvol >= 1, n_pairs pairs) or
+ * ftx_rows_gemm (kvol = 0, n_pairs rows) pick for co output channels; -1 for invalid arguments.  Launches nothing. */
+int32_t ftx_spconv_gemm_block_cols(int32_t co, int64_t n_pairs, int32_t kvol);
 
 /* out[r,:] = sum over k (ascending) of tmp[pos[k,r],:] for pos >= 0; out (n, co) fully written. */
 int ftx_spconv_reduce(const float *tmp, const int32_t *pos, int64_t n, int32_t co, int32_t kvol, float *out, void *stream);
