@@ -1119,7 +1119,9 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------- ViT self-attention
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, scale, tiling=(0, 0)):
+    def forward(ctx, qkv, scale, tiling=(0, 0), bf16=False):
+        if bf16:
+            return _attention_bf16_fwd(ctx, qkv, scale, tiling)
         L = _lib.load()
         qkv = req(qkv.contiguous(), F32, "attention qkv", 5)
         b, t, three, h, d = qkv.shape
@@ -1131,7 +1133,7 @@ class _Attention(torch.autograd.Function):
         _log_launch("attn_fwd", dict(b=b, t=t, h=h, d=d, products=2), lambda: check(L.ftx_attn_fwd_tiled(
             ptr(qkv), b, t, h, d, float(scale), ptr(out), ptr(lse), qw, split, stream()), "ftx_attn_fwd"))
         ctx.save_for_backward(qkv, out, lse)
-        ctx.scale, ctx.tiling = float(scale), (qw, split)
+        ctx.scale, ctx.tiling, ctx.bf16 = float(scale), (qw, split), False
         return out
 
     @staticmethod
@@ -1143,15 +1145,37 @@ class _Attention(torch.autograd.Function):
         gqkv = torch.empty_like(qkv)
         ws_bytes = int(L.ftx_attn_bwd_workspace_bytes(b, t, h))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=qkv.device)
+        if ctx.bf16:
+            _log_launch("attn_bwd_bf16", dict(b=b, t=t, h=h, d=d, products=7), lambda: check(L.ftx_attn_bwd_bf16(
+                ptr(qkv), ptr(out), ptr(go), ptr(lse), b, t, h, d, ctx.scale, ptr(gqkv), ptr(ws), ws_bytes, ctx.tiling[0], ctx.tiling[1], stream()), "ftx_attn_bwd_bf16"))
+            return gqkv, None, None, None
         _log_launch("attn_bwd", dict(b=b, t=t, h=h, d=d, products=7), lambda: check(L.ftx_attn_bwd_tiled(
             ptr(qkv), ptr(out), ptr(go), ptr(lse), b, t, h, d, ctx.scale, ptr(gqkv), ptr(ws), ws_bytes, ctx.tiling[0], ctx.tiling[1], stream()), "ftx_attn_bwd"))
-        return gqkv, None, None
+        return gqkv, None, None, None
 
 
-def attention(qkv, scale, tiling=(0, 0)):
+def _attention_bf16_fwd(ctx, qkv, scale, tiling):
+    L = _lib.load()
+    qkv = req(qkv.contiguous(), F32, "attention qkv", 5)
+    b, t, three, h, d = qkv.shape
+    if three != 3 or d != 64:
+        raise ValueError(f"attention: qkv must be (B, T, 3, heads, 64), got {tuple(qkv.shape)}")
+    out = _empty((b, t, h * d), F32, qkv)
+    lse = _empty((b, h, t), F32, qkv)
+    qw, split = int(tiling[0]), int(tiling[1])
+    _log_launch("attn_fwd_bf16", dict(b=b, t=t, h=h, d=d, products=2), lambda: check(L.ftx_attn_fwd_bf16(
+        ptr(qkv), b, t, h, d, float(scale), ptr(out), ptr(lse), qw, split, stream()), "ftx_attn_fwd_bf16"))
+    ctx.save_for_backward(qkv, out, lse)
+    ctx.scale, ctx.tiling, ctx.bf16 = float(scale), (qw, split), True
+    return out
+
+
+def attention(qkv, scale, tiling=(0, 0), bf16=False):
     """softmax(Q K^T * scale) V for qkv (B, T, 3, heads, 64) -> (B, T, heads*64).  `tiling` = (waves per block, key groups) of the
-    kernels, (0, 0) = chosen per launch (ftx_attn_fwd_tiled in include/ftx.h): a per-call argument for tests and tools."""
-    return _Attention.apply(qkv, scale, tiling)
+    kernels, (0, 0) = chosen per launch (ftx_attn_fwd_tiled in include/ftx.h): a per-call argument for tests and tools.
+    bf16=True: the bf16-operand kernels (ftx_attn_fwd_bf16 / ftx_attn_bwd_bf16: Q, K, V, dO, P and dS rounded to bf16 as MFMA
+    operands, fp32 accumulation, softmax statistics and storage; the contract is stated in include/ftx.h)."""
+    return _Attention.apply(qkv, scale, tiling, bool(bf16))
 
 
 # ---------------------------------------------------------------- fused sample_down

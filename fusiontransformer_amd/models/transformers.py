@@ -8,7 +8,8 @@ restated here with the same attribute names, so DeiT checkpoints keyed
 
 The dense contractions (patch-embed conv, qkv / proj / MLP linears) go through
 torch's hipBLASLt GEMMs; softmax(QK^T/8)V runs in libftx's fused attention
-kernel when `attn_impl == "ftx"`, otherwise as the three explicit ops timm uses."""
+kernel when `attn_impl == "ftx"` (exact fp32) or `"ftx_bf16"` (bf16 operands, fp32 accumulation and softmax:
+functional.attention(bf16=True)), otherwise as the three explicit ops timm uses."""
 from __future__ import annotations
 
 import os
@@ -129,9 +130,9 @@ class Attention(nn.Module):
     def forward(self, x, with_proj_bias=True):
         B, N, C = x.shape
         qkv = _linear(x, self.qkv)
-        if self.attn_impl == "ftx":
+        if self.attn_impl in ("ftx", "ftx_bf16"):
             from .. import functional as spf
-            x = spf.attention(qkv.view(B, N, 3, self.num_heads, C // self.num_heads), self.scale)
+            x = spf.attention(qkv.view(B, N, 3, self.num_heads, C // self.num_heads), self.scale, bf16=self.attn_impl == "ftx_bf16")
         else:
             qkv = qkv.reshape(B, N, 3, self.num_heads, C // self.num_heads).permute(2, 0, 3, 1, 4)
             q, k, v = qkv[0], qkv[1], qkv[2]
@@ -268,7 +269,8 @@ class Image2DTransformer(nn.Module):
     def set_bf16(self, on: bool = True):
         """bf16 operands for the qkv / proj / MLP GEMMs of every block (fp32 accumulate, fp32 everywhere else: LayerNorm,
         softmax, residual stream, attention kernel).  No counterpart in the reference, which is fp32 end to end; the parity
-        bar for this mode is stated in tests/test_model_gpu.py."""
+        bar for this mode is stated in tests/test_model_gpu.py.  The attention kernel gets bf16 operands separately:
+        set_attention_impl("ftx_bf16")."""
         for blk in self.blocks:
             for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
                 lin.ftx_bf16 = bool(on)

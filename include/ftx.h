@@ -314,6 +314,15 @@ int ftx_attn_bwd(const float *qkv, const float *out, const float *grad_out, cons
  * differ in the last bits (the key range is summed in a different grouping), never with timing. */
 int ftx_attn_fwd_tiled(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw, int32_t split, void *stream);
 int ftx_attn_bwd_tiled(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split, void *stream);
+/* bf16-operand attention: the same calls on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (models/transformers.py attn_impl "ftx_bf16").
+ * Storage stays fp32: qkv, out, lse, grad_out, grad_qkv as above.  Q, K, V and dO are rounded to bf16 (round-to-nearest-even) from
+ * their stored values; scale is applied in fp32 to the fp32 score; the softmax max, row sum and lse use the unrounded fp32 exponentials,
+ * so lse is the fp32-accurate log-sum-exp of the bf16-operand scores; P is rounded to bf16 only as the P.V operand.  Backward: P
+ * recomputed from lse, dP = dO V^T on bf16 operands, delta = rowsum(bf16(dO) * O) in fp32, dS rounded to bf16 only as the dK / dQ operand,
+ * every gradient accumulated and written in fp32.  No atomics: deterministic for a given tiling.  Tilings as ftx_attn_fwd_tiled
+ * ((0, 0) = chosen per launch; built (4,2) (2,2) (2,4) (1,2) (1,4) (1,8); anything else refused).  workspace: ftx_attn_bwd_workspace_bytes. */
+int ftx_attn_fwd_bf16(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw, int32_t split, void *stream);
+int ftx_attn_bwd_bf16(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split, void *stream);
 
 /* ---- fused train-step losses + metric: modules/SemanticTrainer.py:158-194, models/metric.py:37-58 ----
  * losses[0] = loss_2d = CE_w(img_logit) + lambda * KL(softmax(lidar_logit) || softmax(img_logit2))

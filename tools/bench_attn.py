@@ -1,5 +1,7 @@
 """Micro-benchmark of the fused attention kernels at the ViT's shape (578 tokens, 12 heads) over the built tilings.
-usage (GPU box): python tools/bench_attn.py [--batches 1,2,4,8] [--iters 50]"""
+usage (GPU box): python tools/bench_attn.py [--batches 1,2,4,8] [--iters 50]
+--bf16: the fp32 kernels and the bf16-operand kernels (ftx_attn_fwd_bf16 / ftx_attn_bwd_bf16) from the same process, each point timed
+--repeats times (median and min-max spread printed), with max |bf16 - fp32| of out and grad_qkv at the same tiling."""
 import argparse, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,6 +12,8 @@ ap.add_argument("--batches", default="1,2,4,8")
 ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--tokens", type=int, default=578)
 ap.add_argument("--heads", type=int, default=12)
+ap.add_argument("--bf16", action="store_true", help="compare the fp32 and the bf16-operand kernels")
+ap.add_argument("--repeats", type=int, default=5, help="--bf16: timed repeats per point")
 args = ap.parse_args()
 L = spf._lib.load()
 T, H = args.tokens, args.heads
@@ -25,6 +29,41 @@ def timeit(fn):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / args.iters * 1e3
 
+
+
+
+def bench_bf16():
+    import statistics
+    print("%5s %8s %5s | %9s %11s %9s | %9s %11s %9s | %9s | max |bf16 - fp32|: out, grad"
+          % ("batch", "(qw,spl)", "prec", "fwd us", "spread", "TFLOP/s", "bwd us", "spread", "TFLOP/s", "f+b us"))
+    for B in [int(x) for x in args.batches.split(",")]:
+        g = torch.Generator(device="cuda"); g.manual_seed(B)
+        qkv = torch.randn(B, T, 3, H, 64, device="cuda", generator=g)
+        go = torch.randn(B, T, H * 64, device="cuda", generator=g)
+        ws_bytes = int(L.ftx_attn_bwd_workspace_bytes(B, T, H)); ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        flop_f = 4.0 * B * H * T * T * 64
+        for qw, sp in CFGS:
+            res = {}
+            for prec in ("fp32", "bf16"):
+                fwd, bwd = (L.ftx_attn_fwd_tiled, L.ftx_attn_bwd_tiled) if prec == "fp32" else (L.ftx_attn_fwd_bf16, L.ftx_attn_bwd_bf16)
+                out = torch.empty(B, T, H * 64, device="cuda"); lse = torch.empty(B, H, T, device="cuda"); gq = torch.empty_like(qkv)
+                f = lambda: fwd(qkv.data_ptr(), B, T, H, 64, 0.125, out.data_ptr(), lse.data_ptr(), qw, sp, spf.stream())
+                bw = lambda: bwd(qkv.data_ptr(), out.data_ptr(), go.data_ptr(), lse.data_ptr(), B, T, H, 64, 0.125, gq.data_ptr(), ws.data_ptr(), ws_bytes, qw, sp, spf.stream())
+                tf = [timeit(f) for _ in range(args.repeats)]
+                tb = [timeit(bw) for _ in range(args.repeats)]
+                res[prec] = (out, gq)
+                mf, mb = statistics.median(tf), statistics.median(tb)
+                d = ""
+                if prec == "bf16":
+                    d = "%.2e %.2e" % ((out - res["fp32"][0]).abs().max().item(), (gq - res["fp32"][1]).abs().max().item())
+                print("%5d %8s %5s | %9.1f %5.1f-%5.1f %9.1f | %9.1f %5.1f-%5.1f %9.1f | %9.1f | %s"
+                      % (B, "auto" if qw == 0 else "(%d,%d)" % (qw, sp), prec, mf, min(tf), max(tf), flop_f / mf / 1e6,
+                         mb, min(tb), max(tb), 2.5 * flop_f / mb / 1e6, mf + mb, d), flush=True)
+
+
+if args.bf16:
+    bench_bf16()
+    sys.exit(0)
 
 print("%5s %8s | %9s %9s | %9s %9s | max |d| vs (4,2): out, grad" % ("batch", "(qw,spl)", "fwd us", "TFLOP/s", "bwd us", "TFLOP/s"))
 for B in [int(x) for x in args.batches.split(",")]:
