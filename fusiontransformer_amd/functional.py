@@ -468,30 +468,40 @@ def _log_launch(kind, meta, launch):
     return out
 
 
-def _spconv_apply(A, W, gather, pos, koff, n_pairs, n_rows_out, co, w_transposed):
+# bf16=True: the bf16-operand twins of the pair GEMM and the weight gradient (csrc/ftx_spconv_bf16.hip; the operands are rounded to bf16,
+# accumulation and storage stay fp32, include/ftx.h).  (C entry, launch-log kind) per precision.
+_PAIRS_GEMM = {False: ("ftx_spconv_pairs_gemm", "spconv_pairs_gemm"), True: ("ftx_spconv_pairs_gemm_bf16", "spconv_pairs_gemm_bf16")}
+_PAIRS_GEMM_SCATTER = {False: "ftx_spconv_pairs_gemm_scatter", True: "ftx_spconv_pairs_gemm_scatter_bf16"}
+_PAIRS_WGRAD = {False: ("ftx_spconv_pairs_wgrad", "ftx_spconv_pairs_wgrad_workspace_bytes", "spconv_pairs_wgrad"),
+                True: ("ftx_spconv_pairs_wgrad_bf16", "ftx_spconv_pairs_wgrad_bf16_workspace_bytes", "spconv_pairs_wgrad_bf16")}
+_ROWS_GEMM = {False: "ftx_rows_gemm", True: "ftx_rows_gemm_bf16"}
+
+
+def _spconv_apply(A, W, gather, pos, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False):
     """reduce(pairs_gemm(A[gather] @ W[k]), pos) -> (n_rows_out, co)."""
     L = _lib.load()
+    gemm, kind = _PAIRS_GEMM[bool(bf16)]
     rows_a, ca = A.shape
     kvol = koff.shape[0] - 1
     tmp = _empty((n_pairs, co), F32, A)
     out = _empty((n_rows_out, co), F32, A)
 
     def launch_gemm():
-        check(L.ftx_spconv_pairs_gemm(ptr(A), rows_a, ptr(gather), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, kvol, ptr(tmp), stream()),
-              "ftx_spconv_pairs_gemm")
+        check(getattr(L, gemm)(ptr(A), rows_a, ptr(gather), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, kvol, ptr(tmp), stream()), gemm)
 
     def launch_reduce():
         check(L.ftx_spconv_reduce(ptr(tmp), ptr(pos), n_rows_out, co, kvol, ptr(out), stream()), "ftx_spconv_reduce")
 
     meta = dict(pairs=n_pairs, n_out=n_rows_out, ca=ca, co=co, kvol=kvol)
-    _log_launch("spconv_pairs_gemm", meta, launch_gemm)
+    _log_launch(kind, meta, launch_gemm)
     _log_launch("spconv_reduce", meta, launch_reduce)
     return out
 
 
-def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_transposed):
+def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False):
     """out[scatter[p]] = A[gather[p]] @ W[k(p)] in ONE launch, for maps whose destination side is a bijection of the pair list."""
     L = _lib.load()
+    gemm, kind = _PAIRS_GEMM_SCATTER[bool(bf16)], _PAIRS_GEMM[bool(bf16)][1]
     rows_a, ca = A.shape
     kvol = koff.shape[0] - 1
     if n_pairs != n_rows_out:
@@ -499,10 +509,10 @@ def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_trans
     out = _empty((n_rows_out, co), F32, A)
 
     def launch():
-        check(L.ftx_spconv_pairs_gemm_scatter(ptr(A), rows_a, ptr(gather), ptr(scatter), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, kvol,
-                                              ptr(out), n_rows_out, stream()), "ftx_spconv_pairs_gemm_scatter")
+        check(getattr(L, gemm)(ptr(A), rows_a, ptr(gather), ptr(scatter), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, kvol,
+                               ptr(out), n_rows_out, stream()), gemm)
 
-    _log_launch("spconv_pairs_gemm", dict(pairs=n_pairs, n_out=n_rows_out, ca=ca, co=co, kvol=kvol, direct=True), launch)
+    _log_launch(kind, dict(pairs=n_pairs, n_out=n_rows_out, ca=ca, co=co, kvol=kvol, direct=True), launch)
     return out
 
 
@@ -554,20 +564,21 @@ def _spconv_ostat(A, W, nbr, n_rows_out, co, w_transposed, flip, part=0, nb=0, p
     return out
 
 
-def _spconv_wgrad(A, idx_a, G, idx_g, koff, n_pairs):
+def _spconv_wgrad(A, idx_a, G, idx_g, koff, n_pairs, bf16=False):
     L = _lib.load()
+    fn, ws_fn, kind = _PAIRS_WGRAD[bool(bf16)]
     rows_a, ca = A.shape
     rows_g, cg = G.shape
     kvol = koff.shape[0] - 1
     dW = _empty((kvol, ca, cg), F32, A)
-    ws_bytes = _ws_bytes("ftx_spconv_pairs_wgrad_workspace_bytes", n_pairs, ca, cg, kvol)
+    ws_bytes = _ws_bytes(ws_fn, n_pairs, ca, cg, kvol)
     ws = _scratch(ws_bytes, A)
 
     def launch():
-        check(L.ftx_spconv_pairs_wgrad(ptr(A), rows_a, ptr(idx_a), ptr(G), rows_g, ptr(idx_g), ptr(koff), n_pairs, ca, cg, kvol, ptr(dW), ptr(ws),
-                                       ws_bytes, stream()), "ftx_spconv_pairs_wgrad")
+        check(getattr(L, fn)(ptr(A), rows_a, ptr(idx_a), ptr(G), rows_g, ptr(idx_g), ptr(koff), n_pairs, ca, cg, kvol, ptr(dW), ptr(ws),
+                             ws_bytes, stream()), fn)
 
-    _log_launch("spconv_pairs_wgrad", dict(pairs=n_pairs, n_out=rows_g, ca=ca, co=cg, kvol=kvol), launch)
+    _log_launch(kind, dict(pairs=n_pairs, n_out=rows_g, ca=ca, co=cg, kvol=kvol), launch)
     return dW
 
 
@@ -579,32 +590,33 @@ def _conv_shapes(feats, kernel, km, transposed):
     return kvol, ca, co, n_in, n_out
 
 
-def _conv_forward(feats, kernel, km, transposed):
+def _conv_forward(feats, kernel, km, transposed, bf16=False):
+    """bf16=True: the bf16-operand kernels; the output-stationary kernel is exact fp32 only, so every layer takes the pair list."""
     kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
     if transposed and km.fine_bijective:
         # every fine row is the destination of exactly one pair: the GEMM epilogue writes `out` itself
-        return _spconv_direct(feats, kernel, km.pair_out, km.pair_in, km.koff, km.n_pairs, n_out, co, 0)
-    if not transposed and n_out > 0 and km.n_pairs > 0 and ostat_preferred(ca, co, kvol, rows=n_out):
+        return _spconv_direct(feats, kernel, km.pair_out, km.pair_in, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
+    if not bf16 and not transposed and n_out > 0 and km.n_pairs > 0 and ostat_preferred(ca, co, kvol, rows=n_out):
         return _spconv_ostat(feats, kernel, km.nbr, n_out, co, 0, 0, pairs=km.n_pairs)
     gather, pos = (km.pair_out, km.pos_t) if transposed else (km.pair_in, km.pos)
-    return _spconv_apply(feats, kernel, gather, pos, km.koff, km.n_pairs, n_out, co, 0)
+    return _spconv_apply(feats, kernel, gather, pos, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
 
 
-def _conv_backward(feats, kernel, km, transposed, grad_out, need_feats, need_kernel):
+def _conv_backward(feats, kernel, km, transposed, grad_out, need_feats, need_kernel, bf16=False):
     kvol, ca, co = kernel.shape
     g_feats = g_kernel = None
     in_side, out_side = (km.pair_out, km.pair_in) if transposed else (km.pair_in, km.pair_out)
     if need_feats:
         if not transposed and km.fine_bijective:
-            g_feats = _spconv_direct(grad_out, kernel, km.pair_out, km.pair_in, km.koff, km.n_pairs, feats.shape[0], ca, 1)
-        elif not transposed and km.submanifold and km.n_pairs > 0 and ostat_preferred(co, ca, kvol, True, rows=feats.shape[0]):
+            g_feats = _spconv_direct(grad_out, kernel, km.pair_out, km.pair_in, km.koff, km.n_pairs, feats.shape[0], ca, 1, bf16=bf16)
+        elif not bf16 and not transposed and km.submanifold and km.n_pairs > 0 and ostat_preferred(co, ca, kvol, True, rows=feats.shape[0]):
             # symmetric map: the data gradient is the same output-stationary kernel on the same table, read mirrored
             g_feats = _spconv_ostat(grad_out, kernel, km.nbr, feats.shape[0], ca, 1, 1, pairs=km.n_pairs)
         else:
             pos_in = km.pos if transposed else km.pos_t
-            g_feats = _spconv_apply(grad_out, kernel, out_side, pos_in, km.koff, km.n_pairs, feats.shape[0], ca, 1)
+            g_feats = _spconv_apply(grad_out, kernel, out_side, pos_in, km.koff, km.n_pairs, feats.shape[0], ca, 1, bf16=bf16)
     if need_kernel:
-        g_kernel = _spconv_wgrad(feats, in_side, grad_out, out_side, km.koff, km.n_pairs)
+        g_kernel = _spconv_wgrad(feats, in_side, grad_out, out_side, km.koff, km.n_pairs, bf16=bf16)
     return g_feats, g_kernel
 
 
@@ -615,44 +627,47 @@ class _SparseConv(torch.autograd.Function):
     transposed conv of models/spvcnn.py:42-46 reuses the paired strided conv's map."""
 
     @staticmethod
-    def forward(ctx, feats, kernel, km, transposed):
+    def forward(ctx, feats, kernel, km, transposed, bf16=False):
         feats = req(feats.contiguous(), F32, "conv3d feats", 2)
         kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
-        out = _conv_forward(feats, kernel, km, transposed)
+        out = _conv_forward(feats, kernel, km, transposed, bf16)
         ctx.save_for_backward(feats, kernel)
-        ctx.km, ctx.transposed = km, transposed
+        ctx.km, ctx.transposed, ctx.bf16 = km, transposed, bf16
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         feats, kernel = ctx.saved_tensors
         grad_out = req(grad_out.contiguous(), F32, "conv3d grad", 2)
-        g_feats, g_kernel = _conv_backward(feats, kernel, ctx.km, ctx.transposed, grad_out, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return g_feats, g_kernel, None, None
+        g_feats, g_kernel = _conv_backward(feats, kernel, ctx.km, ctx.transposed, grad_out, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.bf16)
+        return g_feats, g_kernel, None, None, None
 
 
-def sparse_conv(feats, kernel, km, transposed=False):
-    return _SparseConv.apply(feats, kernel, km, transposed)
+def sparse_conv(feats, kernel, km, transposed=False, bf16=False):
+    """bf16=True: forward, data gradient and weight gradient on bf16-rounded operands with fp32 accumulation (include/ftx.h)."""
+    return _SparseConv.apply(feats, kernel, km, transposed, bool(bf16))
 
 
 # ---------------------------------------------------------------- dense rows (skinny GEMMs)
-def _rows_gemm(A, W, w_transposed, bias, co):
+def _rows_gemm(A, W, w_transposed, bias, co, bf16=False):
     L = _lib.load()
     n, ca = A.shape
     out = _empty((n, co), F32, A)
-    check(L.ftx_rows_gemm(ptr(A), n, ptr(W), int(w_transposed), ptr(bias), ca, co, ptr(out), stream()), "ftx_rows_gemm")
+    fn = _ROWS_GEMM[bool(bf16)]
+    check(getattr(L, fn)(ptr(A), n, ptr(W), int(w_transposed), ptr(bias), ca, co, ptr(out), stream()), fn)
     return out
 
 
-def _rows_wgrad(A, G):
+def _rows_wgrad(A, G, bf16=False):
     """A (n, ca)^T @ G (n, cg) -> (ca, cg)."""
     L = _lib.load()
+    fn, ws_fn, _ = _PAIRS_WGRAD[bool(bf16)]
     n, ca = A.shape
     cg = G.shape[1]
     dW = _empty((1, ca, cg), F32, A)
-    ws_bytes = _ws_bytes("ftx_spconv_pairs_wgrad_workspace_bytes", n, ca, cg, 1)
+    ws_bytes = _ws_bytes(ws_fn, n, ca, cg, 1)
     ws = _scratch(ws_bytes, A)
-    check(L.ftx_spconv_pairs_wgrad(ptr(A), n, 0, ptr(G), n, 0, 0, n, ca, cg, 1, ptr(dW), ptr(ws), ws_bytes, stream()), "ftx_spconv_pairs_wgrad(dense)")
+    check(getattr(L, fn)(ptr(A), n, 0, ptr(G), n, 0, 0, n, ca, cg, 1, ptr(dW), ptr(ws), ws_bytes, stream()), fn + "(dense)")
     return dW[0]
 
 
@@ -664,15 +679,15 @@ class _RowsLinear(torch.autograd.Function):
     """F.linear on (N, C) rows: out = x @ weight^T + bias, weight (co, ca) as nn.Linear stores it."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, bf16=False):
         x = req(x.contiguous(), F32, "linear x", 2)
         weight = req(weight.contiguous(), F32, "linear weight", 2)
         co, ca = weight.shape
         if x.shape[1] != ca:
             raise ValueError("linear: shape mismatch")
         ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        return _rows_gemm(x, weight, 1, bias, co)
+        ctx.has_bias, ctx.bf16 = bias is not None, bf16
+        return _rows_gemm(x, weight, 1, bias, co, bf16)
 
     @staticmethod
     def backward(ctx, go):
@@ -680,44 +695,77 @@ class _RowsLinear(torch.autograd.Function):
         go = req(go.contiguous(), F32, "linear grad", 2)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = _rows_gemm(go, weight, 0, None, weight.shape[1])
+            gx = _rows_gemm(go, weight, 0, None, weight.shape[1], ctx.bf16)
         if ctx.needs_input_grad[1]:
-            gw = _rows_wgrad(go, x)
+            gw = _rows_wgrad(go, x, ctx.bf16)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = colsum(go) if go.shape[1] % 4 == 0 else go.sum(0)
-        return gx, gw, gb
+        return gx, gw, gb, None
 
 
 class _RowsMatmul(torch.autograd.Function):
     """x (N, ca) @ kernel (ca, co): the kernel_size = 1 spnn.Conv3d."""
 
     @staticmethod
-    def forward(ctx, x, kernel):
+    def forward(ctx, x, kernel, bf16=False):
         x = req(x.contiguous(), F32, "matmul x", 2)
         kernel = req(kernel.contiguous(), F32, "matmul kernel", 2)
         ctx.save_for_backward(x, kernel)
-        return _rows_gemm(x, kernel, 0, None, kernel.shape[1])
+        ctx.bf16 = bf16
+        return _rows_gemm(x, kernel, 0, None, kernel.shape[1], bf16)
 
     @staticmethod
     def backward(ctx, go):
         x, kernel = ctx.saved_tensors
         go = req(go.contiguous(), F32, "matmul grad", 2)
-        gx = _rows_gemm(go, kernel, 1, None, kernel.shape[0]) if ctx.needs_input_grad[0] else None
-        gk = _rows_wgrad(x, go) if ctx.needs_input_grad[1] else None
-        return gx, gk
+        gx = _rows_gemm(go, kernel, 1, None, kernel.shape[0], ctx.bf16) if ctx.needs_input_grad[0] else None
+        gk = _rows_wgrad(x, go, ctx.bf16) if ctx.needs_input_grad[1] else None
+        return gx, gk, None
 
 
-def linear(x, weight, bias=None):
+def _bf16_round(t):
+    """t rounded to bf16 (round-to-nearest-even), held in fp32."""
+    return t.bfloat16().float()
+
+
+class _LibraryMatmulBf16(torch.autograd.Function):
+    """x @ w (+ bias) as a library GEMM on bf16-rounded operands with fp32 results, for the shapes the tile kernel does not take: the
+    contract of the bf16 kernels (forward: x and w rounded; data gradient: grad and w; weight gradient: grad and x; bias in fp32)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        xr, wr = _bf16_round(x), _bf16_round(w)
+        ctx.save_for_backward(xr, wr)
+        ctx.has_bias = bias is not None
+        out = torch.matmul(xr, wr)
+        return out + bias if bias is not None else out
+
+    @staticmethod
+    def backward(ctx, go):
+        xr, wr = ctx.saved_tensors
+        gr = _bf16_round(go)
+        gx = torch.matmul(gr, wr.t()) if ctx.needs_input_grad[0] else None
+        gw = torch.matmul(xr.reshape(-1, xr.shape[-1]).t(), gr.reshape(-1, gr.shape[-1])) if ctx.needs_input_grad[1] else None
+        gb = go.reshape(-1, go.shape[-1]).sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        return gx, gw, gb
+
+
+def linear(x, weight, bias=None, bf16=False):
     """nn.Linear on point / voxel rows.  Skinny shapes (tens of thousands of rows, <= 384 channels)
-    run on libftx's tile kernel; anything else is a plain library GEMM."""
+    run on libftx's tile kernel; anything else is a plain library GEMM.  bf16=True: x, weight (and in the backward the output
+    gradient) rounded to bf16 as GEMM operands, fp32 accumulation, on every shape."""
     if x.dim() == 2 and _rows_ok(x.shape[1], weight.shape[0]) and max(weight.shape) <= 512:
-        return _RowsLinear.apply(x, weight, bias)
+        return _RowsLinear.apply(x, weight, bias, bool(bf16))
+    if bf16:
+        return _LibraryMatmulBf16.apply(x, weight.t(), bias)
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def rows_matmul(x, kernel):
+def rows_matmul(x, kernel, bf16=False):
     if x.dim() == 2 and _rows_ok(*kernel.shape) and max(kernel.shape) <= 512:
-        return _RowsMatmul.apply(x, kernel)
+        return _RowsMatmul.apply(x, kernel, bool(bf16))
+    if bf16:
+        return _LibraryMatmulBf16.apply(x, kernel, None)
     return torch.matmul(x, kernel)
 
 
@@ -815,7 +863,7 @@ class _ConvBNTrain(torch.autograd.Function):
     stream's scratch buffer instead of six allocator round trips per layer and direction."""
 
     @staticmethod
-    def forward(ctx, feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu):
+    def forward(ctx, feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bf16=False):
         L = _lib.load()
         feats = req(feats.contiguous(), F32, "conv3d feats", 2)
         kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
@@ -833,14 +881,14 @@ class _ConvBNTrain(torch.autograd.Function):
         st = _stream_scratch()
         direct = (transposed and km.fine_bijective) or n_out == 0 or km.n_pairs == 0
         if direct:
-            x = _conv_forward(feats, kernel, km, transposed)
+            x = _conv_forward(feats, kernel, km, transposed, bf16)
             y = torch.empty_like(x)
             ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n_out, co)
             ws, = _carve(x, ws_bytes)
             _log_launch("bn_fwd", dict(n=n_out, c=co, reads=2 + (residual is not None), writes=1), lambda: check(L.ftx_bn_train_fwd(
                 ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum), float(eps),
                 n_out, co, int(relu), ptr(y), p_mean, p_invstd, ws, ws_bytes, st), "ftx_bn_train_fwd"))
-        elif not transposed and ostat_preferred(ca, co, kvol, rows=n_out):
+        elif not bf16 and not transposed and ostat_preferred(ca, co, kvol, rows=n_out):
             # thin layer: convolution + statistics in one launch, then the apply pass
             nb = _ws_bytes("ftx_spconv_ostat_blocks", n_out)
             part, = _carve(feats, 16 * (nb + 1) * co)
@@ -856,15 +904,16 @@ class _ConvBNTrain(torch.autograd.Function):
             nb = _ws_bytes("ftx_spconv_reduce_stats_blocks", n_out, co)
             tmp, part = _carve(feats, 4 * km.n_pairs * co, 16 * (nb + 1) * co)    # nb partial rows + the totals row, float64
             meta = dict(pairs=km.n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol)
-            _log_launch("spconv_pairs_gemm", meta, lambda: check(L.ftx_spconv_pairs_gemm(
-                ptr(feats), n_in, ptr(gather), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, tmp, st), "ftx_spconv_pairs_gemm"))
+            gemm, kind = _PAIRS_GEMM[bool(bf16)]
+            _log_launch(kind, meta, lambda: check(getattr(L, gemm)(
+                ptr(feats), n_in, ptr(gather), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, tmp, st), gemm))
             _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce_stats(
                 tmp, ptr(pos), n_out, co, kvol, ptr(x), part, nb, st), "ftx_spconv_reduce_stats"))
             _log_launch("bn_fwd", dict(n=n_out, c=co, reads=1 + (residual is not None), writes=1), lambda: check(L.ftx_bn_train_fwd_totals(
                 ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum),
                 float(eps), n_out, co, int(relu), ptr(y), p_mean, p_invstd, part + 16 * nb * co, st), "ftx_bn_train_fwd_totals"))
         ctx.save_for_backward(feats, kernel, x, y, gamma, beta, stats)
-        ctx.km, ctx.transposed, ctx.relu, ctx.has_res = km, transposed, int(relu), residual is not None
+        ctx.km, ctx.transposed, ctx.relu, ctx.has_res, ctx.bf16 = km, transposed, int(relu), residual is not None, bf16
         return y
 
     @staticmethod
@@ -876,6 +925,9 @@ class _ConvBNTrain(torch.autograd.Function):
         n, co = x.shape
         kvol, ca, _ = kernel.shape
         need_feats, need_kernel = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        bf16 = ctx.bf16
+        gemm, gemm_kind = _PAIRS_GEMM[bf16]
+        wgrad, wgrad_ws, wgrad_kind = _PAIRS_WGRAD[bf16]
         st = _stream_scratch()
         p_mean, p_invstd = stats.data_ptr(), stats.data_ptr() + 4 * co
         gparams = _empty((2, co), F32, x)               # row 0: d gamma, row 1: d beta
@@ -883,9 +935,9 @@ class _ConvBNTrain(torch.autograd.Function):
         bn_ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n, co)
         in_side, out_side = (km.pair_out, km.pair_in) if transposed else (km.pair_in, km.pair_out)
         direct = need_feats and (not transposed) and km.fine_bijective
-        ostat = need_feats and (not direct) and (not transposed) and km.submanifold and km.n_pairs > 0 and ostat_preferred(co, ca, kvol, True, rows=feats.shape[0])
+        ostat = need_feats and (not bf16) and (not direct) and (not transposed) and km.submanifold and km.n_pairs > 0 and ostat_preferred(co, ca, kvol, True, rows=feats.shape[0])
         n_feats = feats.shape[0]
-        wg_bytes = _ws_bytes("ftx_spconv_pairs_wgrad_workspace_bytes", km.n_pairs, ca, co, kvol) if (need_kernel and km.n_pairs > 0) else 0
+        wg_bytes = _ws_bytes(wgrad_ws, km.n_pairs, ca, co, kvol) if (need_kernel and km.n_pairs > 0) else 0
         tmp_bytes = 4 * km.n_pairs * ca if (need_feats and not direct and not ostat) else 0
         bn_ws, gx, tmp, wg_ws = _carve(x, bn_ws_bytes, 4 * n * co, tmp_bytes, wg_bytes)
         # BatchNorm half: gx = d loss / d (convolution output) stays in the scratch buffer, it is consumed by the two calls below
@@ -899,28 +951,30 @@ class _ConvBNTrain(torch.autograd.Function):
             if km.n_pairs == 0 or n_feats == 0:
                 g_feats.zero_()
             elif direct:
-                _log_launch("spconv_pairs_gemm", dict(meta, direct=True), lambda: check(L.ftx_spconv_pairs_gemm_scatter(
+                _log_launch(gemm_kind, dict(meta, direct=True), lambda: check(getattr(L, _PAIRS_GEMM_SCATTER[bf16])(
                     gx, n, ptr(km.pair_out), ptr(km.pair_in), ptr(kernel), 1, ptr(km.koff), km.n_pairs, co, ca, kvol, ptr(g_feats), n_feats, st),
-                    "ftx_spconv_pairs_gemm_scatter"))
+                    _PAIRS_GEMM_SCATTER[bf16]))
             elif ostat:
                 _log_launch("spconv_ostat", dict(meta, direct=True), lambda: check(L.ftx_spconv_ostat(
                     gx, n, ptr(km.nbr), n_feats, ptr(kernel), 1, 1, co, ca, kvol, ptr(g_feats), 0, 0, st), "ftx_spconv_ostat"))
             else:
                 pos_in = km.pos if transposed else km.pos_t
-                _log_launch("spconv_pairs_gemm", meta, lambda: check(L.ftx_spconv_pairs_gemm(
-                    gx, n, ptr(out_side), ptr(kernel), 1, ptr(km.koff), km.n_pairs, co, ca, kvol, tmp, st), "ftx_spconv_pairs_gemm"))
+                _log_launch(gemm_kind, meta, lambda: check(getattr(L, gemm)(
+                    gx, n, ptr(out_side), ptr(kernel), 1, ptr(km.koff), km.n_pairs, co, ca, kvol, tmp, st), gemm))
                 _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce(tmp, ptr(pos_in), n_feats, ca, kvol, ptr(g_feats), st), "ftx_spconv_reduce"))
         if need_kernel:
             g_kernel = _empty((kvol, ca, co), F32, x)
-            _log_launch("spconv_pairs_wgrad", dict(pairs=km.n_pairs, n_out=n, ca=ca, co=co, kvol=kvol), lambda: check(L.ftx_spconv_pairs_wgrad(
+            _log_launch(wgrad_kind, dict(pairs=km.n_pairs, n_out=n, ca=ca, co=co, kvol=kvol), lambda: check(getattr(L, wgrad)(
                 ptr(feats), n_feats, ptr(in_side), gx, n, ptr(out_side), ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(g_kernel), wg_ws, wg_bytes, st),
-                "ftx_spconv_pairs_wgrad"))
-        return g_feats, g_kernel, None, None, gres, gparams[0], gparams[1], None, None, None, None, None
+                wgrad))
+        return g_feats, g_kernel, None, None, gres, gparams[0], gparams[1], None, None, None, None, None, None
 
 
-def conv_bn_train(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, residual=None, relu=False):
-    """Conv3d -> BatchNorm(training) (+ residual) (+ ReLU) in one autograd node; see _ConvBNTrain."""
-    return _ConvBNTrain.apply(feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu)
+def conv_bn_train(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, residual=None, relu=False,
+                  bf16=False):
+    """Conv3d -> BatchNorm(training) (+ residual) (+ ReLU) in one autograd node; see _ConvBNTrain.  bf16=True: the convolution's
+    forward, data gradient and weight gradient on bf16-rounded operands (as sparse_conv(bf16=True)); BatchNorm stays fp32."""
+    return _ConvBNTrain.apply(feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bool(bf16))
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, residual=None, relu=False):

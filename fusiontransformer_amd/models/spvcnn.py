@@ -45,20 +45,21 @@ class Conv3d(nn.Module):
 
     def forward(self, x: SparseTensor) -> SparseTensor:
         ks, s = self.kernel_size, self.stride
+        bf16 = getattr(self, "ftx_bf16", False)   # SPVCNN.set_bf16: bf16-operand kernels
         if ks == 1 and s == 1:
-            out = x.derive(spf.rows_matmul(x.F, self.kernel))
+            out = x.derive(spf.rows_matmul(x.F, self.kernel, bf16=bf16))
             out.check()
             return out
         if not self.t:
             km = x.cm.kernel_map(ks, x.s, s)
-            feats = spf.sparse_conv(x.F, self.kernel, km, False)
+            feats = spf.sparse_conv(x.F, self.kernel, km, False, bf16=bf16)
             out = x.derive(feats, km.out_coords, x.s * s)
         else:
             original_stride = x.s // s
             km = x.cm.kernel_maps.get((ks, original_stride, s))
             if km is None:
                 raise RuntimeError("transposed Conv3d needs the kernel map of the paired strided Conv3d")
-            feats = spf.sparse_conv(x.F, self.kernel, km, True)
+            feats = spf.sparse_conv(x.F, self.kernel, km, True, bf16=bf16)
             out = x.derive(feats, x.cm.coords[original_stride], original_stride)
         out.check()
         return out
@@ -105,7 +106,7 @@ def _conv_bn(conv, bn, x, residual=None, relu=True):
         if bn.track_running_stats and bn.num_batches_tracked is not None and not getattr(bn, "_nbt_external", False):
             bn.num_batches_tracked.add_(1)
         feats = spf.conv_bn_train(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                  residual=residual, relu=relu)
+                                  residual=residual, relu=relu, bf16=getattr(conv, "ftx_bf16", False))
         out = x.derive(feats, coords, stride)
         out.check()
         return out
@@ -115,7 +116,7 @@ def _conv_bn(conv, bn, x, residual=None, relu=True):
 
 def _linear_bn_relu(seq, feats):
     """nn.Sequential(Linear, BatchNorm1d, ReLU) on point rows (spvcnn.py:164-180)."""
-    return seq[1].fused(spf.linear(feats, seq[0].weight, seq[0].bias), relu=True)
+    return seq[1].fused(spf.linear(feats, seq[0].weight, seq[0].bias, bf16=getattr(seq[0], "ftx_bf16", False)), relu=True)
 
 
 class BasicConvolutionBlock(nn.Module):
@@ -201,9 +202,29 @@ class SPVCNN(nn.Module):
         ])
         self.weight_initialization()
         self.dropout = nn.Dropout(0.3, True)
+        # cfg.MODEL.lidar_bf16 (default: environment FTX_LIDAR_BF16=1): the LiDAR branch on bf16-operand kernels, see set_bf16
+        self.lidar_bf16 = bool(kwargs.get("lidar_bf16", os.environ.get("FTX_LIDAR_BF16", "0") == "1"))
+        self.set_bf16(self.lidar_bf16)
         # optional injected keep-masks {'y1': (N4,C), 'y3': (N2,C)} so a train-mode run can be
         # compared with the oracle (Dropout RNG streams differ between CPU and GPU)
         self.dropout_masks = None
+
+    # the point-branch Linears of the fusion models (early / middle_fusion.py) that set_bf16 switches with the U-Net
+    _FUSION_TRANSFORMS = ("early_fusion_transform", "middle_fusion_transform")
+
+    def set_bf16(self, on=True):
+        """bf16-operand mode of the LiDAR branch: every Conv3d (sparse convolutions and the 1x1x1 ones) and the nn.Linear of
+        point_transforms and of the early / middle fusion transform run their forward, data gradient and weight gradient with the GEMM
+        operands rounded to bf16 and fp32 accumulation (include/ftx.h).  BatchNorm, the reduce over offsets and all storage stay fp32.
+        The segmentation heads (`linear`, `linear2`) stay fp32.  Subclasses that add a fusion transform call this again after adding it."""
+        self.lidar_bf16 = bool(on)
+        for m in self.modules():
+            if isinstance(m, Conv3d):
+                m.ftx_bf16 = bool(on)
+        seqs = list(self.point_transforms) + [getattr(self, n) for n in self._FUSION_TRANSFORMS if hasattr(self, n)]
+        for seq in seqs:
+            seq[0].ftx_bf16 = bool(on)
+        return self
 
     def weight_initialization(self):
         for m in self.modules():

@@ -250,6 +250,22 @@ int ftx_spconv_pairs_wgrad(const float *A, int64_t rows_a, const int32_t *idx_a,
 int32_t ftx_spconv_wgrad_resident_blocks(int32_t ca, int32_t cg);
 int32_t ftx_spconv_wgrad_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng);
 
+/* bf16-operand sparse convolution (csrc/ftx_spconv_bf16.hip): the same calls, with the same arguments, on v_mfma_f32_32x32x16_bf16.
+ * Precision contract: the MFMA operands -- A and W of the pair GEMM and of the dense rows, A and G of the weight gradient -- are rounded
+ * to bf16 (round-to-nearest-even) from their stored fp32 values as they are staged; nothing else is rounded.  Accumulation is fp32, and
+ * all storage stays fp32: A, W, G, bias, out, dW and the pair rows `tmp`, which keep the layout of ftx_spconv_pairs_gemm, so
+ * ftx_spconv_reduce / ftx_spconv_reduce_stats consume them unchanged (fixed summation order over offsets).  The bias is added in
+ * fp32.  Gather rules as above: an out-of-range source index gives a zero row.  No atomics: results are deterministic, the weight
+ * gradient's partial tiles are added in a fixed order, and tile shapes and workspace sizes are functions of the arguments alone. */
+int ftx_spconv_pairs_gemm_bf16(const float *A, int64_t rows_a, const int32_t *gather, const float *W, int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *tmp, void *stream);
+int ftx_spconv_pairs_gemm_scatter_bf16(const float *A, int64_t rows_a, const int32_t *gather, const int32_t *scatter, const float *W, int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *out, int64_t rows_out, void *stream);
+int ftx_rows_gemm_bf16(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co, float *out, void *stream);
+size_t ftx_spconv_pairs_wgrad_bf16_workspace_bytes(int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol);
+int ftx_spconv_pairs_wgrad_bf16(const float *A, int64_t rows_a, const int32_t *idx_a, const float *G, int64_t rows_g, const int32_t *idx_g, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol, float *dW, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only queries, as ftx_spconv_gemm_block_cols / ftx_spconv_wgrad_table_blocks, for the bf16 kernels' own tilings. */
+int32_t ftx_spconv_gemm_bf16_block_cols(int32_t co, int64_t n_pairs, int32_t kvol);
+int32_t ftx_spconv_wgrad_bf16_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng);
+
 /* ---- BatchNorm1d over rows (+residual, +ReLU): spnn.BatchNorm / nn.BatchNorm1d
  *      models/spvcnn.py:30-31,71-79,100-102,164-180; models/middle_fusion.py:18-22 */
 

@@ -1,5 +1,7 @@
 """Per-layer micro-benchmark of the sparse-conv kernels on the bench workload's real kernel maps.
-usage (GPU box): python tools/bench_spconv.py [--batch 4]"""
+usage (GPU box): python tools/bench_spconv.py [--batch 4] [--bf16]
+--bf16: also time the bf16-operand pair GEMM and weight gradient (csrc/ftx_spconv_bf16.hip) on the same operands, in the same process,
+and print them next to the fp32 kernels per layer."""
 import argparse, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +13,7 @@ from fusiontransformer_amd.sparse import PointTensor
 ap = argparse.ArgumentParser(); ap.add_argument("--batch", type=int, default=4); ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--filter", default="", help="only layers whose name contains one of these comma-separated substrings")
 ap.add_argument("--what", default="gemm,reduce,wgrad,ostat", help="kernels to run (profiling runs: --what wgrad --iters 1)")
+ap.add_argument("--bf16", action="store_true", help="also time the bf16-operand GEMM and weight gradient per layer")
 args = ap.parse_args()
 WHAT = set(args.what.split(","))
 b = make_batch(list(range(args.batch)))
@@ -42,6 +45,7 @@ def timeit(fn, on=True):
 print("%-24s %9s %9s | %8s %8s %8s %8s %8s | %7s %7s | %8s %9s" % ("layer", "rows", "pairs", "gemm us", "reduce", "ostat", "ostat dg", "wgrad", "gemmTF", "wgradTF", "roof us", "fwd/roof"))
 tot = [0, 0, 0]
 tot_os = [0.0, 0.0, 0.0, 0.0]    # forward as shipped (ostat where supported), the same layers on the pair path, roof of forward, roof of wgrad
+bf_rows = []     # (name, pairs, fp32 forward as shipped, fp32 gemm, bf16 gemm, reduce, fp32 wgrad, bf16 wgrad) for --bf16
 for name, ks, cur, st, ca, co in layers:
     if args.filter and not any(f in name for f in args.filter.split(",")):
         continue
@@ -66,9 +70,30 @@ for name, ks, cur, st, ca, co in layers:
     roof = 1e6 * max((4.0 * km.n_pairs * (ca + co) + 4.0 * ks ** 3 * ca * co) / HBM, fl / MFMA)     # the launch's binding roof, us
     fwd = t_o if (t_o == t_o and spf.ostat_preferred(ca, co, ks ** 3)) else t_g + t_r     # what the host wrapper launches for this layer
     print("%-24s %9d %9d | %8.1f %8.1f %8.1f %8.1f %8.1f | %7.1f %7.1f | %8.1f %9.2f" % (name, km.n_out, km.n_pairs, t_g, t_r, t_o, t_od, t_w, fl / t_g / 1e6, fl / t_w / 1e6, roof, roof / fwd))
+    if args.bf16:
+        t_gb = timeit(lambda: L.ftx_spconv_pairs_gemm_bf16(A.data_ptr(), km.n_in, km.pair_in.data_ptr(), W.data_ptr(), int(os.environ.get("FTX_BENCH_WT", "0")), km.koff.data_ptr(), km.n_pairs, ca, co, ks ** 3, tmp.data_ptr(), spf.stream()), "gemm" in WHAT)
+        wsb_bytes = int(L.ftx_spconv_pairs_wgrad_bf16_workspace_bytes(km.n_pairs, ca, co, ks ** 3))
+        wsb = torch.empty(wsb_bytes, dtype=torch.uint8, device="cuda")
+        t_wb = timeit(lambda: L.ftx_spconv_pairs_wgrad_bf16(A.data_ptr(), km.n_in, km.pair_in.data_ptr(), G.data_ptr(), km.n_out, km.pair_out.data_ptr(), km.koff.data_ptr(),
+                                                             km.n_pairs, ca, co, ks ** 3, dW.data_ptr(), wsb.data_ptr(), wsb_bytes, spf.stream()), "wgrad" in WHAT)
+        bf_rows.append((name, km.n_pairs, fwd, t_g, t_gb, t_r, t_w, t_wb))
     tot[0] += t_g; tot[1] += t_r; tot[2] += t_w
     tot_os[0] += fwd; tot_os[1] += t_g + t_r; tot_os[2] += roof; tot_os[3] += roof
 print("sum: gemm %.0f us  reduce %.0f us  wgrad %.0f us" % tuple(tot))
 print("forward as shipped (ostat where it applies) %.0f us, all on the pair-list path %.0f us" % (tot_os[0], tot_os[1]))
 print("binding-roof fraction over these layers, forward + weight gradient: %.3f (sum of max(bytes / 8 TB/s, flop / 157.3 TF) / sum of time)"
       % ((tot_os[2] + tot_os[3]) / (tot_os[0] + tot[2])))
+
+if args.bf16:
+    # fp32 fwd = the forward as the fp32 path launches it (output-stationary kernel where preferred, else pair GEMM + reduce); bf16 mode
+    # has no output-stationary form, so its forward is always bf16 pair GEMM + the same reduce.  gemm / wgrad columns: the kernels alone.
+    print()
+    print("%-24s %9s | %9s %9s %6s | %9s %9s %6s | %9s %9s %6s" % ("layer", "pairs", "fp32 fwd", "bf16 fwd", "x", "fp32 gemm", "bf16 gemm", "x",
+                                                                  "fp32 wgrd", "bf16 wgrd", "x"))
+    t = [0.0] * 6
+    for name, pairs, f_fwd, f_g, b_g, r, f_w, b_w in bf_rows:
+        v = (f_fwd, b_g + r, f_g, b_g, f_w, b_w)
+        print("%-24s %9d | %9.1f %9.1f %6.2f | %9.1f %9.1f %6.2f | %9.1f %9.1f %6.2f" % (name, pairs, v[0], v[1], v[0] / v[1], v[2], v[3], v[2] / v[3], v[4], v[5], v[4] / v[5]))
+        t = [a + b for a, b in zip(t, v)]
+    print("%-24s %9s | %9.1f %9.1f %6.2f | %9.1f %9.1f %6.2f | %9.1f %9.1f %6.2f" % ("total", "", t[0], t[1], t[0] / t[1], t[2], t[3], t[2] / t[3], t[4], t[5], t[4] / t[5]))
+    print("forward + weight gradient over these layers: fp32 %.0f us, bf16 %.0f us" % (t[0] + t[4], t[1] + t[5]))
