@@ -12,6 +12,8 @@ kernel when `attn_impl == "ftx"` (exact fp32) or `"ftx_bf16"` (bf16 operands, fp
 functional.attention(bf16=True)), otherwise as the three explicit ops timm uses."""
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 from functools import partial
 from typing import Dict
@@ -100,7 +102,11 @@ def _over_batch(p, b):
 def _linear(x, lin, with_bias=True):
     if lin.bias is None or not x.is_cuda:
         return F.linear(x, lin.weight, lin.bias if with_bias else None)
-    return _LinearFn.apply(x, lin.weight, lin.bias if with_bias else None, getattr(lin, "ftx_bf16", False))
+    bf16 = getattr(lin, "ftx_bf16", False)
+    if bf16 and getattr(lin, "ftx_linear_impl", "library") == "ftx":
+        from .. import functional as spf
+        return spf.vit_linear(x, lin.weight, lin.bias if with_bias else None)   # library path for shapes the kernels do not take
+    return _LinearFn.apply(x, lin.weight, lin.bias if with_bias else None, bf16)
 
 
 class Mlp(nn.Module):
@@ -112,7 +118,18 @@ class Mlp(nn.Module):
         self.drop = nn.Dropout(drop)
 
     def forward(self, x, with_fc2_bias=True):
+        if self._fused_ftx(x):
+            # vit_linear_impl "ftx": fc1 + GELU + fc2 as one node on the bf16 kernels (GELU in fc1's epilogue, its derivative in fc2's dX)
+            from .. import functional as spf
+            return spf.vit_mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias if with_fc2_bias else None)
         return self.drop(_linear(self.drop(self.act(_linear(x, self.fc1))), self.fc2, with_fc2_bias))
+
+    def _fused_ftx(self, x):
+        fc1, fc2 = self.fc1, self.fc2
+        return (x.is_cuda and getattr(fc1, "ftx_bf16", False) and getattr(fc2, "ftx_bf16", False)
+                and getattr(fc1, "ftx_linear_impl", "library") == "ftx" and getattr(fc2, "ftx_linear_impl", "library") == "ftx"
+                and type(self.act) is nn.GELU and self.act.approximate == "none" and self.drop.p == 0.0
+                and fc1.bias is not None and fc2.bias is not None)
 
 
 class Attention(nn.Module):
@@ -275,6 +292,16 @@ class Image2DTransformer(nn.Module):
             for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
                 lin.ftx_bf16 = bool(on)
 
+    def set_linear_impl(self, impl: str):
+        """How the bf16 qkv / proj / fc1 / fc2 GEMMs run: "library" (torch's bf16 GEMMs, bf16 results widened to fp32, separate cast,
+        bias and GELU kernels) or "ftx" (libftx's ftx_dense_* kernels: bf16 operands, fp32 accumulation and fp32 results, bias and GELU
+        fused into the GEMM epilogues).  Precision is still switched by set_bf16: with set_bf16(False) this setting changes nothing."""
+        if impl not in ("library", "ftx"):
+            raise ValueError(f"vit_linear_impl must be 'library' or 'ftx', got {impl!r}")
+        for blk in self.blocks:
+            for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
+                lin.ftx_linear_impl = impl
+
     def set_attention_impl(self, impl: str):
         for blk in self.blocks:
             blk.attn.attn_impl = impl
@@ -365,8 +392,8 @@ class Image2DTransformer(nn.Module):
     def _graph_key(self, x):
         """Everything a captured graph bakes in: input shape / dtype / requires_grad, the tap set and segment length, the
         per-block execution flags and the parameters' requires_grad pattern.  Changing any of them selects another graph."""
-        flags = tuple((blk.attn.attn_impl, bool(getattr(blk.attn.qkv, "ftx_bf16", False)), bool(getattr(blk.mlp.fc1, "ftx_bf16", False)))
-                      for blk in self.blocks)
+        flags = tuple((blk.attn.attn_impl, bool(getattr(blk.attn.qkv, "ftx_bf16", False)), bool(getattr(blk.mlp.fc1, "ftx_bf16", False)),
+                       _linear_impls(blk)) for blk in self.blocks)
         grads = tuple(p.requires_grad for p in self.parameters())
         return (tuple(x.shape), x.dtype, bool(x.requires_grad), tuple(self.graph_taps), self.last_block, self.graph_segment_blocks,
                 flags, grads, torch.cuda.current_device())
@@ -406,7 +433,8 @@ class Image2DTransformer(nn.Module):
                 or torch.cuda.is_current_stream_capturing()):
             return None
         cache = self.__dict__.setdefault("_infer_cache", {})
-        flags = tuple((blk.attn.attn_impl, bool(getattr(blk.attn.qkv, "ftx_bf16", False))) for blk in self.blocks)
+        flags = tuple((blk.attn.attn_impl, bool(getattr(blk.attn.qkv, "ftx_bf16", False)), bool(getattr(blk.mlp.fc1, "ftx_bf16", False)),
+                       _linear_impls(blk)) for blk in self.blocks)
         key = (tuple(x.shape), x.dtype, tuple(self.graph_taps), self.last_block, flags, torch.cuda.current_device())
         if key not in cache:
             try:
@@ -435,7 +463,7 @@ class Image2DTransformer(nn.Module):
                 run(static_in)                                  # warm-up: lazy initialisation, TunableOp selections, scratch growth
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph):
+        with _no_gc(), torch.no_grad(), torch.cuda.graph(graph):
             static_out = run(static_in)
 
         def replay(inp):
@@ -491,9 +519,29 @@ class Image2DTransformer(nn.Module):
             for seg in segments[1:]:
                 samples.append((h.detach().clone().requires_grad_(True),))
                 h = seg(h)
-        graphed = torch.cuda.make_graphed_callables(tuple(segments), tuple(samples), num_warmup_iters=3)
+        with _no_gc():
+            graphed = torch.cuda.make_graphed_callables(tuple(segments), tuple(samples), num_warmup_iters=3)
         taps_set = set(taps)
         return [(e, g, e in taps_set) for e, g in zip(ends, graphed)]
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """Python's cyclic garbage collector off while a trunk graph is captured: a collection that starts inside the capture can finalise
+    an earlier object that releases a GPU resource, which the runtime refuses during capture (an abort, not an exception)."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
+def _linear_impls(blk):
+    """The vit_linear_impl of a block's four Linears (part of the graph keys: it selects other kernels)."""
+    return tuple(getattr(lin, "ftx_linear_impl", "library") for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2))
 
 
 class _TrunkSegment(nn.Module):

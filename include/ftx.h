@@ -340,6 +340,33 @@ int ftx_attn_bwd_tiled(const float *qkv, const float *out, const float *grad_out
 int ftx_attn_fwd_bf16(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw, int32_t split, void *stream);
 int ftx_attn_bwd_bf16(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split, void *stream);
 
+/* ---- bf16-operand ViT Linears (timm Mlp / Attention qkv, proj, fc1, fc2: models/transformers.py:36-55) (csrc/ftx_dense_bf16.hip) ----
+ * Precision contract: the MFMA operands -- A and W of the GEMM, dY and X of the weight gradient -- are rounded to bf16
+ * (round-to-nearest-even) from their stored fp32 values as they are staged; nothing else is rounded.  Accumulation is fp32
+ * (v_mfma_f32_32x32x16_bf16), and all storage stays fp32: A, W, bias, out, pre_in / pre_out and dW.  Bias, GELU and the GELU
+ * derivative are applied in fp32 to the fp32 sum.  No atomics: results are deterministic, the split weight gradient's partials are
+ * added in a fixed order, and tiles, splits and workspace sizes are functions of the arguments alone.
+ *
+ * GEMM: out (m, n) = epilogue(A (m, k) . B), B = W^T with W (n, k) as nn.Linear stores it (w_kn = 0, the forward) or B = W with W
+ * stored (k, n) (w_kn = 1, the data gradient dX = dY W).  k % 64 == 0, n % 4 == 0, every pointer 16-byte aligned.  Epilogues:
+ *   FTX_EPI_NONE       out = sum
+ *   FTX_EPI_BIAS       out = sum + bias (n)
+ *   FTX_EPI_BIAS_GELU  pre_out = sum + bias, out = gelu(pre_out) (exact erf GELU, nn.GELU())
+ *   FTX_EPI_DGELU      out = sum * gelu'(pre_in), pre_in (m, n) the saved pre-activation: fc1's output gradient straight from fc2's dX
+ * Pointers an epilogue does not use are ignored.  m == 0 returns FTX_OK without launching. */
+#define FTX_EPI_NONE 0
+#define FTX_EPI_BIAS 1
+#define FTX_EPI_BIAS_GELU 2
+#define FTX_EPI_DGELU 3
+int ftx_dense_gemm_bf16(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n, int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream);
+/* Weight gradient: dW (n, k) = dY^T X over the m rows of dY (m, n) and X (m, k); n % 4 == 0, k % 4 == 0.  m == 0 zeroes dW.  The
+ * rows are split for small tile counts (ftx_dense_bf16_tile); workspace: ftx_dense_wgrad_bf16_workspace_bytes(m, n, k). */
+size_t ftx_dense_wgrad_bf16_workspace_bytes(int64_t m, int32_t n, int32_t k);
+int ftx_dense_wgrad_bf16(const float *dY, const float *X, int64_t m, int32_t n, int32_t k, float *dW, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: the tile (rows x columns of the output) and the row split a launch of `form` (0: GEMM, out (m, n); 1: weight gradient,
+ * dW (n, k) over m rows) picks.  Launches nothing. */
+int ftx_dense_bf16_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host);
+
 /* ---- fused train-step losses + metric: modules/SemanticTrainer.py:158-194, models/metric.py:37-58 ----
  * losses[0] = loss_2d = CE_w(img_logit) + lambda * KL(softmax(lidar_logit) || softmax(img_logit2))
  * losses[1] = loss_3d = CE_w(lidar_logit) + lambda * KL(softmax(img_logit) || softmax(lidar_logit2))
