@@ -1398,17 +1398,38 @@ def sample_down(img, conv_w, conv_b, gamma, beta, running_mean, running_var, mom
 class _FusionLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, l3, l2, l3b, l2b, label, class_weights, lambda_xm, conf3d, conf2d, ignore_index, ce_scale=1.0):
-        L = _lib.load()
+        # every operand is checked before anything is launched: the kernel reads C class weights, n rows of all four heads and
+        # adds 64-bit counts into C x C cells of each matrix
         l3 = req(l3.contiguous(), F32, "loss lidar_seg_logit", 2)
         l2 = req(l2.contiguous(), F32, "loss img_seg_logit", 2)
         n, c = l3.shape
-        if l2.shape != (n, c) or label.shape[0] != n:
-            raise ValueError("fusion_loss: shape mismatch")
-        dual = l3b is not None
+        if l2.shape != (n, c):
+            raise ValueError("fusion_loss: img_seg_logit must be (%d, %d), got %s" % (n, c, tuple(l2.shape)))
+        dual = l3b is not None or l2b is not None
         if dual:
+            if l3b is None or l2b is None:
+                raise ValueError("fusion_loss: the dual head needs both second heads")
             l3b = req(l3b.contiguous(), F32, "loss lidar_seg_logit2", 2)
             l2b = req(l2b.contiguous(), F32, "loss img_seg_logit2", 2)
+            for t, name in ((l3b, "lidar_seg_logit2"), (l2b, "img_seg_logit2")):
+                if t.shape != (n, c):
+                    raise ValueError("fusion_loss: %s must be (%d, %d), got %s" % (name, n, c, tuple(t.shape)))
         label = req(label.contiguous(), I64, "loss label", 1)
+        if label.shape[0] != n:
+            raise ValueError("fusion_loss: label must have %d entries, got %d" % (n, label.shape[0]))
+        if class_weights is not None:
+            req(class_weights, F32, "loss class_weights", 1)
+            if class_weights.shape[0] != c:
+                raise ValueError("fusion_loss: class_weights must have %d entries, got %d" % (c, class_weights.shape[0]))
+        for t, name in ((conf3d, "conf3d"), (conf2d, "conf2d")):
+            if t is not None:
+                req(t, I64, "fusion_loss " + name, 2)
+                if tuple(t.shape) != (c, c):
+                    raise ValueError("fusion_loss: %s must be (%d, %d), got %s" % (name, c, c, tuple(t.shape)))
+        for t in (l2, l3b, l2b, label, class_weights, conf3d, conf2d):
+            if t is not None and t.device != l3.device:
+                raise ValueError("fusion_loss: every operand must be on %s" % l3.device)
+        L = _lib.load()
         losses = _empty((2,), F32, l3)
         g3, g2 = torch.empty_like(l3), torch.empty_like(l2)
         g3b = torch.empty_like(l3) if dual else None

@@ -106,8 +106,13 @@ class TrainStep:
             self.optimizer.zero_grad(set_to_none=True)    # first write of each gradient is a move, not fill + add
         preds = self.model(data_batch)
         logits = preds["lidar_seg_logit"]
-        if self.fused_loss and logits.is_cuda and logits.shape[1] % 4 == 0 and logits.shape[1] <= 32:
+        c = logits.shape[1]
+        # the kernel counts one C x C matrix per head under one ignore index: metrics of another size or with differing ignore
+        # indices are updated by the host path
+        fits = all(m.num_classes == c for m in self.metrics) and len({m.ignore_index for m in self.metrics}) <= 1
+        if self.fused_loss and fits and logits.is_cuda and c % 4 == 0 and c <= 32:
             # one fused pass: CE x2 + KL x2 + their gradients + both SegIoU confusion matrices (libftx)
+            ignore_index = self.metrics[0].ignore_index if self.metrics else 0
             conf = {"3d": None, "2d": None}
             for m in self.metrics:
                 if m.mat is None:
@@ -115,7 +120,7 @@ class TrainStep:
                 conf["3d" if "3d" in m.name else "2d"] = m.mat
             from . import functional as spf
             loss_2d, loss_3d = spf.fusion_loss(preds, data_batch["seg_label"], self.class_weights, self.lambda_xm, self.dual_head,
-                                               conf3d=conf["3d"], conf2d=conf["2d"], mix=self.loss_mix)
+                                               conf3d=conf["3d"], conf2d=conf["2d"], ignore_index=ignore_index, mix=self.loss_mix)
         else:
             loss_2d, loss_3d = fusion_losses(preds, data_batch["seg_label"], self.class_weights, self.lambda_xm, self.dual_head, self.loss_mix)
             with torch.no_grad():
