@@ -70,7 +70,8 @@ extern "C" int ftx_voxelize_bwd(const float *grad_out, const int32_t *idx, const
                                 float *grad_feats, void *stream) {
   FTX_REQUIRE(n >= 0 && m >= 0 && c >= 1, "ftx_voxelize_bwd: bad size");
   if (n == 0) return FTX_OK;
-  FTX_REQUIRE(grad_out && idx && counts && grad_feats, "ftx_voxelize_bwd: null pointer");
+  // m == 0: no voxel, every point's gradient is zero and neither grad_out nor counts is read (both may be empty, i.e. null)
+  FTX_REQUIRE(idx && grad_feats && ((grad_out && counts) || m == 0), "ftx_voxelize_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   if (c % 4 == 0)
     voxelize_bwd_kernel<4><<<grid_for(n * (c / 4), 256), 256, 0, st>>>(grad_out, idx, counts, n, c, m, grad_feats);
