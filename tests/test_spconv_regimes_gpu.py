@@ -22,11 +22,10 @@ import pytest
 import torch
 
 from tests import spconv_regimes as S
+from tests.norm_ref import (U, WORST, check, conv_check, conv_mutants, conv_ref, gen, probe_pair, randn, ratio,  # noqa: F401
+                            wgrad_bound_m, wgrad_check, wgrad_mutants, wgrad_ref)
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-WORST = {}      # kernel -> worst ratio of error to bound, printed at the end of the module
 
 
 @pytest.fixture(scope="module")
@@ -36,115 +35,6 @@ def env():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     yield spf, _lib.load()
     print("\nworst error / bound per kernel: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(WORST.items())))
-
-
-def ratio(got, ref, bound):
-    """max |got - ref| / bound (float64); an element whose bound is 0 must match exactly."""
-    d = (got.double() - ref).abs()
-    if bool(((bound <= 0) & (d > 0)).any()):
-        return float("inf")
-    r = torch.where(bound > 0, d / bound.clamp_min(1e-300), torch.zeros_like(d))
-    return float(r.max()) if r.numel() else 0.0
-
-
-def check(kernel, what, got, ref, bound, mutants):
-    """The gate on got, and on each mutant of the reference: a mutant is a list of (index, delta) parts, ref[index] + delta."""
-    got = got.detach().cpu()
-    ref, bound = ref.detach(), bound.detach()
-    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
-    r = ratio(got, ref, bound)
-    WORST[kernel] = max(WORST.get(kernel, 0.0), r)
-    assert r <= 1.0, f"{what}: error is {r:.3g} x the bound"
-    assert len(mutants) == 2
-    for i, parts in enumerate(mutants):
-        assert any(ratio(ref[ix] + dl, ref[ix], bound[ix]) > 1.0 for ix, dl in parts), f"{what}: the gate accepts mutant {i}"
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def randn(g, *shape, scale=1.0):
-    return (torch.randn(*shape, generator=g) * scale).float()
-
-
-# ---------------------------------------------------------------- float64 references
-def conv_ref(A, W, src, dst, koff, n_dst):
-    """out[dst[p]] += A[src[p]] @ W[k(p)], one offset at a time (W oriented (kvol, c_in, c_out))."""
-    out = torch.zeros(n_dst, W.shape[2], dtype=torch.float64)
-    for k in range(W.shape[0]):
-        s, e = int(koff[k]), int(koff[k + 1])
-        if e > s:
-            out.index_add_(0, dst[s:e], A[src[s:e]] @ W[k])
-    return out
-
-
-def wgrad_ref(A, ia, G, ig, koff):
-    kvol = koff.shape[0] - 1
-    out = torch.zeros(kvol, A.shape[1], G.shape[1], dtype=torch.float64)
-    for k in range(kvol):
-        s, e = int(koff[k]), int(koff[k + 1])
-        if e > s:
-            out[k] = A[ia[s:e]].T @ G[ig[s:e]]
-    return out
-
-
-def probe_pair(koff):
-    """(pair in the middle of the largest offset, its offset, the neighbouring offset)."""
-    cnt = (koff[1:] - koff[:-1])
-    k = int(torch.argmax(cnt))
-    kn = k + 1 if k + 1 < cnt.shape[0] else k - 1
-    return int(koff[k]) + int(cnt[k]) // 2, k, kn
-
-
-def conv_mutants(A, W, src, dst, koff):
-    p, k, kn = probe_pair(koff)
-    a, o = A[src[p]], int(dst[p])
-    c = a @ W[k]
-    return [[((o,), -c)], [((o,), a @ W[kn] - c)]]
-
-
-def wgrad_mutants(A, ia, G, ig, koff):
-    p, k, kn = probe_pair(koff)
-    # of the 64 pairs around the middle, the one with the largest contribution
-    lo, hi = max(int(koff[k]), p - 32), min(int(koff[k + 1]) - 1, p + 32)
-    w = torch.arange(lo, hi)
-    p = int(w[torch.argmax(A[ia[w]].abs().amax(1) * G[ig[w]].abs().amax(1))])
-    outer = torch.outer(A[ia[p]], G[ig[p]])
-    if koff.shape[0] == 2:    # one offset (dense rows): the pair credited with the next pair's G row instead
-        return [[((k,), -outer)], [((k,), torch.outer(A[ia[p]], G[ig[p + 1]]) - outer)]]
-    return [[((k,), -outer)], [((k,), -outer), ((kn,), outer)]]
-
-
-def conv_check(kernel, what, got, A, W, src, dst, koff, n_dst):
-    """Pair GEMM (+ reduce): float64 reference, bound with m = c_in + kvol, and the two mutants."""
-    A, W = A.double(), W.double()
-    ref = conv_ref(A, W, src, dst, koff, n_dst)
-    bound = (W.shape[1] + W.shape[0] + 8) * U * conv_ref(A.abs(), W.abs(), src, dst, koff, n_dst)
-    check(kernel, what, got, ref, bound, conv_mutants(A, W, src, dst, koff))
-    return ref
-
-
-def wgrad_bound_m(lib, koff, ca, cg):
-    """Longest addition chain into dW[k] per offset for the weight gradient's tiling: tile_len + tiles of the offset + 16."""
-    kvol = koff.shape[0] - 1
-    n = int(koff[-1])
-    length = S.wgrad_tile_len(lib, n, ca, cg, kvol)
-    tiles = (koff[1:] - koff[:-1] + length - 1) // length
-    return (length + tiles + 16).double().view(kvol, 1, 1)
-
-
-def wgrad_check(lib, kernel, what, got, A, ia, G, ig, koff, extra=None):
-    """Weight gradient: float64 reference, bound with m = wgrad_bound_m, and the two mutants.  `extra`: a bound on the error G itself
-    carries (G computed in float32 by an earlier kernel), added to the bound as sum over pairs of |A| * extra."""
-    A, G = A.double(), G.double()
-    ref = wgrad_ref(A, ia, G, ig, koff)
-    m = wgrad_bound_m(lib, koff, A.shape[1], G.shape[1])
-    bound = (m + 8) * U * wgrad_ref(A.abs(), ia, G.abs(), ig, koff)
-    if extra is not None:
-        bound = bound + wgrad_ref(A.abs(), ia, extra, ig, koff)
-    check(kernel, what, got, ref, bound, wgrad_mutants(A, ia, G, ig, koff))
-    return ref
 
 
 # ---------------------------------------------------------------- pair lists
