@@ -8,10 +8,17 @@ points runs on the GPU with numpy's float32 / float64 rounding (`augment_and_sca
 the build container (tests/golden/voxel_coords_augmented.npz).
 
 2-D (semantic_kitti_dataloader.py:166-212): bottom crop with the point filter, left-right flip with the column update, normalisation,
-HWC -> CHW (`augment_image`); `draw_augmentation_2d` makes the two draws.  Colour jitter is torchvision's (not installed, not used by any
-live config) and is not provided.  That dataloader class cannot be imported here (torchvision, torchsparse), so the 2-D part is
-checked against a numpy restatement of its statements: PARITY UNPINNED, though every operation is an index or a float32 subtraction
-and division."""
+HWC -> CHW (`augment_image`); `draw_augmentation_2d` makes the two draws.  That dataloader class cannot be imported here (torchvision,
+torchsparse), so the 2-D part is checked against a numpy restatement of its statements: PARITY UNPINNED, though every operation is an
+index or a float32 subtraction and division.
+
+Colour jitter (:117,146,196-197, `T.ColorJitter(*color_jitter)` on the cropped PIL image; config key
+DATASET.SemanticKITTISCN.augmentation.color_jitter, off by default): `augment_image_u8(..., jitter=draw_color_jitter(*cfg))` runs it on
+the device (`ftx_color_jitter_chw`), fused with the float conversion, flip, normalisation and HWC -> CHW.  What is pinned: the image
+operations, bit-exact against the installed Pillow's uint8 arithmetic (ImageEnhance.Brightness / Contrast / Color and the HSV round
+trip of adjust_hue) on all 2^24 colours and on full frames (tests/test_color_jitter_gpu.py, tests/golden/color_jitter.npz).  What is not:
+the draws, which restate torchvision 0.8.2 (not importable here) -- [upstream, not in container] PARITY OF THE DRAW ORDER UNPINNED --
+and the reference era's Pillow and torch RNG versions, which are not installed either."""
 from __future__ import annotations
 
 import numpy as np
@@ -19,7 +26,8 @@ import torch
 
 from .. import functional as spf
 
-__all__ = ["draw_augmentation_3d", "augment_and_scale_3d", "draw_augmentation_2d", "augment_image"]
+__all__ = ["draw_augmentation_3d", "augment_and_scale_3d", "draw_augmentation_2d", "augment_image", "draw_color_jitter",
+           "augment_image_u8"]
 
 
 def draw_augmentation_3d(noisy_rot=0.0, flip_x=0.0, flip_y=0.0, rot_z=0.0, transl=False, rng=np.random):
@@ -97,3 +105,71 @@ def augment_image(image: torch.Tensor, points_img: torch.Tensor, box=None, flip=
         std = torch.as_tensor(np.asarray(std, dtype=np.float32), device=image.device)
         image = (image - mean) / std
     return image.permute(2, 0, 1).contiguous(), idx, keep
+
+
+def _jitter_range(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
+    """torchvision 0.8.2 ColorJitter._check_input."""
+    import numbers
+    if isinstance(value, numbers.Number):
+        if value < 0:
+            raise ValueError("If {} is a single number, it must be non negative.".format(name))
+        value = [center - float(value), center + float(value)]
+        if clip_first_on_zero:
+            value[0] = max(value[0], 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        if not bound[0] <= value[0] <= value[1] <= bound[1]:
+            raise ValueError("{} values should be between {}".format(name, bound))
+    else:
+        raise TypeError("{} should be a single number or a list/tuple with length 2.".format(name))
+    if value[0] == value[1] == center:  # brightness / contrast / saturation (1, 1) or hue (0, 0): the op is off
+        value = None
+    return value
+
+
+def draw_color_jitter(brightness=0, contrast=0, saturation=0, hue=0, generator=None):
+    """The draws of one `T.ColorJitter(brightness, contrast, saturation, hue)(img)` call (semantic_kitti_dataloader.py:146,197), as
+    torchvision 0.8.2 makes them: `torch.randperm(4)` picks the order, then each op that is not off draws its factor with
+    `torch.tensor(1.0).uniform_(lo, hi).item()` when its turn comes.  Returns the ordered list of (op, factor), op one of
+    "brightness", "contrast", "saturation", "hue" -- what `augment_image_u8(jitter=...)` and functional.color_jitter_* take.
+    Torch's CPU generator (`generator`, or the global one) is the only source: numpy.random is not touched, so the crop and flip draws
+    of draw_augmentation_2d see the same stream with jitter on or off.
+    [upstream, not in container] PARITY OF THE DRAW ORDER UNPINNED: torchvision is not importable here; this restates its code."""
+    ranges = [_jitter_range(brightness, "brightness"), _jitter_range(contrast, "contrast"), _jitter_range(saturation, "saturation"),
+              _jitter_range(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip_first_on_zero=False)]
+    names = ("brightness", "contrast", "saturation", "hue")
+    out = []
+    for fn_id in torch.randperm(4, generator=generator).tolist():
+        r = ranges[fn_id]
+        if r is None:
+            continue
+        f = torch.tensor(1.0).uniform_(r[0], r[1], generator=generator).item()
+        if fn_id == 3 and not -0.5 <= f <= 0.5:  # F.adjust_hue's check, raised when the op is applied
+            raise ValueError("hue_factor ({}) is not in [-0.5, 0.5].".format(f))
+        out.append((names[fn_id], f))
+    return out
+
+
+def augment_image_u8(image_u8: torch.Tensor, points_img: torch.Tensor, box=None, flip=False, normalizer=None, jitter=None):
+    """augment_image for the uint8 frame the dataloader holds as a PIL image, with the optional colour jitter in its place: crop
+    (a view, no copy), jitter (:197, after the crop), np.array(image, float32) / 255 (:199), flip, normalisation, HWC -> CHW -- the image
+    part in one device call (functional.color_jitter_to_chw), the points exactly as augment_image.  `jitter`: the list of
+    draw_color_jitter, or None.  With jitter=None the image equals augment_image(u8 / 255) with the division correctly rounded
+    (numpy's; note that torch's GPU `u8.float() / 255` multiplies by a rounded reciprocal instead and differs in the last bit)."""
+    if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8 or image_u8.dim() != 3:
+        raise ValueError("augment_image_u8: expected an (H, W, 3) uint8 tensor")
+    keep = torch.ones((points_img.shape[0],), dtype=torch.bool, device=points_img.device)
+    pi = points_img
+    image = image_u8
+    if box is not None:
+        left, top, right, bottom = box
+        keep = (pi[:, 0] >= top) & (pi[:, 0] < bottom) & (pi[:, 1] >= left) & (pi[:, 1] < right)
+        image = image[top:bottom, left:right]
+        pi = pi[keep].clone()
+        pi[:, 0] -= top
+        pi[:, 1] -= left
+    idx = pi.to(torch.int64)
+    if flip:
+        idx = idx.clone()
+        idx[:, 1] = image.shape[1] - 1 - idx[:, 1]
+    img = spf.color_jitter_to_chw(image, jitter, flip, normalizer)
+    return img, idx, keep

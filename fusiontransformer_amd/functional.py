@@ -1503,3 +1503,66 @@ def eval_scatter_back(logits3d, logits2d, inverse, gt, class_labels, conf3d=None
     check(L.ftx_eval_scatter_back(ptr(logits3d), ptr(logits2d), n, c, ptr(inverse), ptr(gt), m, ptr(class_labels), ptr(p3), ptr(p2), ptr(pe),
                                   ptr(conf3d), ptr(conf2d), ptr(conf_ens), ptr(bad), stream()), "ftx_eval_scatter_back")
     return p3, p2, pe, bad
+
+
+# ---- colour jitter of the image-side augmentation (semantic_kitti_dataloader.py:196-212), csrc/ftx_image.hip ----
+JITTER_OPS = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}
+
+
+def _jitter_args(image: torch.Tensor, ops):
+    """Host-side checks of a uint8 (H, W, 3) frame (a crop view with a row pitch is fine) and the packed op codes / factors."""
+    import ctypes
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 3:
+        raise ValueError("color jitter: expected a (H, W, 3) uint8 CUDA tensor")
+    h, w, c = image.shape
+    if image.stride(2) != 1 or image.stride(1) != c or image.stride(0) < c * w:
+        raise ValueError(f"color jitter: pixels must be packed within a row (strides {image.stride()})")
+    ops = list(ops or [])
+    codes = np.zeros(4, dtype=np.int32)
+    factors = np.zeros(4, dtype=np.float64)
+    if len(ops) > 4:
+        raise ValueError("color jitter: at most 4 ops")
+    for i, (op, f) in enumerate(ops):
+        if op not in JITTER_OPS:
+            raise ValueError(f"color jitter: unknown op {op!r}")
+        codes[i], factors[i] = JITTER_OPS[op], float(f)
+    vp = ctypes.c_void_p
+    return (h, w, c, image.stride(0), codes.ctypes.data_as(vp), factors.ctypes.data_as(vp), len(ops),
+            (codes, factors), any(op == "contrast" for op, _ in ops))
+
+
+def _jitter_workspace(image, h, w, needed):
+    if not needed:
+        return 0, 0
+    nbytes = _ws_bytes("ftx_color_jitter_workspace_bytes", h, w)
+    return _carve(image, nbytes)[0], nbytes
+
+
+def color_jitter_u8(image: torch.Tensor, ops) -> torch.Tensor:
+    """ColorJitter's ops on a uint8 (H, W, 3) frame, bit-exact with Pillow: `ops` is the ordered list of (name, factor) that
+    data.augment.draw_color_jitter returns (names: brightness, contrast, saturation, hue).  Returns a contiguous (H, W, 3) uint8."""
+    L = _lib.load()
+    h, w, c, pitch, codes, factors, n, keep, needs_ws = _jitter_args(image, ops)
+    out = torch.empty((h, w, c), dtype=torch.uint8, device=image.device)
+    ws, ws_bytes = _jitter_workspace(image, h, w, needs_ws)
+    check(L.ftx_color_jitter_u8(ptr(image), pitch, h, w, c, codes, factors, n, ptr(out), ws, ws_bytes, stream()), "ftx_color_jitter_u8")
+    return out
+
+
+def color_jitter_to_chw(image: torch.Tensor, ops=None, flip=False, normalizer=None) -> torch.Tensor:
+    """The same ops, fused with the conversion to the model's input: float32(u8) / 255 (correctly rounded, numpy's division), the
+    optional left-right flip, (x - mean) / std with normalizer = (mean, std), HWC -> CHW.  Returns a (3, H, W) float32."""
+    import ctypes
+    L = _lib.load()
+    h, w, c, pitch, codes, factors, n, keep, needs_ws = _jitter_args(image, ops)
+    out = torch.empty((c, h, w), dtype=torch.float32, device=image.device)
+    mean = std = None
+    if normalizer is not None:
+        mean = np.ascontiguousarray(np.asarray(normalizer[0], dtype=np.float32).reshape(3))
+        std = np.ascontiguousarray(np.asarray(normalizer[1], dtype=np.float32).reshape(3))
+    vp = ctypes.c_void_p
+    ws, ws_bytes = _jitter_workspace(image, h, w, needs_ws)
+    check(L.ftx_color_jitter_chw(ptr(image), pitch, h, w, c, codes, factors, n, 1 if flip else 0,
+                                 None if mean is None else mean.ctypes.data_as(vp), None if std is None else std.ctypes.data_as(vp),
+                                 ptr(out), ws, ws_bytes, stream()), "ftx_color_jitter_chw")
+    return out

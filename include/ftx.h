@@ -397,6 +397,30 @@ int ftx_eval_scatter_back(const float *logits3d, const float *logits2d, int64_t 
  * rowcol (n,2) = (v, u) for EVERY point (the caller compacts with keep), i.e. the reference's fliplr(img_points). */
 int ftx_project_points(const float *points, int64_t n, const float *proj_matrix, int32_t width, int32_t height, uint8_t *keep, float *rowcol, void *stream);
 
+/* ---- colour jitter of the image-side augmentation: data/semantic_kitti/semantic_kitti_dataloader.py:117,146,196-212 ----
+ * T.ColorJitter on the cropped PIL image, then np.array(image, float32) / 255, the optional left-right flip, (x - mean) / std and
+ * HWC -> CHW.  src: one uint8 RGB frame, `height` rows of `width` pixels, row r at src + r * pitch (pitch >= 3 * width bytes, any
+ * byte offset: a crop view needs no copy); channels must be 3.  ops_host / factors_host (n_ops <= 4, each op at most once) are the
+ * draws in application order (torchvision's fn_idx order), host arrays:
+ *   FTX_JITTER_BRIGHTNESS f >= 0  ImageEnhance.Brightness(img).enhance(f)
+ *   FTX_JITTER_CONTRAST   f >= 0  ImageEnhance.Contrast(img).enhance(f): grey = int(mean luma of the image at that point + 0.5)
+ *   FTX_JITTER_SATURATION f >= 0  ImageEnhance.Color(img).enhance(f)
+ *   FTX_JITTER_HUE  -0.5 <= f <= 0.5  torchvision adjust_hue: HSV round trip, uint8 hue + (int(f * 255) mod 256)
+ * PRECISION: bit-exact with Pillow's uint8 arithmetic (blend in float32 without fused multiply-adds, convert("L"), the HSV
+ * conversions of libImaging/Convert.c); the float output is float32(u8) / 255 correctly rounded, then (x - mean) / std rounded twice.
+ * workspace: caller-owned, 16-byte aligned, ftx_color_jitter_workspace_bytes(height, width) bytes; only read when a contrast op is
+ * present (NULL allowed otherwise).  One launch, or two with a contrast op; no host synchronisation. */
+#define FTX_JITTER_BRIGHTNESS 0
+#define FTX_JITTER_CONTRAST 1
+#define FTX_JITTER_SATURATION 2
+#define FTX_JITTER_HUE 3
+size_t ftx_color_jitter_workspace_bytes(int32_t height, int32_t width);
+/* dst (height, width, 3) uint8, contiguous: the jittered frame. */
+int ftx_color_jitter_u8(const uint8_t *src, int64_t pitch, int32_t height, int32_t width, int32_t channels, const int32_t *ops_host, const double *factors_host, int32_t n_ops, uint8_t *dst, void *workspace, size_t workspace_bytes, void *stream);
+/* dst (3, height, width) float32, contiguous: the jittered frame as the model's input; flip != 0 mirrors the columns;
+ * mean_host / std_host (3 floats each) both NULL = no normalisation. */
+int ftx_color_jitter_chw(const uint8_t *src, int64_t pitch, int32_t height, int32_t width, int32_t channels, const int32_t *ops_host, const double *factors_host, int32_t n_ops, int32_t flip, const float *mean_host, const float *std_host, float *dst, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
