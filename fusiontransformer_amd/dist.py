@@ -196,7 +196,7 @@ class GradReducer:
             else:
                 src.append(g)
                 dst.append(v)
-        if src and os.environ.get("FTX_REDUCER_NOPACK") != "1":     # measurement aid: 1 = host work only, no copy issued
+        if src:
             torch._foreach_copy_(dst, src)
             # produced on a branch stream, read on the exchange stream: kept alive until finish() has made the step's stream wait for the
             # exchange (tensor.record_stream would do, at an event per gradient when it is freed)
@@ -231,8 +231,7 @@ class GradReducer:
                     return False
                 if self.world > 1:
                     b.flat.div_(self.world)
-                if os.environ.get("FTX_REDUCER_NOCOMM") != "1":      # measurement aid: everything but the collective itself
-                    b.work = dist.all_reduce(b.flat, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
+                b.work = dist.all_reduce(b.flat, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
         else:
             if not self._pack(b, early):
                 return False
@@ -266,17 +265,16 @@ class GradReducer:
         on one GPU with no byte moved, all of it gone when the waits are removed (why is not fully established: the exchange stream
         shares the image branch's hardware queue -- four queues for six streams --, yet the exchange on the default stream costs the
         same).  Waiting for the PREVIOUS bucket's events, which are (nearly) reached by the time the next
-        tail arrives, costs +0.5-0.8 ms (tools/probes/reducer_ab6.sh)."""
+        tail arrives, costs +0.5-0.8 ms (profiles/r03_reducer_one_gpu_cost.txt)."""
         t0 = time.perf_counter()
         b = self.buckets[i]
         b.tail_seen = True
         if b.flat.is_cuda and self.active:
             self._mark(b)
-        if os.environ.get("FTX_REDUCER_LATE") != "1":       # measurement aid: 1 = nothing goes out before finish()
-            before = self.next_to_launch
-            self._launch_ready_prefix(i if os.environ.get("FTX_REDUCER_EAGER") != "1" else i + 1)   # aid: 1 = round 3's launch at the tail
-            self.hook_stats["early_launches"] += self.next_to_launch - before
-            self.hook_stats["deferred"] += int(self.next_to_launch == before)
+        before = self.next_to_launch
+        self._launch_ready_prefix(i)
+        self.hook_stats["early_launches"] += self.next_to_launch - before
+        self.hook_stats["deferred"] += int(self.next_to_launch == before)
         self.hook_stats["calls"] += 1
         self.hook_stats["host_ms"] += 1e3 * (time.perf_counter() - t0)
 
@@ -293,7 +291,7 @@ class GradReducer:
                 b.work.wait()     # NCCL: the CURRENT stream waits for the collective (no host block); gloo: the host waits
                 b.work = None
         if self.active and self.buckets and self.buckets[0].flat.is_cuda:
-            # packs without a collective behind them (FTX_REDUCER_NOCOMM) and the held gradients: the step's stream waits for the exchange stream
+            # the packs and the held gradients: the step's stream waits for the exchange stream
             torch.cuda.current_stream().wait_stream(self._comm_stream(self.buckets[0].flat.device))
         for b in self.buckets:
             b.hold = None

@@ -9,8 +9,6 @@ the GPU, index tensors are int32 (torchsparse returns int64 and immediately
 `.int()`s them, utils.py:22,51)."""
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
@@ -516,11 +514,7 @@ def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_trans
     return out
 
 
-_OSTAT = os.environ.get("FTX_OSTAT", "1") != "0"      # A/B aid: 0 = every convolution on the pair-list kernels
-_OSTAT_ALL = os.environ.get("FTX_OSTAT", "1") == "all"   # every layer the kernel supports, not only where it is faster
 _OSTAT_OK = {}
-
-
 _OSTAT_MAX_ROWS = 64 * 4096      # one block per 64 output rows, at most 4096 partial rows in the statistics hand-over
 
 
@@ -531,19 +525,15 @@ def ostat_supported(ca, co, kvol, w_transposed=False, rows=0):
     v = _OSTAT_OK.get(key)
     if v is None:
         v = _OSTAT_OK[key] = bool(_lib.load().ftx_spconv_ostat_supported(key[0], key[1], key[2], int(key[3])))
-    return v and _OSTAT and rows <= _OSTAT_MAX_ROWS
+    return v and rows <= _OSTAT_MAX_ROWS
 
 
 def ostat_preferred(ca, co, kvol, w_transposed=False, rows=0):
     """Where the output-stationary kernel is FASTER than pair GEMM + reduce on MI355X (tools/bench_spconv.py, profiles/r03_spconv_layer_micro.txt):
     forward convolutions with c_in <= 32 and c_out = 32 -- the stem, the 32 -> 32 layers of levels 1 and 2, the strided 32 -> 32 layers.
     It is bound by instruction issue (~23 instructions per pair), so 64-channel layers and the transposed-W data-gradient form lose
-    (csrc/ftx_spconv_ostat.hip); FTX_OSTAT=all routes everything the kernel supports through it (tests, measurements)."""
-    if not ostat_supported(ca, co, kvol, w_transposed, rows):
-        return False
-    if _OSTAT_ALL:
-        return True
-    return (not w_transposed) and co == 32 and ca <= 32
+    (csrc/ftx_spconv_ostat.hip)."""
+    return ostat_supported(ca, co, kvol, w_transposed, rows) and not w_transposed and co == 32 and ca <= 32
 
 
 def _spconv_ostat(A, W, nbr, n_rows_out, co, w_transposed, flip, part=0, nb=0, pairs=0):
@@ -772,7 +762,7 @@ def rows_matmul(x, kernel, bf16=False):
 # ---------------------------------------------------------------- BatchNorm (+residual)(+ReLU)
 class _BatchNormTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu):
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, remask):
         L = _lib.load()
         x = req(x.contiguous(), F32, "bn x", 2)
         n, c = x.shape
@@ -795,14 +785,15 @@ class _BatchNormTrain(torch.autograd.Function):
         ctx.save_for_backward(x, y, gamma, beta, mean, invstd)
         ctx.relu = int(relu)
         ctx.has_res = residual is not None
+        ctx.remask = bool(remask)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, y, gamma, beta, mean, invstd = ctx.saved_tensors
         gy = req(gy.contiguous(), F32, "bn grad", 2)
-        gx, gres, ggamma, gbeta = _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, ctx.relu, ctx.has_res)
-        return gx, gres, ggamma, gbeta, None, None, None, None, None
+        gx, gres, ggamma, gbeta = _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, ctx.relu, ctx.has_res, ctx.remask)
+        return gx, gres, ggamma, gbeta, None, None, None, None, None, None
 
 
 class _BatchNormEval(torch.autograd.Function):
@@ -830,13 +821,7 @@ class _BatchNormEval(torch.autograd.Function):
         return gx, (dy if ctx.has_res else None), None, None, None, None, None, None
 
 
-def _remask_beta(beta):
-    """beta for ftx_bn_train_bwd: with it the ReLU mask of a residual-free BatchNorm is recomputed from x instead of read from y
-    (FTX_BN_REMASK=0 withholds it: A/B aid, read at call time)."""
-    return 0 if os.environ.get("FTX_BN_REMASK") == "0" else ptr(beta)
-
-
-def _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, relu, has_res):
+def _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, relu, has_res, remask):
     L = _lib.load()
     n, c = x.shape
     gx = torch.empty_like(x)
@@ -848,7 +833,7 @@ def _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, relu, has_res):
     # two passes (statistics, apply), each reading gy and x (and y for the ReLU mask when a residual went into it: otherwise the mask is
     # recomputed from x); one or two row matrices written
     _log_launch("bn_bwd", dict(n=n, c=c, reads=2 * (2 + (1 if (relu and has_res) else 0)), writes=1 + (1 if has_res else 0)), lambda: check(L.ftx_bn_train_bwd(
-        ptr(gy), ptr(x), ptr(y), ptr(gamma), _remask_beta(beta), ptr(mean), ptr(invstd), n, c, int(relu), ptr(gx), ptr(gres), ptr(ggamma),
+        ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta) if remask else 0, ptr(mean), ptr(invstd), n, c, int(relu), ptr(gx), ptr(gres), ptr(ggamma),
         ptr(gbeta), ptr(ws), ws_bytes, _stream_scratch()), "ftx_bn_train_bwd"))
     return gx, gres, ggamma, gbeta
 
@@ -863,7 +848,7 @@ class _ConvBNTrain(torch.autograd.Function):
     stream's scratch buffer instead of six allocator round trips per layer and direction."""
 
     @staticmethod
-    def forward(ctx, feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bf16=False):
+    def forward(ctx, feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bf16, remask):
         L = _lib.load()
         feats = req(feats.contiguous(), F32, "conv3d feats", 2)
         kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
@@ -913,7 +898,7 @@ class _ConvBNTrain(torch.autograd.Function):
                 ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum),
                 float(eps), n_out, co, int(relu), ptr(y), p_mean, p_invstd, part + 16 * nb * co, st), "ftx_bn_train_fwd_totals"))
         ctx.save_for_backward(feats, kernel, x, y, gamma, beta, stats)
-        ctx.km, ctx.transposed, ctx.relu, ctx.has_res, ctx.bf16 = km, transposed, int(relu), residual is not None, bf16
+        ctx.km, ctx.transposed, ctx.relu, ctx.has_res, ctx.bf16, ctx.remask = km, transposed, int(relu), residual is not None, bf16, bool(remask)
         return y
 
     @staticmethod
@@ -942,7 +927,7 @@ class _ConvBNTrain(torch.autograd.Function):
         bn_ws, gx, tmp, wg_ws = _carve(x, bn_ws_bytes, 4 * n * co, tmp_bytes, wg_bytes)
         # BatchNorm half: gx = d loss / d (convolution output) stays in the scratch buffer, it is consumed by the two calls below
         _log_launch("bn_bwd", dict(n=n, c=co, reads=2 * (2 + (1 if (ctx.relu and ctx.has_res) else 0)), writes=1 + (1 if ctx.has_res else 0)), lambda: check(L.ftx_bn_train_bwd(
-            ptr(gy), ptr(x), ptr(y), ptr(gamma), _remask_beta(beta), p_mean, p_invstd, n, co, ctx.relu, gx, ptr(gres), gparams.data_ptr(), gparams.data_ptr() + 4 * co,
+            ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta) if ctx.remask else 0, p_mean, p_invstd, n, co, ctx.relu, gx, ptr(gres), gparams.data_ptr(), gparams.data_ptr() + 4 * co,
             bn_ws, bn_ws_bytes, st), "ftx_bn_train_bwd"))
         g_feats = g_kernel = None
         meta = dict(pairs=km.n_pairs, n_out=n_feats, ca=co, co=ca, kvol=kvol)
@@ -967,20 +952,23 @@ class _ConvBNTrain(torch.autograd.Function):
             _log_launch(wgrad_kind, dict(pairs=km.n_pairs, n_out=n, ca=ca, co=co, kvol=kvol), lambda: check(getattr(L, wgrad)(
                 ptr(feats), n_feats, ptr(in_side), gx, n, ptr(out_side), ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(g_kernel), wg_ws, wg_bytes, st),
                 wgrad))
-        return g_feats, g_kernel, None, None, gres, gparams[0], gparams[1], None, None, None, None, None, None
+        return g_feats, g_kernel, None, None, gres, gparams[0], gparams[1], None, None, None, None, None, None, None
 
 
 def conv_bn_train(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, residual=None, relu=False,
-                  bf16=False):
+                  bf16=False, remask=True):
     """Conv3d -> BatchNorm(training) (+ residual) (+ ReLU) in one autograd node; see _ConvBNTrain.  bf16=True: the convolution's
-    forward, data gradient and weight gradient on bf16-rounded operands (as sparse_conv(bf16=True)); BatchNorm stays fp32."""
-    return _ConvBNTrain.apply(feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bool(bf16))
+    forward, data gradient and weight gradient on bf16-rounded operands (as sparse_conv(bf16=True)); BatchNorm stays fp32.
+    remask: as in batch_norm."""
+    return _ConvBNTrain.apply(feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bool(bf16),
+                              bool(remask))
 
 
-def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, residual=None, relu=False):
-    """y = relu?(BN(x) (+ residual)) over the rows of x (N,C)."""
+def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, residual=None, relu=False, remask=True):
+    """y = relu?(BN(x) (+ residual)) over the rows of x (N,C).  remask (training): the backward recomputes the ReLU mask of a
+    residual-free BatchNorm from x instead of reading it from y (ftx_bn_train_bwd given beta); False reads y."""
     if training:
-        return _BatchNormTrain.apply(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu)
+        return _BatchNormTrain.apply(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bool(remask))
     return _BatchNormEval.apply(x, residual, gamma, beta, running_mean, running_var, eps, relu)
 
 
@@ -1064,11 +1052,8 @@ def resample_nearest(x, size):
 
 
 # ---------------------------------------------------------------- LayerNorm (+ the residual add in front of it)
-_FUSED_LN = os.environ.get("FTX_FUSED_LN", "1") != "0"      # A/B aid: 0 = torch's add + LayerNorm kernels in the ViT blocks
-
-
 def layer_norm_supported(x: torch.Tensor) -> bool:
-    return _FUSED_LN and x.is_cuda and x.dtype == F32 and x.shape[-1] % 256 == 0 and 256 <= x.shape[-1] <= 1024
+    return x.is_cuda and x.dtype == F32 and x.shape[-1] % 256 == 0 and 256 <= x.shape[-1] <= 1024
 
 
 def _ln_forward(x, y, weight, bias, eps, y_bias=None):

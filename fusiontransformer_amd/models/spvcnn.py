@@ -9,7 +9,6 @@ launch plus one fused BN/residual/ReLU pass instead of four separate ops."""
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -17,11 +16,9 @@ import torch.nn.functional as F
 
 from .. import functional as spf
 from ..sparse import PendingIndex, PointTensor, PreparedIndex, SparseTensor, cat, drain, index_stream as _index_stream
-from .utils import initial_voxelize, initial_voxelize_steps, point_index, point_to_voxel, voxel_index, voxel_to_point
+from .utils import initial_voxelize_steps, point_index, point_to_voxel, voxel_index, voxel_to_point
 
 __all__ = ["SPVCNN", "Conv3d", "BatchNorm", "ReLU"]
-
-_FUSE_CONV_BN = os.environ.get("FTX_FUSE_CONV_BN", "1") != "0"
 
 
 class Conv3d(nn.Module):
@@ -91,9 +88,9 @@ class ReLU(nn.ReLU):
 
 def _conv_bn(conv, bn, x, residual=None, relu=True):
     """Conv3d -> BatchNorm (-> + residual) (-> ReLU).  In training a k>1 convolution and its BatchNorm run as one autograd node whose
-    reduce pass also produces the batch statistics (functional.conv_bn_train); FTX_FUSE_CONV_BN=0 keeps the two separate nodes."""
+    reduce pass also produces the batch statistics (functional.conv_bn_train); eval and 1x1x1 layers run the two separately."""
     ks, s = conv.kernel_size, conv.stride
-    if bn.training and _FUSE_CONV_BN and not (ks == 1 and s == 1) and x.F.is_cuda:
+    if bn.training and not (ks == 1 and s == 1) and x.F.is_cuda:
         if not conv.t:
             km = x.cm.kernel_map(ks, x.s, s)
             coords, stride = km.out_coords, x.s * s
@@ -202,8 +199,8 @@ class SPVCNN(nn.Module):
         ])
         self.weight_initialization()
         self.dropout = nn.Dropout(0.3, True)
-        # cfg.MODEL.lidar_bf16 (default: environment FTX_LIDAR_BF16=1): the LiDAR branch on bf16-operand kernels, see set_bf16
-        self.lidar_bf16 = bool(kwargs.get("lidar_bf16", os.environ.get("FTX_LIDAR_BF16", "0") == "1"))
+        # cfg.MODEL.lidar_bf16: the LiDAR branch on bf16-operand kernels, see set_bf16
+        self.lidar_bf16 = bool(kwargs.get("lidar_bf16", False))
         self.set_bf16(self.lidar_bf16)
         # optional injected keep-masks {'y1': (N4,C), 'y3': (N2,C)} so a train-mode run can be
         # compared with the oracle (Dropout RNG streams differ between CPU and GPU)
@@ -323,18 +320,14 @@ class SPVCNN(nn.Module):
     def _index_steps(self, x, ahead=False):
         """Everything of a batch that depends on its coordinates only: the voxelisation of the points, the voxel hash, the
         coordinates and kernel maps of the five U-Net levels and (ahead=True) the point <-> voxel index structures of the strides
-        the network visits.  Each data-dependent size is read back after a "sync" yield (6 per batch), so a scheduler can issue
-        image-branch work instead of waiting for it."""
+        the network visits.  Each data-dependent size is read back after a "sync" yield (two per batch: all level sizes, then all
+        pair counts), so a scheduler can issue image-branch work instead of waiting for it."""
         coords = x.C
         if coords.dtype != torch.float32:
             coords = coords.float()
         z = PointTensor(x.F, coords.contiguous())
-        if os.environ.get("FTX_EAGER_INDEX_READS") == "1":   # A/B aid: block on every read as it comes
-            x0 = initial_voxelize(z, self.pres, self.vres)
-        else:
-            levels = None if os.environ.get("FTX_LAZY_LEVELS") == "1" else (1, 2, 4, 8, 16)   # A/B aid: 1 = level l+1 from level l, six reads
-            x0 = yield from initial_voxelize_steps(z, self.pres, self.vres, levels=levels)
-            yield from x0.cm.unet_levels_steps((1, 2, 4, 8, 16))
+        x0 = yield from initial_voxelize_steps(z, self.pres, self.vres, levels=(1, 2, 4, 8, 16))
+        yield from x0.cm.unet_levels_steps((1, 2, 4, 8, 16))
         if ahead:
             cm, seg = x0.cm, torch.is_grad_enabled()
             # the strides of voxel_to_point / point_to_voxel in _backbone_steps: x0 / y4 (1), x4 (16), y2 (4)

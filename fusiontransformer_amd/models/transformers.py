@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import contextlib
 import gc
-import os
 from functools import partial
 from typing import Dict
 
@@ -387,7 +386,7 @@ class Image2DTransformer(nn.Module):
 
     # ---- HIP-graph execution of the trunk ------------------------------------------------------------------
     graph_taps = None   # sorted block indices whose outputs the caller uses; None: eager execution
-    graph_segment_blocks = int(os.environ.get("FTX_GRAPH_SEGMENT_BLOCKS", "3"))   # blocks per captured segment (a tap always ends one)
+    graph_segment_blocks = 3   # blocks per captured segment (a tap always ends one)
 
     def _graph_key(self, x):
         """Everything a captured graph bakes in: input shape / dtype / requires_grad, the tap set and segment length, the
@@ -423,7 +422,7 @@ class Image2DTransformer(nn.Module):
         return cache[key]
 
     # ---- forward-only graph for evaluation -----------------------------------------------------------------------------------
-    eval_graphs = os.environ.get("FTX_VIT_EVAL_GRAPHS", "1") != "0"
+    eval_graphs = True
 
     def _inference_graph(self, x):
         """Replay function of the forward-only HIP graph for this input shape, or None (not on the GPU, gradients enabled, training

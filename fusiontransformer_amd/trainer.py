@@ -10,8 +10,6 @@ SemanticTrainer.py:158-178, Adam step.  Differences, all behaviour-preserving:
     losses and the IoU confusion matrices stay on the device."""
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
 
@@ -50,10 +48,10 @@ def build_optimizer(cfg, model):
     params = [p for p in model.parameters() if p.requires_grad]
     kwargs = dict(lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY)
     on_gpu = bool(params) and params[0].is_cuda
-    if cfg.OPTIMIZER.TYPE == "Adam" and on_gpu and os.environ.get("FTX_ADAM", "1") != "0":
+    if cfg.OPTIMIZER.TYPE == "Adam" and on_gpu:
         from .optim import Adam      # torch.optim.Adam's rule and state layout, stepped by one libftx launch (csrc/ftx_optim.hip)
         return Adam(params, **kwargs)
-    if cfg.OPTIMIZER.TYPE in ("Adam", "AdamW") and on_gpu:
+    if cfg.OPTIMIZER.TYPE == "AdamW" and on_gpu:
         kwargs["fused"] = True  # same update rule, one multi-tensor kernel instead of ~10 passes over 108 M parameters
     return getattr(torch.optim, cfg.OPTIMIZER.TYPE)(params, **kwargs)
 
@@ -77,7 +75,7 @@ class TrainStep:
         self.grad_reducer = grad_reducer
         self.fused_loss = True
         self.prefetch_wait = False     # next_batch: start its index build without blocking this thread (SPVCNN.prepare(wait=False))
-        self.prefetch_budget_ms = float(os.environ.get("FTX_PREFETCH_BUDGET_MS", "1.5"))   # ... then poll its host reads this long at most
+        self.prefetch_budget_ms = 1.5  # ... then poll its host reads this long at most
         self._prefetch_misses = self._prefetch_pause = 0
         self.last = {}
 

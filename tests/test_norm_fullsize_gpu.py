@@ -237,8 +237,8 @@ def test_batch_norm_eval_at_full_size(env, n, c, res):
     gate("bn eval", f"eval {n}x{c}", y, ref, bound, [whole(batch - ref), [(ix, pre[ix])]])
 
 
-def test_batch_norm_remask_matches_the_stored_mask(env, monkeypatch):
-    """The backward's recomputed ReLU mask (the default without a residual) against the mask read from y (FTX_BN_REMASK=0) where
+def test_batch_norm_remask_matches_the_stored_mask(env):
+    """The backward's recomputed ReLU mask (the default without a residual) against the mask read from y (remask=False) where
     pre-activations are the exact residual of a product, of either sign, or exactly 0.
 
     Planted columns take four distinct x values; after one forward, beta_j = -f32(t gamma_j) with t = f32(f32(x0 - mean_j) invstd_j)
@@ -261,18 +261,16 @@ def test_batch_norm_remask_matches_the_stored_mask(env, monkeypatch):
     bet[:planted] = -(t * gam[:planted])
     bd = bet.cuda().requires_grad_(True)
 
-    def run():
+    def run(remask=True):
         xd.grad = gd.grad = bd.grad = None
-        y = spf.batch_norm(xd, gd, bd, None, None, True, MOM, EPS, relu=True)
+        y = spf.batch_norm(xd, gd, bd, None, None, True, MOM, EPS, relu=True, remask=remask)
         stats = [t.clone() for t in y.grad_fn.saved_tensors[4:6]]
         y.backward(gy.cuda())
         return y, stats, xd.grad.clone(), gd.grad.clone(), bd.grad.clone()
 
     y, stats, gx_a, gg_a, gb_a = run()
     assert torch.equal(stats[0], mean0) and torch.equal(stats[1], inv0)
-    monkeypatch.setenv("FTX_BN_REMASK", "0")
-    y_b, _, gx_b, gg_b, gb_b = run()
-    monkeypatch.delenv("FTX_BN_REMASK")
+    y_b, _, gx_b, gg_b, gb_b = run(remask=False)
     assert torch.equal(y, y_b)
     assert torch.equal(gx_a, gx_b) and torch.equal(gg_a, gg_b) and torch.equal(gb_a, gb_b)
     yc = y.detach().cpu()

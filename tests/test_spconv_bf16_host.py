@@ -135,8 +135,7 @@ def _flagged(lb):
 
 
 @pytest.mark.parametrize("kind,transform", [("middle", "middle_fusion_transform"), ("early", "early_fusion_transform")])
-def test_lidar_bf16_flags_the_lidar_gemms_and_no_head(kind, transform, monkeypatch):
-    monkeypatch.delenv("FTX_LIDAR_BF16", raising=False)
+def test_lidar_bf16_flags_the_lidar_gemms_and_no_head(kind, transform):
     lb = _lidar(True, kind)
     convs, linears = _flagged(lb)
     assert len(convs) > 40 and all(c.ftx_bf16 for c in convs)
@@ -148,14 +147,13 @@ def test_lidar_bf16_flags_the_lidar_gemms_and_no_head(kind, transform, monkeypat
     assert not any(c.ftx_bf16 for c in convs) and not any(getattr(m, "ftx_bf16", False) for m in linears.values())
 
 
-def test_default_build_flags_nothing(monkeypatch):
-    monkeypatch.delenv("FTX_LIDAR_BF16", raising=False)
+def test_default_build_flags_nothing_whatever_the_environment(monkeypatch):
     lb = _lidar()
     convs, linears = _flagged(lb)
     assert not lb.lidar_bf16
     assert not any(getattr(c, "ftx_bf16", False) for c in convs)
     assert not any(getattr(m, "ftx_bf16", False) for m in linears.values())
-    # the ViT trunk's own bf16 switch is independent
+    # only cfg.MODEL.lidar_bf16 chooses: FTX_LIDAR_BF16 (a switch since removed) left in the environment changes nothing
     monkeypatch.setenv("FTX_LIDAR_BF16", "1")
-    assert _lidar().lidar_bf16
+    assert not _lidar().lidar_bf16
     assert not _lidar(False).lidar_bf16

@@ -116,13 +116,9 @@ def _lins(vit):
     return [lin for blk in vit.blocks for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2)]
 
 
-def _trunk(monkeypatch, env=None, **model_kw):
+def _trunk(**model_kw):
     from fusiontransformer_amd.models.build import build_model
     from tests.helpers import small_cfg
-    if env is None:
-        monkeypatch.delenv("FTX_VIT_LINEAR", raising=False)
-    else:
-        monkeypatch.setenv("FTX_VIT_LINEAR", env)
     cfg = small_cfg("middle")
     for k, v in model_kw.items():
         cfg.MODEL[k] = v
@@ -131,16 +127,24 @@ def _trunk(monkeypatch, env=None, **model_kw):
     return model.image_backbone.backbone
 
 
-def test_linear_impl_defaults_to_library(monkeypatch):
-    vit = _trunk(monkeypatch)
+def test_linear_impl_defaults_to_library():
+    vit = _trunk()
     assert all(lin.ftx_linear_impl == "library" for lin in _lins(vit))
 
 
-@pytest.mark.parametrize("how", ["cfg", "env"])
-def test_linear_impl_reaches_every_linear(monkeypatch, how):
-    vit = _trunk(monkeypatch, vit_linear_impl="ftx") if how == "cfg" else _trunk(monkeypatch, env="ftx")
+def test_linear_impl_reaches_every_linear():
+    vit = _trunk(vit_linear_impl="ftx")
     assert len(vit.blocks) == 2
     assert all(lin.ftx_linear_impl == "ftx" for lin in _lins(vit))
+    assert not any(getattr(lin, "ftx_bf16", False) for lin in _lins(vit)), "the impl does not switch precision"
+
+
+def test_linear_impl_default_ignores_the_environment(monkeypatch):
+    """Only cfg.MODEL.vit_linear_impl chooses: FTX_VIT_LINEAR (a switch since removed) left in the environment changes nothing."""
+    monkeypatch.setenv("FTX_VIT_LINEAR", "ftx")
+    vit = _trunk()
+    assert len(vit.blocks) == 2
+    assert all(lin.ftx_linear_impl == "library" for lin in _lins(vit))
     assert not any(getattr(lin, "ftx_bf16", False) for lin in _lins(vit)), "the impl does not switch precision"
 
 
@@ -166,7 +170,7 @@ def test_linear_impl_is_inert_without_bf16(monkeypatch):
     """set_bf16(False): the ftx setting routes nothing to the new kernels; set_bf16(True) turns the fused MLP route on."""
     from fusiontransformer_amd import functional as spf
     from fusiontransformer_amd.models import transformers as T
-    b = _trunk(monkeypatch, vit_linear_impl="ftx")
+    b = _trunk(vit_linear_impl="ftx")
     xc = torch.zeros(1, 5, 768).as_subclass(_Cuda)
     mlp = b.blocks[0].mlp
     assert not mlp._fused_ftx(xc)
@@ -193,7 +197,7 @@ def test_linear_impl_is_inert_without_bf16(monkeypatch):
 def test_graph_keys_distinguish_linear_impl(monkeypatch):
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)   # the key records the device; no GPU is touched here
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    a, b = _trunk(monkeypatch), _trunk(monkeypatch, vit_linear_impl="ftx")
+    a, b = _trunk(), _trunk(vit_linear_impl="ftx")
     for t in (a, b):
         t.set_bf16(True)
     assert a.graph_taps and b.graph_taps

@@ -12,7 +12,6 @@ python tools/bench_bn.py > $O/bn_layer_micro.txt 2>&1; tail -1 $O/bn_layer_micro
 python tools/probes/eval_throughput.py > $O/eval_throughput.txt 2>&1; tail -2 $O/eval_throughput.txt
 python tools/bench_attn.py > $O/attn_tilings.txt 2>&1; tail -3 $O/attn_tilings.txt
 python tools/probes/loss_time.py > $O/loss_time.txt 2>&1; tail -2 $O/loss_time.txt
-bash tools/probes/reducer_ab6.sh > $O/reducer_one_gpu_cost.txt 2>&1; cat $O/reducer_one_gpu_cost.txt
 # N > 1 code path (bucketed overlapped all-reduce, per-rank batches) rehearsed as 2 ranks on this one GPU over gloo: NOT a scaling number
 FTX_DIST_BACKEND=gloo FTX_FORCE_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
   bench.py --gpus 2 --steps 6 --warmup 3 --no-cpu-baseline > $O/bench_2ranks_one_gpu_gloo.json 2> $O/bench_2ranks.err; tail -c 300 $O/bench_2ranks_one_gpu_gloo.json
