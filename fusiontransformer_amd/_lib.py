@@ -116,6 +116,10 @@ SIGNATURES = {
     "ftx_color_jitter_workspace_bytes": (_sz, [_i32, _i32]),
     "ftx_color_jitter_u8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "ftx_color_jitter_chw": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ftx_resize_ksize": (_i32, [_i32, _i32]),
+    "ftx_resize_coeffs_host": (C.c_int, [_i32, _i32, _vp, _vp]),
+    "ftx_resize_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ftx_resize_bilinear_u8": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

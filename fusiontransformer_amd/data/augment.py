@@ -18,7 +18,15 @@ the device (`ftx_color_jitter_chw`), fused with the float conversion, flip, norm
 operations, bit-exact against the installed Pillow's uint8 arithmetic (ImageEnhance.Brightness / Contrast / Color and the HSV round
 trip of adjust_hue) on all 2^24 colours and on full frames (tests/test_color_jitter_gpu.py, tests/golden/color_jitter.npz).  What is not:
 the draws, which restate torchvision 0.8.2 (not importable here) -- [upstream, not in container] PARITY OF THE DRAW ORDER UNPINNED --
-and the reference era's Pillow and torch RNG versions, which are not installed either."""
+and the reference era's Pillow and torch RNG versions, which are not installed either.
+
+Resize (data/nuscenes/nuscenes_dataloader.py:175-185, `image.resize(self.resize, Image.BILINEAR)` on every 1600 x 900 camera frame and the
+two statements that rescale the projected points, before jitter, / 255, flip and normalisation): `augment_image_u8(..., resize=(w, h))`,
+or `functional.resize_bilinear_u8` and `resize_points_img` on their own.  What is pinned: the image bytes, bit-exact against the installed
+Pillow 12.2.0's 8-bit bilinear resample (integer arithmetic on a coefficient table built in double: include/ftx.h) on full frames, both
+directions, every row alignment of a crop view (tests/test_resize_host.py, tests/test_resize_gpu.py, tests/golden/resize_bilinear.npz);
+the points against numpy's rounding of the two statements.  What is not: the reference era's Pillow is not installed, so its 8bpc
+resample could not be run here -- PARITY WITH THAT VERSION UNPINNED."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,7 +35,7 @@ import torch
 from .. import functional as spf
 
 __all__ = ["draw_augmentation_3d", "augment_and_scale_3d", "draw_augmentation_2d", "augment_image", "draw_color_jitter",
-           "augment_image_u8"]
+           "resize_points_img", "augment_image_u8"]
 
 
 def draw_augmentation_3d(noisy_rot=0.0, flip_x=0.0, flip_y=0.0, rot_z=0.0, transl=False, rng=np.random):
@@ -149,14 +157,44 @@ def draw_color_jitter(brightness=0, contrast=0, saturation=0, hue=0, generator=N
     return out
 
 
-def augment_image_u8(image_u8: torch.Tensor, points_img: torch.Tensor, box=None, flip=False, normalizer=None, jitter=None):
+def resize_points_img(points_img: torch.Tensor, image_size, resize) -> torch.Tensor:
+    """The two statements of nuscenes_dataloader.py:181-182 with numpy's rounding: points_img (N, 2) float (row, col) of a frame of
+    image_size = (width, height) that is resized to resize = (width, height); row' = float(resize[1]) / image_size[1] * floor(row), the
+    same with index 0 for the columns.  The Python scalar is a weak scalar to numpy: for float32 points the product is
+    float32(scalar) * floor(p) rounded once in float32 (not the float64 product rounded to float32: they differ on non-dyadic ratios), for
+    float64 points it is the float64 product.  Returns the scaled points as a new tensor on the points' device; the truncation to int64
+    stays with the caller."""
+    if not isinstance(points_img, torch.Tensor) or points_img.dtype not in (torch.float32, torch.float64) or points_img.dim() != 2 \
+            or points_img.shape[1] != 2:
+        raise ValueError("resize_points_img: expected a (N, 2) float32 or float64 tensor")
+    sy = float(resize[1]) / image_size[1]
+    sx = float(resize[0]) / image_size[0]
+    if points_img.dtype == torch.float32:
+        sy, sx = float(np.float32(sy)), float(np.float32(sx))  # exact in float32: one rounding, that of the product
+    fl = torch.floor(points_img)
+    return torch.stack([fl[:, 0] * sy, fl[:, 1] * sx], 1)
+
+
+def augment_image_u8(image_u8: torch.Tensor, points_img: torch.Tensor, box=None, flip=False, normalizer=None, jitter=None, resize=None):
     """augment_image for the uint8 frame the dataloader holds as a PIL image, with the optional colour jitter in its place: crop
     (a view, no copy), jitter (:197, after the crop), np.array(image, float32) / 255 (:199), flip, normalisation, HWC -> CHW -- the image
     part in one device call (functional.color_jitter_to_chw), the points exactly as augment_image.  `jitter`: the list of
     draw_color_jitter, or None.  With jitter=None the image equals augment_image(u8 / 255) with the division correctly rounded
-    (numpy's; note that torch's GPU `u8.float() / 255` multiplies by a rounded reciprocal instead and differs in the last bit)."""
+    (numpy's; note that torch's GPU `u8.float() / 255` multiplies by a rounded reciprocal instead and differs in the last bit).
+    `resize` = (width, height), the NuScenes loader's first step (nuscenes_dataloader.py:175-185): if the frame's size differs, the
+    points are rescaled (resize_points_img) and the frame is resized (functional.resize_bilinear_u8, bit-exact with PIL's
+    Image.BILINEAR) before everything else; enlarging raises ValueError (the loader asserts image.size[0] > resize[0]).  A `box` then
+    counts in the resized frame's coordinates (no reference loader combines the two).  resize=None changes nothing."""
     if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8 or image_u8.dim() != 3:
         raise ValueError("augment_image_u8: expected an (H, W, 3) uint8 tensor")
+    if resize is not None:
+        size = (image_u8.shape[1], image_u8.shape[0])
+        resize = (int(resize[0]), int(resize[1]))
+        if size != resize:
+            if not size[0] > resize[0]:
+                raise ValueError(f"augment_image_u8: resize {resize} would enlarge a frame of {size}")
+            points_img = resize_points_img(points_img, size, resize)
+            image_u8 = spf.resize_bilinear_u8(image_u8, resize)
     keep = torch.ones((points_img.shape[0],), dtype=torch.bool, device=points_img.device)
     pi = points_img
     image = image_u8

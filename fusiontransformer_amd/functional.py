@@ -1551,3 +1551,70 @@ def color_jitter_to_chw(image: torch.Tensor, ops=None, flip=False, normalizer=No
                                  None if mean is None else mean.ctypes.data_as(vp), None if std is None else std.ctypes.data_as(vp),
                                  ptr(out), ws, ws_bytes, stream()), "ftx_color_jitter_chw")
     return out
+
+
+# ---- image resize of the NuScenes loader (nuscenes_dataloader.py:185, Image.BILINEAR), csrc/ftx_resize.hip ----
+_RESIZE_TABLES = {}
+
+
+def resize_table(in_size: int, out_size: int, device):
+    """Pillow's coefficient table of one axis (include/ftx.h) on `device`: (bounds (out, 2) int32, kk (out, ksize) int32, ksize).
+    Computed on the host by ftx_resize_coeffs_host and uploaded once per (in, out, device); later calls return the same tensors."""
+    import ctypes
+    device = torch.device(device)
+    key = (int(in_size), int(out_size), device.index if device.index is not None else torch.cuda.current_device())
+    hit = _RESIZE_TABLES.get(key)
+    if hit is not None:
+        return hit
+    L = _lib.load()
+    ksize = int(L.ftx_resize_ksize(key[0], key[1]))
+    if ksize < 0:
+        check(ksize, "ftx_resize_ksize")
+    bounds = np.empty((key[1], 2), dtype=np.int32)
+    kk = np.empty((key[1], ksize), dtype=np.int32)
+    vp = ctypes.c_void_p
+    check(L.ftx_resize_coeffs_host(key[0], key[1], bounds.ctypes.data_as(vp), kk.ctypes.data_as(vp)), "ftx_resize_coeffs_host")
+    dev = torch.device("cuda", key[2])
+    if len(_RESIZE_TABLES) >= 256:
+        _RESIZE_TABLES.clear()
+    hit = _RESIZE_TABLES[key] = (torch.from_numpy(bounds).to(dev), torch.from_numpy(kk).to(dev), ksize)
+    return hit
+
+
+def resize_bilinear_u8(image_u8: torch.Tensor, size) -> torch.Tensor:
+    """PIL's `image.resize(size, Image.BILINEAR)` on a uint8 RGB frame, bit-exact with Pillow's 8-bit resample: image_u8 (H, W, 3), or a
+    batch (B, H, W, 3) of equal-sized frames resized by the same launches; a crop view with a row pitch is fine (pixels packed within
+    a row, as for the colour jitter).  size = (width, height), Pillow's order.  Returns a contiguous (height, width, 3) or
+    (B, height, width, 3) uint8; both directions are supported.  When the size does not change the INPUT is returned, a view and
+    not the copy Pillow makes.  The coefficient tables stay on the device (resize_table), so a stream of equal-sized frames makes no
+    host-to-device copy and allocates the output only."""
+    if not isinstance(image_u8, torch.Tensor) or not image_u8.is_cuda or image_u8.dtype != torch.uint8 or image_u8.dim() not in (3, 4):
+        raise ValueError("resize_bilinear_u8: expected a (H, W, 3) or (B, H, W, 3) uint8 CUDA tensor")
+    batched = image_u8.dim() == 4
+    n = image_u8.shape[0] if batched else 1
+    h, w, c = image_u8.shape[-3:]
+    st = image_u8.stride()
+    if c != 3 or st[-1] != 1 or st[-2] != c or st[-3] < c * w or (batched and st[0] < 0):
+        raise ValueError(f"resize_bilinear_u8: 3 channels, pixels packed within a row (shape {tuple(image_u8.shape)}, strides {st})")
+    ow, oh = (int(v) for v in size)
+    if ow <= 0 or oh <= 0 or h <= 0 or w <= 0:
+        raise ValueError(f"resize_bilinear_u8: sizes must be positive, got {(w, h)} -> {(ow, oh)}")
+    if (ow, oh) == (w, h):
+        return image_u8
+    L = _lib.load()
+    out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=image_u8.device)
+    if n == 0:
+        return out
+    bx, kx, ksx = resize_table(w, ow, image_u8.device) if ow != w else (None, None, 0)
+    by, ky, ksy = resize_table(h, oh, image_u8.device) if oh != h else (None, None, 0)
+    nbytes = _ws_bytes("ftx_resize_workspace_bytes", n, h, w, oh, ow)
+    ws = hold = 0
+    if nbytes:
+        if torch.cuda.is_current_stream_capturing():   # from the graph's pool; the kernels recorded below are ordered before its reuse
+            hold = torch.empty((nbytes,), dtype=torch.uint8, device=image_u8.device)
+            ws = hold.data_ptr()
+        else:
+            ws = _carve(image_u8, nbytes)[0]
+    check(L.ftx_resize_bilinear_u8(ptr(image_u8), st[0] if batched else 0, st[-3], n, h, w, c, ptr(bx), ptr(kx), ksx, ptr(by), ptr(ky), ksy,
+                                   oh, ow, ptr(out), ws, nbytes, stream()), "ftx_resize_bilinear_u8")
+    return out if batched else out[0]

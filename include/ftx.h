@@ -421,6 +421,34 @@ int ftx_color_jitter_u8(const uint8_t *src, int64_t pitch, int32_t height, int32
  * mean_host / std_host (3 floats each) both NULL = no normalisation. */
 int ftx_color_jitter_chw(const uint8_t *src, int64_t pitch, int32_t height, int32_t width, int32_t channels, const int32_t *ops_host, const double *factors_host, int32_t n_ops, int32_t flip, const float *mean_host, const float *std_host, float *dst, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- image resize of the NuScenes loader: data/nuscenes/nuscenes_dataloader.py:185, image.resize(size, Image.BILINEAR) ----
+ * PRECISION: bit-exact with Pillow's 8bpc bilinear resample (libImaging/Resample.c), which is integer arithmetic on a table that is
+ * built in double.  For one axis of input length `in` and output length `out`, over the whole axis, all in C double:
+ *   scale = filterscale = in / out;  if (filterscale < 1.0) filterscale = 1.0;  support = 1.0 * filterscale;
+ *   ksize = (int)ceil(support) * 2 + 1
+ *   for xx in 0..out-1:
+ *     center = (xx + 0.5) * scale
+ *     xmin = (int)(center - support + 0.5), at least 0;  xmax = (int)(center + support + 0.5), at most in;  taps = xmax - xmin
+ *     k[x] = tri((x + xmin - center + 0.5) * (1.0 / filterscale)) for x < taps, each divided by their sum if that is not 0; 0 up to ksize
+ *     kk[x] = (int)(k[x] < 0 ? -0.5 + k[x] * (1 << 22) : 0.5 + k[x] * (1 << 22))
+ *   tri(a) = |a| < 1.0 ? 1.0 - |a| : 0.0;  the (int) casts truncate toward zero; 1.0 / filterscale is formed once and multiplied.
+ * A pass over one axis: acc = (1 << 21) + sum_x src[xmin + x] * kk[x] in 32-bit integers per channel, result clip8(acc >> 22)
+ * (arithmetic shift, clamped to 0..255).  The horizontal pass runs first and rounds and clamps to uint8; the vertical pass works
+ * on those bytes.  A pass whose axis keeps its length is not run.
+ * ftx_resize_ksize / ftx_resize_coeffs_host are host code and need no GPU: bounds_host (out, 2) int32 = (xmin, taps) per output
+ * index, kk_host (out, ksize) int32.  They answer -1 for in <= 0, out <= 0 or a null pointer.
+ * ftx_resize_bilinear_u8: n_frames equal-sized RGB frames, frame f at src + f * frame_stride, row r at + r * pitch (pitch >= 3 * in_w
+ * bytes, any byte offset: a crop view needs no copy); channels must be 3.  bounds_x / kk_x / ksize_x are the table of (in_w, out_w),
+ * bounds_y / kk_y / ksize_y that of (in_h, out_h), DEVICE pointers; the table of an axis that keeps its length is not read (NULL
+ * allowed).  Equal sizes on both axes are refused: there is nothing to resample.  dst (n_frames, out_h, out_w, 3) uint8, contiguous.
+ * Both directions (shrinking and enlarging) are supported.  workspace: caller-owned, 16-byte aligned,
+ * ftx_resize_workspace_bytes(...) bytes (the uint8 intermediate; 0 when only one axis changes, NULL allowed then).  One launch per
+ * axis that changes, for all frames; no atomics, no host synchronisation, capturable. */
+int32_t ftx_resize_ksize(int32_t in, int32_t out);
+int ftx_resize_coeffs_host(int32_t in, int32_t out, int32_t *bounds_host, int32_t *kk_host);
+size_t ftx_resize_workspace_bytes(int32_t n_frames, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w);
+int ftx_resize_bilinear_u8(const uint8_t *src, int64_t frame_stride, int64_t pitch, int32_t n_frames, int32_t in_h, int32_t in_w, int32_t channels, const int32_t *bounds_x, const int32_t *kk_x, int32_t ksize_x, const int32_t *bounds_y, const int32_t *kk_y, int32_t ksize_y, int32_t out_h, int32_t out_w, uint8_t *dst, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
