@@ -9,6 +9,8 @@ the GPU, index tensors are int32 (torchsparse returns int64 and immediately
 `.int()`s them, utils.py:22,51)."""
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -243,8 +245,6 @@ def sorted_rank(sorted_keys: torch.Tensor, n_sorted: torch.Tensor, queries: torc
 
 def rotate_points(points: torch.Tensor, rot) -> torch.Tensor:
     """points (N,3) float32 @ rot (3,3) float32 (host array) with the rounding of numpy's `points.dot(rot)` (libftx)."""
-    import ctypes
-    import numpy as np
     L = _lib.load()
     req(points, F32, "rotate_points points", 2)
     if points.shape[1] != 3:
@@ -475,42 +475,83 @@ _PAIRS_WGRAD = {False: ("ftx_spconv_pairs_wgrad", "ftx_spconv_pairs_wgrad_worksp
 _ROWS_GEMM = {False: "ftx_rows_gemm", True: "ftx_rows_gemm_bf16"}
 
 
+# The launchers: the ONE call site of each convolution / BatchNorm entry point and of its launch-log metadata.  Pointers are raw device
+# addresses; results and temporaries go where the caller says (sparse_conv and batch_norm allocate tensors, so they can be captured
+# into a HIP graph; conv_bn_train carves its temporaries from the stream's scratch buffer).
+def _launch_pairs(a, rows_a, gather, w, w_transposed, pos, koff, n_pairs, ca, co, kvol, tmp, out, n_out, st, bf16, part=0, nb=0):
+    """tmp[p] = A[gather[p]] @ W[k(p)], then out = the reduce of tmp over the offsets through `pos`.  part != 0: the reduce also leaves
+    the BatchNorm statistics of `out` there (nb partial rows + the totals row, float64; `st` then has its tickets attached)."""
+    L = _lib.load()
+    gemm, kind = _PAIRS_GEMM[bf16]
+    meta = dict(pairs=n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol)
+    _log_launch(kind, meta, lambda: check(getattr(L, gemm)(a, rows_a, gather, w, w_transposed, koff, n_pairs, ca, co, kvol, tmp, st), gemm))
+    if part:
+        _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce_stats(tmp, pos, n_out, co, kvol, out, part, nb, st), "ftx_spconv_reduce_stats"))
+    else:
+        _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce(tmp, pos, n_out, co, kvol, out, st), "ftx_spconv_reduce"))
+
+
+def _launch_direct(a, rows_a, gather, scatter, w, w_transposed, koff, n_pairs, ca, co, kvol, out, n_out, st, bf16):
+    """out[scatter[p]] = A[gather[p]] @ W[k(p)]: the pair GEMM with the scatter epilogue."""
+    L = _lib.load()
+    gemm = _PAIRS_GEMM_SCATTER[bf16]
+    _log_launch(_PAIRS_GEMM[bf16][1], dict(pairs=n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol, direct=True), lambda: check(getattr(L, gemm)(
+        a, rows_a, gather, scatter, w, w_transposed, koff, n_pairs, ca, co, kvol, out, n_out, st), gemm))
+
+
+def _launch_ostat(a, rows_a, nbr, n_out, w, w_transposed, flip, ca, co, kvol, out, part, nb, st, pairs):
+    """out[o] = sum_k A[nbr[k, o]] @ W[k]; part != 0: also the BatchNorm statistics, as _launch_pairs.  `pairs` is for the log only."""
+    L = _lib.load()
+    _log_launch("spconv_ostat", dict(pairs=pairs, n_out=n_out, ca=ca, co=co, kvol=kvol, direct=True), lambda: check(L.ftx_spconv_ostat(
+        a, rows_a, nbr, n_out, w, w_transposed, flip, ca, co, kvol, out, part, nb, st), "ftx_spconv_ostat"))
+
+
+def _launch_wgrad(a, rows_a, idx_a, g, rows_g, idx_g, koff, n_pairs, ca, cg, kvol, dw, ws, ws_bytes, st, bf16):
+    """dw[k] = sum over the pairs p of offset k of A[idx_a[p]]^T G[idx_g[p]]."""
+    L = _lib.load()
+    fn, _, kind = _PAIRS_WGRAD[bf16]
+    _log_launch(kind, dict(pairs=n_pairs, n_out=rows_g, ca=ca, co=cg, kvol=kvol), lambda: check(getattr(L, fn)(
+        a, rows_a, idx_a, g, rows_g, idx_g, koff, n_pairs, ca, cg, kvol, dw, ws, ws_bytes, st), fn))
+
+
+def _launch_bn_fwd(x, residual, gamma, beta, running_mean, running_var, momentum, eps, n, c, relu, y, mean, invstd, st, ws=0, ws_bytes=0, totals=0):
+    """y = relu?(BN(x) (+ residual)).  totals = 0: a statistics pass and the apply pass both read x (workspace `ws`); otherwise the
+    address of the column totals that the convolution left while it wrote x, and x is read once."""
+    L = _lib.load()
+    args = (x, residual, gamma, beta, running_mean, running_var, float(momentum), float(eps), n, c, int(relu), y, mean, invstd)
+    if totals:
+        _log_launch("bn_fwd", dict(n=n, c=c, reads=1 + (residual != 0), writes=1), lambda: check(L.ftx_bn_train_fwd_totals(*args, totals, st), "ftx_bn_train_fwd_totals"))
+    else:
+        _log_launch("bn_fwd", dict(n=n, c=c, reads=2 + (residual != 0), writes=1), lambda: check(L.ftx_bn_train_fwd(*args, ws, ws_bytes, st), "ftx_bn_train_fwd"))
+
+
+def _launch_bn_bwd(gy, x, y, gamma, beta, mean, invstd, n, c, relu, gx, gres, ggamma, gbeta, ws, ws_bytes, st):
+    """Two passes (statistics, apply), each reading gy and x (and y for the ReLU mask when a residual went into it: otherwise the mask is
+    recomputed from x; beta = 0 reads y in that case too); one or two row matrices written (gres = 0: there was no residual)."""
+    L = _lib.load()
+    has_res = gres != 0
+    _log_launch("bn_bwd", dict(n=n, c=c, reads=2 * (2 + (1 if (relu and has_res) else 0)), writes=1 + (1 if has_res else 0)), lambda: check(
+        L.ftx_bn_train_bwd(gy, x, y, gamma, beta, mean, invstd, n, c, int(relu), gx, gres, ggamma, gbeta, ws, ws_bytes, st), "ftx_bn_train_bwd"))
+
+
 def _spconv_apply(A, W, gather, pos, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False):
     """reduce(pairs_gemm(A[gather] @ W[k]), pos) -> (n_rows_out, co)."""
-    L = _lib.load()
-    gemm, kind = _PAIRS_GEMM[bool(bf16)]
     rows_a, ca = A.shape
-    kvol = koff.shape[0] - 1
     tmp = _empty((n_pairs, co), F32, A)
     out = _empty((n_rows_out, co), F32, A)
-
-    def launch_gemm():
-        check(getattr(L, gemm)(ptr(A), rows_a, ptr(gather), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, kvol, ptr(tmp), stream()), gemm)
-
-    def launch_reduce():
-        check(L.ftx_spconv_reduce(ptr(tmp), ptr(pos), n_rows_out, co, kvol, ptr(out), stream()), "ftx_spconv_reduce")
-
-    meta = dict(pairs=n_pairs, n_out=n_rows_out, ca=ca, co=co, kvol=kvol)
-    _log_launch(kind, meta, launch_gemm)
-    _log_launch("spconv_reduce", meta, launch_reduce)
+    _launch_pairs(ptr(A), rows_a, ptr(gather), ptr(W), int(w_transposed), ptr(pos), ptr(koff), n_pairs, ca, co, koff.shape[0] - 1, ptr(tmp), ptr(out),
+                  n_rows_out, stream(), bool(bf16))
     return out
 
 
 def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False):
     """out[scatter[p]] = A[gather[p]] @ W[k(p)] in ONE launch, for maps whose destination side is a bijection of the pair list."""
-    L = _lib.load()
-    gemm, kind = _PAIRS_GEMM_SCATTER[bool(bf16)], _PAIRS_GEMM[bool(bf16)][1]
     rows_a, ca = A.shape
-    kvol = koff.shape[0] - 1
     if n_pairs != n_rows_out:
         raise ValueError("direct sparse conv: the pair list must cover every destination row exactly once")
     out = _empty((n_rows_out, co), F32, A)
-
-    def launch():
-        check(getattr(L, gemm)(ptr(A), rows_a, ptr(gather), ptr(scatter), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, kvol,
-                               ptr(out), n_rows_out, stream()), gemm)
-
-    _log_launch(kind, dict(pairs=n_pairs, n_out=n_rows_out, ca=ca, co=co, kvol=kvol, direct=True), launch)
+    _launch_direct(ptr(A), rows_a, ptr(gather), ptr(scatter), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, koff.shape[0] - 1, ptr(out),
+                   n_rows_out, stream(), bool(bf16))
     return out
 
 
@@ -532,43 +573,31 @@ def ostat_preferred(ca, co, kvol, w_transposed=False, rows=0):
     """Where the output-stationary kernel is FASTER than pair GEMM + reduce on MI355X (tools/bench_spconv.py, profiles/r03_spconv_layer_micro.txt):
     forward convolutions with c_in <= 32 and c_out = 32 -- the stem, the 32 -> 32 layers of levels 1 and 2, the strided 32 -> 32 layers.
     It is bound by instruction issue (~23 instructions per pair), so 64-channel layers and the transposed-W data-gradient form lose
-    (csrc/ftx_spconv_ostat.hip)."""
+    (csrc/ftx_spconv_ostat.hip).  No data gradient is therefore ever sent to it: _conv_route asks for forward convolutions only, and the
+    mirrored form (w_transposed = 1, flip = 1) is reached through _spconv_ostat alone."""
     return ostat_supported(ca, co, kvol, w_transposed, rows) and not w_transposed and co == 32 and ca <= 32
 
 
 def _spconv_ostat(A, W, nbr, n_rows_out, co, w_transposed, flip, part=0, nb=0, pairs=0):
     """out[o] = sum_k A[nbr[k, o]] @ W[k] in ONE launch (no pair rows, no reduce pass); `part`: also the BatchNorm statistics."""
-    L = _lib.load()
     rows_a, ca = A.shape
     kvol = nbr.shape[0]
     if nbr.shape[1] != n_rows_out:
         raise ValueError("ostat sparse conv: the neighbour table does not match the output rows")
     out = _empty((n_rows_out, co), F32, A)
-    st = _stream_scratch() if part else stream()
-
-    def launch():
-        check(L.ftx_spconv_ostat(ptr(A), rows_a, ptr(nbr), n_rows_out, ptr(W), int(w_transposed), int(flip), ca, co, kvol, ptr(out), part, nb, st),
-              "ftx_spconv_ostat")
-
-    _log_launch("spconv_ostat", dict(pairs=pairs, n_out=n_rows_out, ca=ca, co=co, kvol=kvol, direct=True), launch)
+    _launch_ostat(ptr(A), rows_a, ptr(nbr), n_rows_out, ptr(W), int(w_transposed), int(flip), ca, co, kvol, ptr(out), part, nb,
+                  _stream_scratch() if part else stream(), pairs)
     return out
 
 
 def _spconv_wgrad(A, idx_a, G, idx_g, koff, n_pairs, bf16=False):
-    L = _lib.load()
-    fn, ws_fn, kind = _PAIRS_WGRAD[bool(bf16)]
     rows_a, ca = A.shape
     rows_g, cg = G.shape
     kvol = koff.shape[0] - 1
     dW = _empty((kvol, ca, cg), F32, A)
-    ws_bytes = _ws_bytes(ws_fn, n_pairs, ca, cg, kvol)
+    ws_bytes = _ws_bytes(_PAIRS_WGRAD[bool(bf16)][1], n_pairs, ca, cg, kvol)
     ws = _scratch(ws_bytes, A)
-
-    def launch():
-        check(getattr(L, fn)(ptr(A), rows_a, ptr(idx_a), ptr(G), rows_g, ptr(idx_g), ptr(koff), n_pairs, ca, cg, kvol, ptr(dW), ptr(ws),
-                             ws_bytes, stream()), fn)
-
-    _log_launch(kind, dict(pairs=n_pairs, n_out=rows_g, ca=ca, co=cg, kvol=kvol), launch)
+    _launch_wgrad(ptr(A), rows_a, ptr(idx_a), ptr(G), rows_g, ptr(idx_g), ptr(koff), n_pairs, ca, cg, kvol, ptr(dW), ptr(ws), ws_bytes, stream(), bool(bf16))
     return dW
 
 
@@ -580,33 +609,64 @@ def _conv_shapes(feats, kernel, km, transposed):
     return kvol, ca, co, n_in, n_out
 
 
+def _map_sides(km, transposed):
+    """(src, src_pos, dst, dst_pos): per pair the row the convolution reads (`src`) and the row it writes (`dst`), and per side the
+    (kvol, rows) table of each row's pairs.  The forward gathers `src` and scatters to `dst` / reduces through `dst_pos`; the data
+    gradient gathers `dst` and scatters to `src` / reduces through `src_pos`.  `transposed` swaps the two sides of the map."""
+    if transposed:
+        return km.pair_out, km.pos, km.pair_in, km.pos_t
+    return km.pair_in, km.pos_t, km.pair_out, km.pos
+
+
+_EMPTY, _DIRECT, _OSTAT, _PAIRS = "empty", "direct", "ostat", "pairs"
+
+
+def _conv_route(km, transposed, ca, co, kvol, rows, bf16, grad=False):
+    """How sparse_conv and conv_bn_train compute the (rows, co) result of a ca -> co GEMM over the map's pairs: a layer's forward, or
+    (grad=True) its data gradient.  _DIRECT: one launch with the scatter epilogue, where every row written is the destination of
+    exactly one pair (the strided 2^3 map seen from its fine side: forward of the transposed conv, data gradient of the strided one).
+    _OSTAT: the output-stationary kernel on the neighbour table, for the thin fp32 forward layers.  _PAIRS: pair GEMM + reduce.
+    _EMPTY: no pair or no row -- the forward takes the pair list without the statistics-producing forms, the gradient is a zero fill."""
+    if grad:
+        if rows == 0 or km.n_pairs == 0:
+            return _EMPTY
+        return _DIRECT if (not transposed and km.fine_bijective) else _PAIRS
+    if transposed and km.fine_bijective:
+        return _DIRECT
+    if rows == 0 or km.n_pairs == 0:
+        return _EMPTY
+    if not bf16 and not transposed and ostat_preferred(ca, co, kvol, rows=rows):
+        return _OSTAT
+    return _PAIRS
+
+
 def _conv_forward(feats, kernel, km, transposed, bf16=False):
     """bf16=True: the bf16-operand kernels; the output-stationary kernel is exact fp32 only, so every layer takes the pair list."""
     kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
-    if transposed and km.fine_bijective:
-        # every fine row is the destination of exactly one pair: the GEMM epilogue writes `out` itself
-        return _spconv_direct(feats, kernel, km.pair_out, km.pair_in, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
-    if not bf16 and not transposed and n_out > 0 and km.n_pairs > 0 and ostat_preferred(ca, co, kvol, rows=n_out):
+    route = _conv_route(km, transposed, ca, co, kvol, n_out, bf16)
+    src, _, dst, dst_pos = _map_sides(km, transposed)
+    if route == _DIRECT:
+        return _spconv_direct(feats, kernel, src, dst, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
+    if route == _OSTAT:
         return _spconv_ostat(feats, kernel, km.nbr, n_out, co, 0, 0, pairs=km.n_pairs)
-    gather, pos = (km.pair_out, km.pos_t) if transposed else (km.pair_in, km.pos)
-    return _spconv_apply(feats, kernel, gather, pos, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
+    return _spconv_apply(feats, kernel, src, dst_pos, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
 
 
 def _conv_backward(feats, kernel, km, transposed, grad_out, need_feats, need_kernel, bf16=False):
     kvol, ca, co = kernel.shape
+    n_feats = feats.shape[0]
     g_feats = g_kernel = None
-    in_side, out_side = (km.pair_out, km.pair_in) if transposed else (km.pair_in, km.pair_out)
+    src, src_pos, dst, _ = _map_sides(km, transposed)
     if need_feats:
-        if not transposed and km.fine_bijective:
-            g_feats = _spconv_direct(grad_out, kernel, km.pair_out, km.pair_in, km.koff, km.n_pairs, feats.shape[0], ca, 1, bf16=bf16)
-        elif not bf16 and not transposed and km.submanifold and km.n_pairs > 0 and ostat_preferred(co, ca, kvol, True, rows=feats.shape[0]):
-            # symmetric map: the data gradient is the same output-stationary kernel on the same table, read mirrored
-            g_feats = _spconv_ostat(grad_out, kernel, km.nbr, feats.shape[0], ca, 1, 1, pairs=km.n_pairs)
+        route = _conv_route(km, transposed, co, ca, kvol, n_feats, bf16, grad=True)
+        if route == _EMPTY:
+            g_feats = torch.zeros((n_feats, ca), dtype=F32, device=feats.device)
+        elif route == _DIRECT:
+            g_feats = _spconv_direct(grad_out, kernel, dst, src, km.koff, km.n_pairs, n_feats, ca, 1, bf16=bf16)
         else:
-            pos_in = km.pos if transposed else km.pos_t
-            g_feats = _spconv_apply(grad_out, kernel, out_side, pos_in, km.koff, km.n_pairs, feats.shape[0], ca, 1, bf16=bf16)
+            g_feats = _spconv_apply(grad_out, kernel, dst, src_pos, km.koff, km.n_pairs, n_feats, ca, 1, bf16=bf16)
     if need_kernel:
-        g_kernel = _spconv_wgrad(feats, in_side, grad_out, out_side, km.koff, km.n_pairs, bf16=bf16)
+        g_kernel = _spconv_wgrad(feats, src, grad_out, dst, km.koff, km.n_pairs, bf16=bf16)
     return g_feats, g_kernel
 
 
@@ -760,28 +820,32 @@ def rows_matmul(x, kernel, bf16=False):
 
 
 # ---------------------------------------------------------------- BatchNorm (+residual)(+ReLU)
+def _bn_operands(residual, gamma, beta, n, c, who, params):
+    """Operand checks of the training-mode BatchNorm nodes; returns the contiguous residual."""
+    if residual is not None:
+        residual = req(residual.contiguous(), F32, "bn residual", 2)
+        if residual.shape != (n, c):
+            raise ValueError(who + ": residual shape mismatch")
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        req(t, F32, "bn " + nm, 1)
+        if t.shape[0] != c:
+            raise ValueError(f"{who}: {params}")
+    return residual
+
+
 class _BatchNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, remask):
-        L = _lib.load()
         x = req(x.contiguous(), F32, "bn x", 2)
         n, c = x.shape
-        if residual is not None:
-            residual = req(residual.contiguous(), F32, "bn residual", 2)
-            if residual.shape != x.shape:
-                raise ValueError("bn: residual shape mismatch")
-        for t, nm in ((gamma, "gamma"), (beta, "beta")):
-            req(t, F32, "bn " + nm, 1)
-            if t.shape[0] != c:
-                raise ValueError("bn: parameter length != channels")
+        residual = _bn_operands(residual, gamma, beta, n, c, "bn", "parameter length != channels")
         y = torch.empty_like(x)
         mean = _empty((c,), F32, x)
         invstd = _empty((c,), F32, x)
         ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n, c)
         ws = _scratch(ws_bytes, x)
-        _log_launch("bn_fwd", dict(n=n, c=c, reads=2 + (residual is not None), writes=1), lambda: check(L.ftx_bn_train_fwd(
-            ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum), float(eps),
-            n, c, int(relu), ptr(y), ptr(mean), ptr(invstd), ptr(ws), ws_bytes, _stream_scratch()), "ftx_bn_train_fwd"))
+        _launch_bn_fwd(ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), momentum, eps, n, c, relu, ptr(y), ptr(mean),
+                       ptr(invstd), _stream_scratch(), ptr(ws), ws_bytes)
         ctx.save_for_backward(x, y, gamma, beta, mean, invstd)
         ctx.relu = int(relu)
         ctx.has_res = residual is not None
@@ -792,7 +856,15 @@ class _BatchNormTrain(torch.autograd.Function):
     def backward(ctx, gy):
         x, y, gamma, beta, mean, invstd = ctx.saved_tensors
         gy = req(gy.contiguous(), F32, "bn grad", 2)
-        gx, gres, ggamma, gbeta = _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, ctx.relu, ctx.has_res, ctx.remask)
+        n, c = x.shape
+        gx = torch.empty_like(x)
+        gres = torch.empty_like(x) if ctx.has_res else None
+        ggamma = _empty((c,), F32, x)
+        gbeta = _empty((c,), F32, x)
+        ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n, c)
+        ws = _scratch(ws_bytes, x)
+        _launch_bn_bwd(ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta) if ctx.remask else 0, ptr(mean), ptr(invstd), n, c, ctx.relu, ptr(gx), ptr(gres),
+                       ptr(ggamma), ptr(gbeta), ptr(ws), ws_bytes, _stream_scratch())
         return gx, gres, ggamma, gbeta, None, None, None, None, None, None
 
 
@@ -821,23 +893,6 @@ class _BatchNormEval(torch.autograd.Function):
         return gx, (dy if ctx.has_res else None), None, None, None, None, None, None
 
 
-def _bn_backward_launch(gy, x, y, gamma, beta, mean, invstd, relu, has_res, remask):
-    L = _lib.load()
-    n, c = x.shape
-    gx = torch.empty_like(x)
-    gres = torch.empty_like(x) if has_res else None
-    ggamma = _empty((c,), F32, x)
-    gbeta = _empty((c,), F32, x)
-    ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n, c)
-    ws = _scratch(ws_bytes, x)
-    # two passes (statistics, apply), each reading gy and x (and y for the ReLU mask when a residual went into it: otherwise the mask is
-    # recomputed from x); one or two row matrices written
-    _log_launch("bn_bwd", dict(n=n, c=c, reads=2 * (2 + (1 if (relu and has_res) else 0)), writes=1 + (1 if has_res else 0)), lambda: check(L.ftx_bn_train_bwd(
-        ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta) if remask else 0, ptr(mean), ptr(invstd), n, c, int(relu), ptr(gx), ptr(gres), ptr(ggamma),
-        ptr(gbeta), ptr(ws), ws_bytes, _stream_scratch()), "ftx_bn_train_bwd"))
-    return gx, gres, ggamma, gbeta
-
-
 class _ConvBNTrain(torch.autograd.Function):
     """spnn.Conv3d -> spnn.BatchNorm (training statistics) (-> + residual) (-> ReLU) as ONE autograd node
     (models/spvcnn.py:22-35,38-50,53-79).  The reduce pass of the convolution produces the BatchNorm's batch statistics while
@@ -845,113 +900,75 @@ class _ConvBNTrain(torch.autograd.Function):
     once, by the one apply launch (ftx_bn_train_fwd_totals), instead of twice;
     one node instead of two also halves the host work per layer, and everything that does not outlive the call -- the pair rows `tmp`,
     the partial statistics, the BatchNorm input gradient between the two halves of the backward, the kernel workspaces -- lives in the
-    stream's scratch buffer instead of six allocator round trips per layer and direction."""
+    stream's scratch buffer instead of six allocator round trips per layer and direction.  Route and launchers are sparse_conv's."""
 
     @staticmethod
     def forward(ctx, feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bf16, remask):
-        L = _lib.load()
         feats = req(feats.contiguous(), F32, "conv3d feats", 2)
         kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
         kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
-        if residual is not None:
-            residual = req(residual.contiguous(), F32, "bn residual", 2)
-            if residual.shape != (n_out, co):
-                raise ValueError("conv_bn: residual shape mismatch")
-        for t, nm in ((gamma, "gamma"), (beta, "beta")):
-            req(t, F32, "bn " + nm, 1)
-            if t.shape[0] != co:
-                raise ValueError("conv_bn: BatchNorm parameter length != output channels")
+        residual = _bn_operands(residual, gamma, beta, n_out, co, "conv_bn", "BatchNorm parameter length != output channels")
         stats = _empty((2, co), F32, feats)              # row 0: batch mean, row 1: 1 / sqrt(var + eps)
-        p_mean, p_invstd = stats.data_ptr(), stats.data_ptr() + 4 * co
+        x = _empty((n_out, co), F32, feats)
+        y = torch.empty_like(x)
         st = _stream_scratch()
-        direct = (transposed and km.fine_bijective) or n_out == 0 or km.n_pairs == 0
-        if direct:
-            x = _conv_forward(feats, kernel, km, transposed, bf16)
-            y = torch.empty_like(x)
+        route = _conv_route(km, transposed, ca, co, kvol, n_out, bf16)
+        src, _, dst, dst_pos = _map_sides(km, transposed)
+        tmp_bytes = 0 if route in (_DIRECT, _OSTAT) else 4 * km.n_pairs * co
+        if route in (_OSTAT, _PAIRS):   # the convolution leaves the statistics (nb partial rows + the totals row, float64), then the apply pass
+            nb = _ws_bytes("ftx_spconv_ostat_blocks", n_out) if route == _OSTAT else _ws_bytes("ftx_spconv_reduce_stats_blocks", n_out, co)
+            tmp, part = _carve(feats, tmp_bytes, 16 * (nb + 1) * co)
+            ws = ws_bytes = 0
+            totals = part + 16 * nb * co
+        else:                           # scatter epilogue or empty map: the plain convolution, then the BatchNorm's own statistics pass
             ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n_out, co)
-            ws, = _carve(x, ws_bytes)
-            _log_launch("bn_fwd", dict(n=n_out, c=co, reads=2 + (residual is not None), writes=1), lambda: check(L.ftx_bn_train_fwd(
-                ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum), float(eps),
-                n_out, co, int(relu), ptr(y), p_mean, p_invstd, ws, ws_bytes, st), "ftx_bn_train_fwd"))
-        elif not bf16 and not transposed and ostat_preferred(ca, co, kvol, rows=n_out):
-            # thin layer: convolution + statistics in one launch, then the apply pass
-            nb = _ws_bytes("ftx_spconv_ostat_blocks", n_out)
-            part, = _carve(feats, 16 * (nb + 1) * co)
-            x = _spconv_ostat(feats, kernel, km.nbr, n_out, co, 0, 0, part=part, nb=nb, pairs=km.n_pairs)
-            y = torch.empty_like(x)
-            _log_launch("bn_fwd", dict(n=n_out, c=co, reads=1 + (residual is not None), writes=1), lambda: check(L.ftx_bn_train_fwd_totals(
-                ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum),
-                float(eps), n_out, co, int(relu), ptr(y), p_mean, p_invstd, part + 16 * nb * co, st), "ftx_bn_train_fwd_totals"))
+            tmp, ws = _carve(feats, tmp_bytes, ws_bytes)
+            part = nb = totals = 0
+        if route == _DIRECT:
+            _launch_direct(ptr(feats), n_in, ptr(src), ptr(dst), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(x), n_out, st, bf16)
+        elif route == _OSTAT:
+            _launch_ostat(ptr(feats), n_in, ptr(km.nbr), n_out, ptr(kernel), 0, 0, ca, co, kvol, ptr(x), part, nb, st, km.n_pairs)
         else:
-            gather, pos = (km.pair_out, km.pos_t) if transposed else (km.pair_in, km.pos)
-            x = _empty((n_out, co), F32, feats)
-            y = torch.empty_like(x)
-            nb = _ws_bytes("ftx_spconv_reduce_stats_blocks", n_out, co)
-            tmp, part = _carve(feats, 4 * km.n_pairs * co, 16 * (nb + 1) * co)    # nb partial rows + the totals row, float64
-            meta = dict(pairs=km.n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol)
-            gemm, kind = _PAIRS_GEMM[bool(bf16)]
-            _log_launch(kind, meta, lambda: check(getattr(L, gemm)(
-                ptr(feats), n_in, ptr(gather), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, tmp, st), gemm))
-            _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce_stats(
-                tmp, ptr(pos), n_out, co, kvol, ptr(x), part, nb, st), "ftx_spconv_reduce_stats"))
-            _log_launch("bn_fwd", dict(n=n_out, c=co, reads=1 + (residual is not None), writes=1), lambda: check(L.ftx_bn_train_fwd_totals(
-                ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum),
-                float(eps), n_out, co, int(relu), ptr(y), p_mean, p_invstd, part + 16 * nb * co, st), "ftx_bn_train_fwd_totals"))
+            _launch_pairs(ptr(feats), n_in, ptr(src), ptr(kernel), 0, ptr(dst_pos), ptr(km.koff), km.n_pairs, ca, co, kvol, tmp, ptr(x), n_out, st, bf16,
+                          part, nb)
+        _launch_bn_fwd(ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), momentum, eps, n_out, co, relu, ptr(y),
+                       stats.data_ptr(), stats.data_ptr() + 4 * co, st, ws, ws_bytes, totals)
         ctx.save_for_backward(feats, kernel, x, y, gamma, beta, stats)
         ctx.km, ctx.transposed, ctx.relu, ctx.has_res, ctx.bf16, ctx.remask = km, transposed, int(relu), residual is not None, bf16, bool(remask)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        L = _lib.load()
         feats, kernel, x, y, gamma, beta, stats = ctx.saved_tensors
-        km, transposed = ctx.km, ctx.transposed
+        km, transposed, bf16 = ctx.km, ctx.transposed, ctx.bf16
         gy = req(gy.contiguous(), F32, "conv_bn grad", 2)
         n, co = x.shape
         kvol, ca, _ = kernel.shape
+        n_feats = feats.shape[0]
         need_feats, need_kernel = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        bf16 = ctx.bf16
-        gemm, gemm_kind = _PAIRS_GEMM[bf16]
-        wgrad, wgrad_ws, wgrad_kind = _PAIRS_WGRAD[bf16]
         st = _stream_scratch()
-        p_mean, p_invstd = stats.data_ptr(), stats.data_ptr() + 4 * co
         gparams = _empty((2, co), F32, x)               # row 0: d gamma, row 1: d beta
         gres = torch.empty_like(x) if ctx.has_res else None
+        src, src_pos, dst, _ = _map_sides(km, transposed)
+        route = _conv_route(km, transposed, co, ca, kvol, n_feats, bf16, grad=True) if need_feats else None
         bn_ws_bytes = _ws_bytes("ftx_bn_workspace_bytes", n, co)
-        in_side, out_side = (km.pair_out, km.pair_in) if transposed else (km.pair_in, km.pair_out)
-        direct = need_feats and (not transposed) and km.fine_bijective
-        ostat = need_feats and (not bf16) and (not direct) and (not transposed) and km.submanifold and km.n_pairs > 0 and ostat_preferred(co, ca, kvol, True, rows=feats.shape[0])
-        n_feats = feats.shape[0]
-        wg_bytes = _ws_bytes(wgrad_ws, km.n_pairs, ca, co, kvol) if (need_kernel and km.n_pairs > 0) else 0
-        tmp_bytes = 4 * km.n_pairs * ca if (need_feats and not direct and not ostat) else 0
-        bn_ws, gx, tmp, wg_ws = _carve(x, bn_ws_bytes, 4 * n * co, tmp_bytes, wg_bytes)
+        wg_bytes = _ws_bytes(_PAIRS_WGRAD[bf16][1], km.n_pairs, ca, co, kvol) if (need_kernel and km.n_pairs > 0) else 0
+        bn_ws, gx, tmp, wg_ws = _carve(x, bn_ws_bytes, 4 * n * co, 4 * km.n_pairs * ca if route == _PAIRS else 0, wg_bytes)
         # BatchNorm half: gx = d loss / d (convolution output) stays in the scratch buffer, it is consumed by the two calls below
-        _log_launch("bn_bwd", dict(n=n, c=co, reads=2 * (2 + (1 if (ctx.relu and ctx.has_res) else 0)), writes=1 + (1 if ctx.has_res else 0)), lambda: check(L.ftx_bn_train_bwd(
-            ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta) if ctx.remask else 0, p_mean, p_invstd, n, co, ctx.relu, gx, ptr(gres), gparams.data_ptr(), gparams.data_ptr() + 4 * co,
-            bn_ws, bn_ws_bytes, st), "ftx_bn_train_bwd"))
+        _launch_bn_bwd(ptr(gy), ptr(x), ptr(y), ptr(gamma), ptr(beta) if ctx.remask else 0, stats.data_ptr(), stats.data_ptr() + 4 * co, n, co, ctx.relu,
+                       gx, ptr(gres), gparams.data_ptr(), gparams.data_ptr() + 4 * co, bn_ws, bn_ws_bytes, st)
         g_feats = g_kernel = None
-        meta = dict(pairs=km.n_pairs, n_out=n_feats, ca=co, co=ca, kvol=kvol)
         if need_feats:
             g_feats = _empty((n_feats, ca), F32, x)
-            if km.n_pairs == 0 or n_feats == 0:
+            if route == _EMPTY:
                 g_feats.zero_()
-            elif direct:
-                _log_launch(gemm_kind, dict(meta, direct=True), lambda: check(getattr(L, _PAIRS_GEMM_SCATTER[bf16])(
-                    gx, n, ptr(km.pair_out), ptr(km.pair_in), ptr(kernel), 1, ptr(km.koff), km.n_pairs, co, ca, kvol, ptr(g_feats), n_feats, st),
-                    _PAIRS_GEMM_SCATTER[bf16]))
-            elif ostat:
-                _log_launch("spconv_ostat", dict(meta, direct=True), lambda: check(L.ftx_spconv_ostat(
-                    gx, n, ptr(km.nbr), n_feats, ptr(kernel), 1, 1, co, ca, kvol, ptr(g_feats), 0, 0, st), "ftx_spconv_ostat"))
+            elif route == _DIRECT:
+                _launch_direct(gx, n, ptr(dst), ptr(src), ptr(kernel), 1, ptr(km.koff), km.n_pairs, co, ca, kvol, ptr(g_feats), n_feats, st, bf16)
             else:
-                pos_in = km.pos if transposed else km.pos_t
-                _log_launch(gemm_kind, meta, lambda: check(getattr(L, gemm)(
-                    gx, n, ptr(out_side), ptr(kernel), 1, ptr(km.koff), km.n_pairs, co, ca, kvol, tmp, st), gemm))
-                _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce(tmp, ptr(pos_in), n_feats, ca, kvol, ptr(g_feats), st), "ftx_spconv_reduce"))
+                _launch_pairs(gx, n, ptr(dst), ptr(kernel), 1, ptr(src_pos), ptr(km.koff), km.n_pairs, co, ca, kvol, tmp, ptr(g_feats), n_feats, st, bf16)
         if need_kernel:
             g_kernel = _empty((kvol, ca, co), F32, x)
-            _log_launch(wgrad_kind, dict(pairs=km.n_pairs, n_out=n, ca=ca, co=co, kvol=kvol), lambda: check(getattr(L, wgrad)(
-                ptr(feats), n_feats, ptr(in_side), gx, n, ptr(out_side), ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(g_kernel), wg_ws, wg_bytes, st),
-                wgrad))
+            _launch_wgrad(ptr(feats), n_feats, ptr(src), gx, n, ptr(dst), ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(g_kernel), wg_ws, wg_bytes, st, bf16)
         return g_feats, g_kernel, None, None, gres, gparams[0], gparams[1], None, None, None, None, None, None, None
 
 
@@ -1156,12 +1173,16 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------- ViT self-attention
+# (forward entry, its launch-log kind, backward entry, its kind) per precision
+_ATTENTION = {False: ("ftx_attn_fwd_tiled", "attn_fwd", "ftx_attn_bwd_tiled", "attn_bwd"),
+              True: ("ftx_attn_fwd_bf16", "attn_fwd_bf16", "ftx_attn_bwd_bf16", "attn_bwd_bf16")}
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, scale, tiling=(0, 0), bf16=False):
-        if bf16:
-            return _attention_bf16_fwd(ctx, qkv, scale, tiling)
         L = _lib.load()
+        fn, kind = _ATTENTION[bf16][:2]
         qkv = req(qkv.contiguous(), F32, "attention qkv", 5)
         b, t, three, h, d = qkv.shape
         if three != 3 or d != 64:
@@ -1169,44 +1190,25 @@ class _Attention(torch.autograd.Function):
         out = _empty((b, t, h * d), F32, qkv)
         lse = _empty((b, h, t), F32, qkv)
         qw, split = int(tiling[0]), int(tiling[1])
-        _log_launch("attn_fwd", dict(b=b, t=t, h=h, d=d, products=2), lambda: check(L.ftx_attn_fwd_tiled(
-            ptr(qkv), b, t, h, d, float(scale), ptr(out), ptr(lse), qw, split, stream()), "ftx_attn_fwd"))
+        _log_launch(kind, dict(b=b, t=t, h=h, d=d, products=2), lambda: check(getattr(L, fn)(
+            ptr(qkv), b, t, h, d, float(scale), ptr(out), ptr(lse), qw, split, stream()), fn))
         ctx.save_for_backward(qkv, out, lse)
-        ctx.scale, ctx.tiling, ctx.bf16 = float(scale), (qw, split), False
+        ctx.scale, ctx.tiling, ctx.bf16 = float(scale), (qw, split), bf16
         return out
 
     @staticmethod
     def backward(ctx, go):
         L = _lib.load()
+        fn, kind = _ATTENTION[ctx.bf16][2:]
         qkv, out, lse = ctx.saved_tensors
         b, t, _, h, d = qkv.shape
         go = req(go.contiguous(), F32, "attention grad", 3)
         gqkv = torch.empty_like(qkv)
         ws_bytes = int(L.ftx_attn_bwd_workspace_bytes(b, t, h))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=qkv.device)
-        if ctx.bf16:
-            _log_launch("attn_bwd_bf16", dict(b=b, t=t, h=h, d=d, products=7), lambda: check(L.ftx_attn_bwd_bf16(
-                ptr(qkv), ptr(out), ptr(go), ptr(lse), b, t, h, d, ctx.scale, ptr(gqkv), ptr(ws), ws_bytes, ctx.tiling[0], ctx.tiling[1], stream()), "ftx_attn_bwd_bf16"))
-            return gqkv, None, None, None
-        _log_launch("attn_bwd", dict(b=b, t=t, h=h, d=d, products=7), lambda: check(L.ftx_attn_bwd_tiled(
-            ptr(qkv), ptr(out), ptr(go), ptr(lse), b, t, h, d, ctx.scale, ptr(gqkv), ptr(ws), ws_bytes, ctx.tiling[0], ctx.tiling[1], stream()), "ftx_attn_bwd"))
+        _log_launch(kind, dict(b=b, t=t, h=h, d=d, products=7), lambda: check(getattr(L, fn)(
+            ptr(qkv), ptr(out), ptr(go), ptr(lse), b, t, h, d, ctx.scale, ptr(gqkv), ptr(ws), ws_bytes, ctx.tiling[0], ctx.tiling[1], stream()), fn))
         return gqkv, None, None, None
-
-
-def _attention_bf16_fwd(ctx, qkv, scale, tiling):
-    L = _lib.load()
-    qkv = req(qkv.contiguous(), F32, "attention qkv", 5)
-    b, t, three, h, d = qkv.shape
-    if three != 3 or d != 64:
-        raise ValueError(f"attention: qkv must be (B, T, 3, heads, 64), got {tuple(qkv.shape)}")
-    out = _empty((b, t, h * d), F32, qkv)
-    lse = _empty((b, h, t), F32, qkv)
-    qw, split = int(tiling[0]), int(tiling[1])
-    _log_launch("attn_fwd_bf16", dict(b=b, t=t, h=h, d=d, products=2), lambda: check(L.ftx_attn_fwd_bf16(
-        ptr(qkv), b, t, h, d, float(scale), ptr(out), ptr(lse), qw, split, stream()), "ftx_attn_fwd_bf16"))
-    ctx.save_for_backward(qkv, out, lse)
-    ctx.scale, ctx.tiling, ctx.bf16 = float(scale), (qw, split), True
-    return out
 
 
 def attention(qkv, scale, tiling=(0, 0), bf16=False):
@@ -1257,7 +1259,6 @@ def _dense_wgrad(g, x):
 
 def dense_bf16_tile(form, m, n, k):
     """(tile rows, tile columns, row splits) that ftx_dense_gemm_bf16 (form 0) or ftx_dense_wgrad_bf16 (form 1) picks: host only."""
-    import ctypes
     tm, tn, sp = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     check(_lib.load().ftx_dense_bf16_tile(form, m, n, k, ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(sp)), "ftx_dense_bf16_tile")
     return tm.value, tn.value, sp.value
@@ -1496,7 +1497,6 @@ JITTER_OPS = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}
 
 def _jitter_args(image: torch.Tensor, ops):
     """Host-side checks of a uint8 (H, W, 3) frame (a crop view with a row pitch is fine) and the packed op codes / factors."""
-    import ctypes
     if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 3:
         raise ValueError("color jitter: expected a (H, W, 3) uint8 CUDA tensor")
     h, w, c = image.shape
@@ -1537,7 +1537,6 @@ def color_jitter_u8(image: torch.Tensor, ops) -> torch.Tensor:
 def color_jitter_to_chw(image: torch.Tensor, ops=None, flip=False, normalizer=None) -> torch.Tensor:
     """The same ops, fused with the conversion to the model's input: float32(u8) / 255 (correctly rounded, numpy's division), the
     optional left-right flip, (x - mean) / std with normalizer = (mean, std), HWC -> CHW.  Returns a (3, H, W) float32."""
-    import ctypes
     L = _lib.load()
     h, w, c, pitch, codes, factors, n, keep, needs_ws = _jitter_args(image, ops)
     out = torch.empty((c, h, w), dtype=torch.float32, device=image.device)
@@ -1560,7 +1559,6 @@ _RESIZE_TABLES = {}
 def resize_table(in_size: int, out_size: int, device):
     """Pillow's coefficient table of one axis (include/ftx.h) on `device`: (bounds (out, 2) int32, kk (out, ksize) int32, ksize).
     Computed on the host by ftx_resize_coeffs_host and uploaded once per (in, out, device); later calls return the same tensors."""
-    import ctypes
     device = torch.device(device)
     key = (int(in_size), int(out_size), device.index if device.index is not None else torch.cuda.current_device())
     hit = _RESIZE_TABLES.get(key)
