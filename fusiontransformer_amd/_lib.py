@@ -107,6 +107,10 @@ SIGNATURES = {
     "ftx_dense_wgrad_bf16_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ftx_dense_wgrad_bf16": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
     "ftx_dense_bf16_tile": (C.c_int, [_i32, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "ftx_dense_gemm_split": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ftx_dense_wgrad_split_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ftx_dense_wgrad_split": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ftx_dense_split_tile": (C.c_int, [_i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "ftx_fusion_loss_workspace_bytes": (_sz, []),
     "ftx_fusion_loss": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ftx_fusion_loss_mix": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

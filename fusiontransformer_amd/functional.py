@@ -1222,6 +1222,9 @@ def attention(qkv, scale, tiling=(0, 0), bf16=False):
 # ---------------------------------------------------------------- bf16-operand ViT Linears
 # Epilogues of ftx_dense_gemm_bf16 (include/ftx.h FTX_EPI_*)
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU = 0, 1, 2, 3
+# mode of the kernels -> the C entries' suffix.  "bf16": operands rounded to bf16.  "split": every operand split into three bf16 pieces,
+# six piece products summed in fp32 (fp32-class accuracy; the contract is stated in include/ftx.h).
+_DENSE_MODES = {"bf16": "bf16", "split": "split"}
 
 
 def vit_linear_supported(x, weight):
@@ -1232,28 +1235,31 @@ def vit_linear_supported(x, weight):
             and x.numel() // k <= (1 << 30))
 
 
-def _dense_gemm(a, w, w_kn, epi, bias=None, pre_in=None, with_pre=False):
-    """ftx_dense_gemm_bf16: a (m, kr) times W ((n, kr) for w_kn = 0, (kr, n) for w_kn = 1) -> (out, pre_out or None), fp32."""
+def _dense_gemm(a, w, w_kn, epi, bias=None, pre_in=None, with_pre=False, mode="bf16"):
+    """ftx_dense_gemm_bf16 (mode "bf16") or ftx_dense_gemm_split (mode "split"): a (m, kr) times W ((n, kr) for w_kn = 0, (kr, n) for
+    w_kn = 1) -> (out, pre_out or None), fp32."""
     L = _lib.load()
+    entry = _DENSE_MODES[mode]
     m, kr = a.shape
     n = w.shape[1] if w_kn else w.shape[0]
     out = _empty((m, n), F32, a)
     pre = _empty((m, n), F32, a) if with_pre else None
-    _log_launch("vit_gemm_bf16", dict(m=m, n=n, k=kr, w_kn=w_kn, epi=epi), lambda: check(L.ftx_dense_gemm_bf16(
-        ptr(a), ptr(w), w_kn, ptr(bias), ptr(pre_in), m, n, kr, epi, ptr(out), ptr(pre), stream()), "ftx_dense_gemm_bf16"))
+    _log_launch("vit_gemm_" + mode, dict(m=m, n=n, k=kr, w_kn=w_kn, epi=epi), lambda: check(getattr(L, "ftx_dense_gemm_" + entry)(
+        ptr(a), ptr(w), w_kn, ptr(bias), ptr(pre_in), m, n, kr, epi, ptr(out), ptr(pre), stream()), "ftx_dense_gemm_" + entry))
     return out, pre
 
 
-def _dense_wgrad(g, x):
-    """ftx_dense_wgrad_bf16: dW (n, k) = g (m, n)^T x (m, k)."""
+def _dense_wgrad(g, x, mode="bf16"):
+    """ftx_dense_wgrad_bf16 / ftx_dense_wgrad_split: dW (n, k) = g (m, n)^T x (m, k)."""
     L = _lib.load()
+    entry = _DENSE_MODES[mode]
     m, n = g.shape
     k = x.shape[1]
     dw = _empty((n, k), F32, g)
-    ws_bytes = _ws_bytes("ftx_dense_wgrad_bf16_workspace_bytes", m, n, k)
+    ws_bytes = _ws_bytes(f"ftx_dense_wgrad_{entry}_workspace_bytes", m, n, k)
     ws = _scratch(ws_bytes, g)
-    _log_launch("vit_wgrad_bf16", dict(m=m, n=n, k=k), lambda: check(L.ftx_dense_wgrad_bf16(
-        ptr(g), ptr(x), m, n, k, ptr(dw), ptr(ws), ws_bytes, stream()), "ftx_dense_wgrad_bf16"))
+    _log_launch("vit_wgrad_" + mode, dict(m=m, n=n, k=k), lambda: check(getattr(L, "ftx_dense_wgrad_" + entry)(
+        ptr(g), ptr(x), m, n, k, ptr(dw), ptr(ws), ws_bytes, stream()), "ftx_dense_wgrad_" + entry))
     return dw
 
 
@@ -1264,76 +1270,99 @@ def dense_bf16_tile(form, m, n, k):
     return tm.value, tn.value, sp.value
 
 
+def dense_split_tile(form, m, n, k):
+    """(tile rows, tile columns, row splits) that ftx_dense_gemm_split (form 0) or ftx_dense_wgrad_split (form 1) picks: host only."""
+    tm, tn, sp = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    check(_lib.load().ftx_dense_split_tile(form, m, n, k, ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(sp)), "ftx_dense_split_tile")
+    return tm.value, tn.value, sp.value
+
+
 class _VitLinear(torch.autograd.Function):
     """y = x W^T (+ b) on ftx_dense_gemm_bf16; dX on the same kernel with W in the reduction-strided orientation, dW on
-    ftx_dense_wgrad_bf16, the bias gradient on ftx_colsum.  Operands rounded to bf16 as they are staged, everything else fp32."""
+    ftx_dense_wgrad_bf16, the bias gradient on ftx_colsum.  Operands rounded to bf16 as they are staged, everything else fp32.
+    mode "split": the same node on ftx_dense_gemm_split / ftx_dense_wgrad_split (three-piece operands, fp32-class results)."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, mode="bf16"):
         x2 = req(x.reshape(-1, x.shape[-1]).contiguous(), F32, "vit_linear x", 2)
         w = req(w.contiguous(), F32, "vit_linear weight", 2)
-        y, _ = _dense_gemm(x2, w, 0, EPI_BIAS if b is not None else EPI_NONE, bias=b)
+        y, _ = _dense_gemm(x2, w, 0, EPI_BIAS if b is not None else EPI_NONE, bias=b, mode=mode)
         ctx.save_for_backward(x2, w)
-        ctx.in_shape, ctx.has_bias = x.shape, b is not None
+        ctx.in_shape, ctx.has_bias, ctx.mode = x.shape, b is not None, mode
         return y.view(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors
+        mode = ctx.mode
         dy2 = req(dy.reshape(-1, dy.shape[-1]).contiguous(), F32, "vit_linear grad", 2)
-        dx = _dense_gemm(dy2, w, 1, EPI_NONE)[0].view(ctx.in_shape) if ctx.needs_input_grad[0] else None
-        dw = _dense_wgrad(dy2, x2) if ctx.needs_input_grad[1] else None
+        dx = _dense_gemm(dy2, w, 1, EPI_NONE, mode=mode)[0].view(ctx.in_shape) if ctx.needs_input_grad[0] else None
+        dw = _dense_wgrad(dy2, x2, mode) if ctx.needs_input_grad[1] else None
         db = colsum(dy2) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        return dx, dw, db
+        return dx, dw, db, None
 
 
 class _VitMlp(torch.autograd.Function):
     """fc2(gelu(fc1(x))) as one node: fc1 with the BIAS_GELU epilogue (writes the pre-activation and its GELU), fc2 with BIAS or NONE;
-    backward: fc2's dX with the DGELU epilogue IS fc1's output gradient, so no GELU-backward pass runs."""
+    backward: fc2's dX with the DGELU epilogue IS fc1's output gradient, so no GELU-backward pass runs.  mode as _VitLinear."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2):
+    def forward(ctx, x, w1, b1, w2, b2, mode="bf16"):
         x2 = req(x.reshape(-1, x.shape[-1]).contiguous(), F32, "vit_mlp x", 2)
         w1 = req(w1.contiguous(), F32, "vit_mlp fc1 weight", 2)
         w2 = req(w2.contiguous(), F32, "vit_mlp fc2 weight", 2)
-        h, pre = _dense_gemm(x2, w1, 0, EPI_BIAS_GELU, bias=b1, with_pre=True)
-        y, _ = _dense_gemm(h, w2, 0, EPI_BIAS if b2 is not None else EPI_NONE, bias=b2)
+        h, pre = _dense_gemm(x2, w1, 0, EPI_BIAS_GELU, bias=b1, with_pre=True, mode=mode)
+        y, _ = _dense_gemm(h, w2, 0, EPI_BIAS if b2 is not None else EPI_NONE, bias=b2, mode=mode)
         ctx.save_for_backward(x2, w1, pre, h, w2)
-        ctx.in_shape, ctx.has_b2 = x.shape, b2 is not None
+        ctx.in_shape, ctx.has_b2, ctx.mode = x.shape, b2 is not None, mode
         return y.view(*x.shape[:-1], w2.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w1, pre, h, w2 = ctx.saved_tensors
+        mode = ctx.mode
         dy2 = req(dy.reshape(-1, dy.shape[-1]).contiguous(), F32, "vit_mlp grad", 2)
-        dpre, _ = _dense_gemm(dy2, w2, 1, EPI_DGELU, pre_in=pre)
-        dw2 = _dense_wgrad(dy2, h) if ctx.needs_input_grad[3] else None
+        dpre, _ = _dense_gemm(dy2, w2, 1, EPI_DGELU, pre_in=pre, mode=mode)
+        dw2 = _dense_wgrad(dy2, h, mode) if ctx.needs_input_grad[3] else None
         db2 = colsum(dy2) if ctx.has_b2 and ctx.needs_input_grad[4] else None
-        dx = _dense_gemm(dpre, w1, 1, EPI_NONE)[0].view(ctx.in_shape) if ctx.needs_input_grad[0] else None
-        dw1 = _dense_wgrad(dpre, x2) if ctx.needs_input_grad[1] else None
+        dx = _dense_gemm(dpre, w1, 1, EPI_NONE, mode=mode)[0].view(ctx.in_shape) if ctx.needs_input_grad[0] else None
+        dw1 = _dense_wgrad(dpre, x2, mode) if ctx.needs_input_grad[1] else None
         db1 = colsum(dpre) if ctx.needs_input_grad[2] else None
-        return dx, dw1, db1, dw2, db2
+        return dx, dw1, db1, dw2, db2, None
 
 
-def vit_linear(x, w, b=None, bf16=True):
+def vit_linear(x, w, b=None, bf16=True, mode="bf16"):
     """x W^T (+ b) for a ViT Linear (x (..., K), w (N, K) as nn.Linear).  bf16=True on a shape the kernels take
     (vit_linear_supported): the ftx_dense_* kernels -- x, w and (backward) dy rounded to bf16 as MFMA operands, fp32 accumulation,
     fp32 output, bias and gradients (include/ftx.h).  Any other call runs the library path the model ran before
-    (models/transformers._LinearFn, with bf16 the library bf16 GEMMs)."""
+    (models/transformers._LinearFn, with bf16 the library bf16 GEMMs).
+    mode="split": the three-piece split kernels (ftx_dense_gemm_split / ftx_dense_wgrad_split: fp32-class results on the bf16 MFMA);
+    `bf16` is then ignored, and a shape the kernels do not take runs the FP32 library path (_LinearFn(..., False))."""
+    if mode not in _DENSE_MODES:
+        raise ValueError(f"vit_linear mode must be 'bf16' or 'split', got {mode!r}")
+    if mode == "split":
+        if vit_linear_supported(x, w):
+            return _VitLinear.apply(x, w, b, "split")
+        from .models.transformers import _LinearFn
+        return _LinearFn.apply(x, w, b, False)
     if bf16 and vit_linear_supported(x, w):
         return _VitLinear.apply(x, w, b)
     from .models.transformers import _LinearFn
     return _LinearFn.apply(x, w, b, bool(bf16))
 
 
-def vit_mlp(x, w1, b1, w2, b2=None):
+def vit_mlp(x, w1, b1, w2, b2=None, mode="bf16"):
     """fc2(gelu(fc1(x))) with exact GELU, bf16 operands and fp32 everything else, as one autograd node (see _VitMlp).  b2 None: fc2's
-    bias is left to the caller (Block.chain).  Shapes the kernels do not take run the library bf16 path with nn.GELU()."""
+    bias is left to the caller (Block.chain).  Shapes the kernels do not take run the library bf16 path with nn.GELU().
+    mode="split": the node on the three-piece split kernels; shapes they do not take run the fp32 library path."""
+    if mode not in _DENSE_MODES:
+        raise ValueError(f"vit_mlp mode must be 'bf16' or 'split', got {mode!r}")
     if (b1 is not None and vit_linear_supported(x, w1) and w2.is_cuda and w2.dtype == F32 and w2.shape[1] == w1.shape[0]
             and w2.shape[0] % 64 == 0):
-        return _VitMlp.apply(x, w1, b1, w2, b2)
+        return _VitMlp.apply(x, w1, b1, w2, b2, mode) if mode == "split" else _VitMlp.apply(x, w1, b1, w2, b2)
     from .models.transformers import _LinearFn
-    return _LinearFn.apply(torch.nn.functional.gelu(_LinearFn.apply(x, w1, b1, True)), w2, b2, True)
+    lib_bf16 = mode != "split"
+    return _LinearFn.apply(torch.nn.functional.gelu(_LinearFn.apply(x, w1, b1, lib_bf16)), w2, b2, lib_bf16)
 
 
 # ---------------------------------------------------------------- fused sample_down

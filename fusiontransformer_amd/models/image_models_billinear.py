@@ -123,7 +123,8 @@ class Net2DBillinear(nn.Module):
         if kw.get("vit_bf16", False):
             self.backbone.set_bf16(True)   # BASELINE configs[4] "bf16 forward"; default is fp32 like the reference
         # how those bf16 GEMMs run: "library" (default) or "ftx" (libftx's bf16 kernels, fp32 results, fused bias / GELU).  Inert
-        # while the GEMMs are fp32.
+        # while the GEMMs are fp32.  "ftx_split": the fp32 model's own kernels (three bf16 pieces per fp32 operand, six products
+        # summed in fp32: fp32-class results with the fused bias / GELU epilogues); routes with vit_bf16 off or on.
         self.backbone.set_linear_impl(kw.get("vit_linear_impl", "library"))
         # Training on the GPU runs the trunk as HIP graphs, one per tapped segment (transformers.py): ~500 kernel launches
         # per step become 4 graph launches, which takes 7 ms off the host side of a step (batch 4: the host issue time

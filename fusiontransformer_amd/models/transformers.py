@@ -102,7 +102,11 @@ def _linear(x, lin, with_bias=True):
     if lin.bias is None or not x.is_cuda:
         return F.linear(x, lin.weight, lin.bias if with_bias else None)
     bf16 = getattr(lin, "ftx_bf16", False)
-    if bf16 and getattr(lin, "ftx_linear_impl", "library") == "ftx":
+    impl = getattr(lin, "ftx_linear_impl", "library")
+    if impl == "ftx_split":   # the more specific request: routes whether or not set_bf16 is on
+        from .. import functional as spf
+        return spf.vit_linear(x, lin.weight, lin.bias if with_bias else None, mode="split")   # fp32 library path for shapes the kernels do not take
+    if bf16 and impl == "ftx":
         from .. import functional as spf
         return spf.vit_linear(x, lin.weight, lin.bias if with_bias else None)   # library path for shapes the kernels do not take
     return _LinearFn.apply(x, lin.weight, lin.bias if with_bias else None, bf16)
@@ -118,15 +122,18 @@ class Mlp(nn.Module):
 
     def forward(self, x, with_fc2_bias=True):
         if self._fused_ftx(x):
-            # vit_linear_impl "ftx": fc1 + GELU + fc2 as one node on the bf16 kernels (GELU in fc1's epilogue, its derivative in fc2's dX)
+            # vit_linear_impl "ftx" / "ftx_split": fc1 + GELU + fc2 as one node on the bf16 / three-piece split kernels (GELU in fc1's
+            # epilogue, its derivative in fc2's dX)
             from .. import functional as spf
-            return spf.vit_mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias if with_fc2_bias else None)
+            mode = "split" if getattr(self.fc1, "ftx_linear_impl", "library") == "ftx_split" else "bf16"
+            return spf.vit_mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias if with_fc2_bias else None, mode=mode)
         return self.drop(_linear(self.drop(self.act(_linear(x, self.fc1))), self.fc2, with_fc2_bias))
 
     def _fused_ftx(self, x):
         fc1, fc2 = self.fc1, self.fc2
-        return (x.is_cuda and getattr(fc1, "ftx_bf16", False) and getattr(fc2, "ftx_bf16", False)
-                and getattr(fc1, "ftx_linear_impl", "library") == "ftx" and getattr(fc2, "ftx_linear_impl", "library") == "ftx"
+        impls = (getattr(fc1, "ftx_linear_impl", "library"), getattr(fc2, "ftx_linear_impl", "library"))
+        bf16 = getattr(fc1, "ftx_bf16", False) and getattr(fc2, "ftx_bf16", False)
+        return (x.is_cuda and (impls == ("ftx_split", "ftx_split") or (bool(bf16) and impls == ("ftx", "ftx")))
                 and type(self.act) is nn.GELU and self.act.approximate == "none" and self.drop.p == 0.0
                 and fc1.bias is not None and fc2.bias is not None)
 
@@ -294,9 +301,12 @@ class Image2DTransformer(nn.Module):
     def set_linear_impl(self, impl: str):
         """How the bf16 qkv / proj / fc1 / fc2 GEMMs run: "library" (torch's bf16 GEMMs, bf16 results widened to fp32, separate cast,
         bias and GELU kernels) or "ftx" (libftx's ftx_dense_* kernels: bf16 operands, fp32 accumulation and fp32 results, bias and GELU
-        fused into the GEMM epilogues).  Precision is still switched by set_bf16: with set_bf16(False) this setting changes nothing."""
-        if impl not in ("library", "ftx"):
-            raise ValueError(f"vit_linear_impl must be 'library' or 'ftx', got {impl!r}")
+        fused into the GEMM epilogues).  For these two, precision is still switched by set_bf16: with set_bf16(False) they change nothing.
+        "ftx_split" is the fp32 model's own path: libftx's ftx_dense_*_split kernels split every fp32 operand into three bf16 pieces and
+        sum six piece products in fp32 on the bf16 MFMA (fp32-class results, same fused epilogues; contract in include/ftx.h).  It is the
+        more specific request, so it routes whether or not set_bf16 is on."""
+        if impl not in ("library", "ftx", "ftx_split"):
+            raise ValueError(f"vit_linear_impl must be 'library', 'ftx' or 'ftx_split', got {impl!r}")
         for blk in self.blocks:
             for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
                 lin.ftx_linear_impl = impl

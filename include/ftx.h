@@ -367,6 +367,31 @@ int ftx_dense_wgrad_bf16(const float *dY, const float *X, int64_t m, int32_t n, 
  * dW (n, k) over m rows) picks.  Launches nothing. */
 int ftx_dense_bf16_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host);
 
+/* ---- fp32-accurate ViT Linears on the bf16 MFMA: three-piece operand split (csrc/ftx_dense_split.hip) ----
+ * The same GEMM, epilogues, weight gradient, argument rules, error texts and m == 0 behaviour as the bf16-operand entries above, for
+ * the fp32 model: no operand bit is discarded below the stated range, and the result is fp32-class (measured: DESIGN section 5).
+ * Precision contract:
+ *   split     every fp32 operand element x (A, W; dY, X) is split as it is staged, round-to-nearest-even, both subtractions in fp32
+ *             (they are exact):  h = bf16(x),  m = bf16(x - h),  l = bf16((x - h) - m).
+ *             For finite x with |x| < 2^127 (above it h rounds to inf) x == h + m + l exactly (24 significand bits into 3 x 8), except
+ *             that pieces below 2^-126 may be lost.  If h is not finite, m = l = 0: inf and NaN propagate as through an fp32 GEMM,
+ *             i.e. to the same output elements, NaN as NaN; an inf may arrive as NaN instead (inf times a zero piece of the
+ *             other operand).
+ *   products  six of the nine piece products are summed, fp32 accumulation on v_mfma_f32_32x32x16_bf16: hh, hm, mh, hl, lh, mm (first
+ *             letter: the piece of A / dY).  Each bf16 x bf16 product is exact in fp32.  The dropped ml, lm, ll are each below
+ *             2.01 * 2^-24 * |a b|.
+ *   order     fixed: two fp32 accumulators per output element.  One takes the hh products, reduction index ascending.  The other
+ *             takes, per 16-wide reduction step, mm, hl, lh, hm, mh in that order (smallest first).  They are added once, in the
+ *             epilogue: sum = hh + corrections.  No atomics; a split weight gradient's partials are added in split order.  Results
+ *             are bit-reproducible and a function of the arguments alone.
+ *   storage   A, W, bias, out, pre_in / pre_out, dW: fp32.  Bias, GELU and the GELU derivative are applied in fp32 to the fp32 sum by
+ *             the bf16 entries' epilogue code.
+ * ftx_dense_split_tile: as ftx_dense_bf16_tile for these entries (form 0: GEMM, 1: weight gradient).  Host only. */
+int ftx_dense_gemm_split(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n, int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream);
+size_t ftx_dense_wgrad_split_workspace_bytes(int64_t m, int32_t n, int32_t k);
+int ftx_dense_wgrad_split(const float *dY, const float *X, int64_t m, int32_t n, int32_t k, float *dW, void *workspace, size_t workspace_bytes, void *stream);
+int ftx_dense_split_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host);
+
 /* ---- fused train-step losses + metric: modules/SemanticTrainer.py:158-194, models/metric.py:37-58 ----
  * losses[0] = loss_2d = CE_w(img_logit) + lambda * KL(softmax(lidar_logit) || softmax(img_logit2))
  * losses[1] = loss_3d = CE_w(lidar_logit) + lambda * KL(softmax(img_logit) || softmax(lidar_logit2))
