@@ -85,3 +85,24 @@ def fusion_cfg(kind: str = "middle") -> CfgNode:
         "TRAIN": {"BATCH_SIZE": 10, "CLASS_WEIGHTS": _CLASS_WEIGHTS, "FusionTransformer": {"lambda_xm": 0.1}},
     })
     return cfg
+
+
+def _single_cfg(model) -> CfgNode:
+    cfg = get_cfg_defaults()
+    cfg.merge_from_dict({
+        "MODEL": dict(DUAL_HEAD=False, NUM_CLASSES=20, **model),
+        "OPTIMIZER": {"TYPE": "Adam", "BASE_LR": 1e-4, "WEIGHT_DECAY": 0.0005},
+        "TRAIN": {"BATCH_SIZE": 10, "CLASS_WEIGHTS": _CLASS_WEIGHTS, "FusionTransformer": {"lambda_xm": 0.0}},
+    })
+    return cfg
+
+
+def lidar_cfg() -> CfgNode:
+    """The LiDAR-only baseline (the reference's configs/semantic_kitti/lidar.yaml): SPVCNN + one linear head."""
+    return _single_cfg(dict(TYPE="LidarSeg", USE_LIDAR=True))
+
+
+def image_cfg() -> CfgNode:
+    """The image-only baseline (the reference's configs/semantic_kitti/imageBilinear.yaml): the ViT trunk tapped after its last
+    block, lifted onto the points, one linear head."""
+    return _single_cfg(dict(TYPE="ImageSegBilinear", USE_IMAGE=True, late_feat_block_number=11))

@@ -258,3 +258,91 @@ extern "C" int ftx_fusion_loss(const float *lidar_logit, const float *img_logit,
   return ftx_fusion_loss_mix(lidar_logit, img_logit, lidar_logit2, img_logit2, label, class_weights, 1.f, lambda_xm, n, c, ignore_index, losses,
                              grad_lidar, grad_img, grad_lidar2, grad_img2, conf3d, conf2d, workspace, workspace_bytes, stream);
 }
+
+// ---- one head: the weighted cross-entropy of a LiDAR-only or image-only model (modules/SemanticTrainer.py:180-186,
+// data/utils/validate.py:122-128) ----
+// The CE part of loss_main_kernel on one logit tensor, with the same grid, the same per-block double sums and the same finalize order,
+// so the loss and the gradient are the bits ftx_fusion_loss_mix gives for that head at lambda = 0.  GRAD = false is the validation
+// loss: the kernel then holds no gradient arithmetic and no gradient store at all.  part[block] = sum w * nll.
+template <int C, bool GRAD>
+__global__ __launch_bounds__(256) void seg_loss_main_kernel(const float *__restrict__ logit, const int64_t *__restrict__ label,
+                                                            const float *__restrict__ cw, const double *__restrict__ wpart, int64_t n,
+                                                            int ignore_index, float *__restrict__ grad, long long *__restrict__ conf,
+                                                            double *__restrict__ part) {
+  constexpr int c = C;
+  __shared__ double sh[4];
+  __shared__ float s_invW;
+  __shared__ unsigned int cf[C * C];     // block-local confusion counts, flushed once (see loss_main_kernel)
+  for (int j = threadIdx.x; j < c * c; j += blockDim.x) cf[j] = 0u;
+  if (GRAD && threadIdx.x == 0) s_invW = (float)(1.0 / loss_wsum_total(wpart));
+  __syncthreads();
+  const float invW = GRAD ? s_invW : 0.f;
+  double a_ce = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    Row<C> lp;
+    load_row<C>(logit + i * c, lp);
+    const int am = log_softmax_row<C>(lp);
+    const int64_t y64 = label[i];
+    const bool yv = y64 >= 0 && y64 < c;
+    const int y = yv ? (int)y64 : -1;
+    const float w = yv ? (cw ? cw[y] : 1.f) : 0.f;
+    if (yv) {
+      a_ce += (double)(-w * pick<C>(lp, y));
+      if (conf && y != ignore_index) atomicAdd(&cf[y * c + am], 1u);
+    }
+    if constexpr (GRAD) {
+      const float wW = w * invW;
+      Row<C> g;
+#pragma unroll
+      for (int j = 0; j < C; ++j) g.v[j] = wW * (expf(lp.v[j]) - ((j == y) ? 1.f : 0.f));
+      store_row<C>(grad + i * c, g);
+    }
+  }
+  const double r = loss_block_sum(a_ce, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = r;
+  __syncthreads();
+  if (conf)
+    for (int j = threadIdx.x; j < c * c; j += blockDim.x)
+      if (cf[j]) atomicAdd((unsigned long long *)&conf[j], (unsigned long long)cf[j]);
+}
+
+// thread b holds block row b (at most LOSS_BLOCKS = 256 of them), added by the fixed shuffle tree of loss_finalize_kernel
+__global__ __launch_bounds__(256) void seg_loss_finalize_kernel(const double *__restrict__ part, int nb, const double *__restrict__ wpart,
+                                                                float *__restrict__ loss) {
+  __shared__ double sh[4];
+  const int b = threadIdx.x;
+  const double s = loss_block_sum(b < nb ? part[b] : 0.0, sh);
+  if (threadIdx.x != 0) return;
+  loss[0] = (float)(s / loss_wsum_total(wpart));
+}
+
+extern "C" size_t ftx_seg_loss_workspace_bytes(void) { return sizeof(double) * (LOSS_BLOCKS + WSUM_BLOCKS) + 256; }
+
+extern "C" int ftx_seg_loss(const float *logit, const int64_t *label, const float *class_weights, int64_t n, int32_t c, int32_t ignore_index,
+                            float *loss, float *grad, int64_t *conf, void *workspace, size_t workspace_bytes, void *stream) {
+  FTX_REQUIRE(n >= 1, "ftx_seg_loss: needs at least one point");
+  FTX_REQUIRE(c >= 4 && c % 4 == 0 && c <= LC_MAX, "ftx_seg_loss: classes must be a multiple of 4 and <= %d (got %d)", LC_MAX, c);
+  FTX_REQUIRE(logit && label && loss && workspace, "ftx_seg_loss: null pointer");
+  if (workspace_bytes < ftx_seg_loss_workspace_bytes()) {
+    set_error("ftx_seg_loss: workspace too small");
+    return FTX_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = (double *)workspace;
+  double *wpart = part + LOSS_BLOCKS;
+  loss_wsum_kernel<<<WSUM_BLOCKS, 256, 0, st>>>(label, class_weights, n, c, wpart);
+  const int nb = (int)(ceil_div(n, 256) < LOSS_BLOCKS ? ceil_div(n, 256) : LOSS_BLOCKS);
+#define SEG_CASE(C_)                                                                                                                      \
+  case C_:                                                                                                                                \
+    if (grad)                                                                                                                             \
+      seg_loss_main_kernel<C_, true><<<nb, 256, 0, st>>>(logit, label, class_weights, wpart, n, ignore_index, grad, (long long *)conf, part);  \
+    else                                                                                                                                  \
+      seg_loss_main_kernel<C_, false><<<nb, 256, 0, st>>>(logit, label, class_weights, wpart, n, ignore_index, nullptr, (long long *)conf, part); \
+    break
+  switch (c) {
+    SEG_CASE(4); SEG_CASE(8); SEG_CASE(12); SEG_CASE(16); SEG_CASE(20); SEG_CASE(24); SEG_CASE(28); SEG_CASE(32);
+  }
+#undef SEG_CASE
+  seg_loss_finalize_kernel<<<1, 256, 0, st>>>(part, nb, wpart, loss);
+  return check_launch("ftx_seg_loss");
+}

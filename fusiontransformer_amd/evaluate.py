@@ -68,11 +68,14 @@ def pack_inverse_maps(inverse_maps, points_per_frame, device):
     return torch.from_numpy(packed).to(device, non_blocking=True)
 
 
-def validate_batch(preds, data_batch, class_labels, evaluator_3d=None, evaluator_2d=None, evaluator_ensemble=None, want_preds=False):
+def validate_batch(preds, data_batch, class_labels, evaluator_3d=None, evaluator_2d=None, evaluator_ensemble=None, want_preds=False,
+                   seg_label=None, class_weights=None):
     """The per-batch body of validate.py:62-120: `data_batch` carries `orig_seg_label` (list[B] of (M_b,) learning
     ids), `inverse_map` (list[B] of (M_b,)) and `sparse_orig_points_idx` (list[B] of bool masks, all True) as the
     reference's collate (data/collate.py) produces them.  Returns the per-original-point predictions (original
-    label ids) when `want_preds`."""
+    label ids) when `want_preds`.  `seg_label` (one learning id per model point), when given, adds the per-batch validation
+    losses of validate.py:122-128 for every head present: `seg_loss_3d` / `seg_loss_2d`, device scalars of the weighted
+    cross-entropy under `class_weights` (forward-only kernel, nothing is read back)."""
     l3, l2 = preds.get("lidar_seg_logit"), preds.get("img_seg_logit")
     ref = l3 if l3 is not None else l2
     if "inverse_map_packed" in data_batch:
@@ -92,4 +95,11 @@ def validate_batch(preds, data_batch, class_labels, evaluator_3d=None, evaluator
                                             conf3d=None if evaluator_3d is None else evaluator_3d.mat,
                                             conf2d=None if evaluator_2d is None else evaluator_2d.mat,
                                             conf_ens=None if evaluator_ensemble is None else evaluator_ensemble.mat, want_preds=want_preds)
-    return {"pred_3d": p3, "pred_2d": p2, "pred_ensemble": pe, "bad_index_flag": bad}
+    out = {"pred_3d": p3, "pred_2d": p2, "pred_ensemble": pe, "bad_index_flag": bad}
+    if seg_label is not None:
+        with torch.no_grad():
+            if l3 is not None:
+                out["seg_loss_3d"] = spf.seg_loss(l3, seg_label, class_weights)
+            if l2 is not None:
+                out["seg_loss_2d"] = spf.seg_loss(l2, seg_label, class_weights)
+    return out

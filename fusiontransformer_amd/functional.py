@@ -1483,6 +1483,61 @@ def fusion_loss(preds, seg_label, class_weights, lambda_xm, dual_head, conf3d=No
     return out[0], out[1]
 
 
+def _seg_loss_call(logit, label, class_weights, conf, ignore_index, want_grad):
+    """Operand checks, then ftx_seg_loss.  Returns (0-dim loss, (n,c) gradient or None)."""
+    # every operand is checked before anything is launched: the kernel reads C class weights and n rows, and adds 64-bit counts
+    # into C x C cells of the matrix
+    logit = req(logit.contiguous(), F32, "seg_loss logit", 2)
+    n, c = logit.shape
+    if not isinstance(label, torch.Tensor) or label.dim() != 1 or label.shape[0] != n:
+        raise ValueError("seg_loss: seg_label must have %d entries, got shape %s" % (n, tuple(getattr(label, "shape", ()))))
+    label = req(label.contiguous(), I64, "seg_loss seg_label", 1)
+    if class_weights is not None:
+        req(class_weights, F32, "seg_loss class_weights", 1)
+        if class_weights.shape[0] != c:
+            raise ValueError("seg_loss: class_weights must have %d entries, got %d" % (c, class_weights.shape[0]))
+    if conf is not None:
+        req(conf, I64, "seg_loss conf", 2)
+        if tuple(conf.shape) != (c, c):
+            raise ValueError("seg_loss: conf must be (%d, %d), got %s" % (c, c, tuple(conf.shape)))
+    for t in (label, class_weights, conf):
+        if t is not None and t.device != logit.device:
+            raise ValueError("seg_loss: every operand must be on %s" % logit.device)
+    L = _lib.load()
+    loss = _empty((), F32, logit)
+    grad = torch.empty_like(logit) if want_grad else None
+    ws_bytes = int(L.ftx_seg_loss_workspace_bytes())
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=logit.device)
+    check(L.ftx_seg_loss(ptr(logit), ptr(label), ptr(class_weights), n, c, int(ignore_index), ptr(loss), ptr(grad), ptr(conf), ptr(ws), ws_bytes,
+                         stream()), "ftx_seg_loss")
+    return loss, grad
+
+
+class _SegLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, label, class_weights, conf, ignore_index):
+        loss, grad = _seg_loss_call(logit, label, class_weights, conf, ignore_index, True)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None, None
+
+
+def seg_loss(logit, seg_label, class_weights=None, conf=None, ignore_index=0):
+    """Weighted-mean cross-entropy of ONE head, F.cross_entropy(logit, seg_label, weight=class_weights), as a 0-dim tensor: the loss
+    of the LiDAR-only and image-only models (SemanticTrainer.py:180-186) and the per-batch validation loss (validate.py:122-128).
+    conf (C,C) int64, when given, accumulates the SegIoU confusion matrix of models/metric.py:37-58.  Under torch.no_grad(), or for
+    a logit that requires no gradient, the forward-only kernel runs and no (n, C) gradient buffer is allocated."""
+    if isinstance(seg_label, torch.Tensor) and seg_label.dtype != I64 and not seg_label.dtype.is_floating_point:
+        seg_label = seg_label.long()
+    if torch.is_grad_enabled() and isinstance(logit, torch.Tensor) and logit.requires_grad:
+        return _SegLoss.apply(logit, seg_label, class_weights, conf, ignore_index)
+    return _seg_loss_call(logit, seg_label, class_weights, conf, ignore_index, False)[0]
+
+
 def eval_scatter_back(logits3d, logits2d, inverse, gt, class_labels, conf3d=None, conf2d=None, conf_ens=None, want_preds=True):
     """Predictions of the model points mapped to the original points + confusion-matrix update in one kernel
     (reference data/utils/validate.py:62-120, data/utils/evaluate.py:12-26; see include/ftx.h).

@@ -89,6 +89,8 @@ def prepare_batch(model, data_dict, ready=None, wait=True):
     batch's tensors are valid (default: everything queued on the current stream so far); `wait=False`: issue the build up to its first
     host read and return without blocking (SPVCNN.prepare).  Returns data_dict."""
     lb = getattr(model, "lidar_backbone", None)
+    if lb is None:
+        lb = getattr(model, "backbone", None)      # LidarSeg keeps its SPVCNN in `backbone` (models/lidar_model.py)
     lidar = data_dict.get("lidar") if isinstance(data_dict, dict) else None
     if lb is not None and lidar is not None and hasattr(lb, "prepare"):
         lb.prepare(lidar, ready=ready, wait=wait)

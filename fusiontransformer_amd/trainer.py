@@ -1,5 +1,8 @@
-"""Train step of the fusion path: the counterpart of SemanticTrainer.train_step
-(FusionTransformer/modules/SemanticTrainer.py:141-209).
+"""Train step: the counterpart of SemanticTrainer.train_step
+(FusionTransformer/modules/SemanticTrainer.py:141-209), for the fusion models and for the LiDAR-only and
+image-only baselines it branches to (SemanticTrainer.py:157-200, SemanticTorchpackTrainer.py:70-106).
+
+Fusion path:
 
 Same loss: weighted CE x2 + lambda_xm * KL x2 in the additive form of
 SemanticTrainer.py:158-178, Adam step.  Differences, all behaviour-preserving:
@@ -7,7 +10,9 @@ SemanticTrainer.py:158-178, Adam step.  Differences, all behaviour-preserving:
     the LiDAR branch detached (middle_fusion.py:102), so the two loss graphs are disjoint and
     the summed gradients are identical;
   * no `.item()` / `.cpu()` host syncs inside the step (the reference has 4+ per step);
-    losses and the IoU confusion matrices stay on the device."""
+    losses and the IoU confusion matrices stay on the device.
+Single-modality paths (cfg.MODEL.USE_LIDAR / USE_IMAGE without USE_FUSION): one weighted CE on the one head the model has
+(`functional.seg_loss`), one backward; lambda_xm and DUAL_HEAD play no part (SemanticTrainer.py:180-186)."""
 from __future__ import annotations
 
 import torch
@@ -63,6 +68,11 @@ class TrainStep:
         if loss_mix not in ("additive", "torchpack"):
             raise ValueError("loss_mix must be 'additive' or 'torchpack'")
         self.cfg, self.model, self.loss_mix = cfg, model, loss_mix
+        # the reference's order (SemanticTrainer.py:157,180,184): fusion, else LiDAR only, else image only
+        m = cfg.MODEL
+        self.mode = "fusion" if m.get("USE_FUSION") else "lidar" if m.get("USE_LIDAR") else "image" if m.get("USE_IMAGE") else None
+        if self.mode is None:
+            raise ValueError("TrainStep: cfg.MODEL sets none of USE_FUSION / USE_LIDAR / USE_IMAGE")
         self.optimizer = optimizer if optimizer is not None else build_optimizer(cfg, model)
         dev = next(model.parameters()).device
         cw = cfg.TRAIN.CLASS_WEIGHTS
@@ -71,6 +81,8 @@ class TrainStep:
             self.class_weights = default_class_weights(int(cfg.MODEL.NUM_CLASSES), dev)
         self.lambda_xm = float(cfg.TRAIN.FusionTransformer.lambda_xm)
         self.dual_head = bool(cfg.MODEL.DUAL_HEAD)
+        if metrics is not None and hasattr(metrics, "update_dict"):
+            metrics = (metrics,)       # build_model returns one bare SegIoU for the single-modality models
         self.metrics = metrics or ()
         self.grad_reducer = grad_reducer
         self.fused_loss = True
@@ -103,6 +115,8 @@ class TrainStep:
         else:
             self.optimizer.zero_grad(set_to_none=True)    # first write of each gradient is a move, not fill + add
         preds = self.model(data_batch)
+        if self.mode != "fusion":
+            return self._single_step(preds, data_batch, next_batch, ready)
         logits = preds["lidar_seg_logit"]
         c = logits.shape[1]
         # the kernel counts one C x C matrix per head under one ignore index: metrics of another size or with differing ignore
@@ -125,6 +139,41 @@ class TrainStep:
                 for m in self.metrics:
                     m.update_dict(preds, data_batch)
         (loss_2d + loss_3d).backward()
+        self._finish_step(next_batch, ready)
+        self.last = {"loss_2d": loss_2d.detach(), "loss_3d": loss_3d.detach()}
+        return preds
+
+    def _single_step(self, preds, data_batch, next_batch, ready):
+        """The LiDAR-only / image-only step: one head, one loss, one backward."""
+        key, tag = ("lidar_seg_logit", "3d") if self.mode == "lidar" else ("img_seg_logit", "2d")
+        logits = preds[key]
+        c = logits.shape[1]
+        metrics = [m for m in self.metrics if tag in m.name]     # a metric of the other modality has no head to read here
+        fits = all(m.num_classes == c for m in metrics) and len(metrics) <= 1
+        if self.fused_loss and fits and logits.is_cuda and c % 4 == 0 and c <= 32:
+            # one fused pass: CE + its gradient + the SegIoU confusion matrix (libftx, ftx_seg_loss)
+            conf = None
+            for m in metrics:
+                if m.mat is None:
+                    m.mat = torch.zeros((m.num_classes, m.num_classes), dtype=torch.int64, device=logits.device)
+                conf = m.mat
+            from . import functional as spf
+            loss = spf.seg_loss(logits, data_batch["seg_label"], self.class_weights, conf=conf,
+                                ignore_index=metrics[0].ignore_index if metrics else 0)
+        else:
+            loss = F.cross_entropy(logits, data_batch["seg_label"].long(), weight=self.class_weights)
+            with torch.no_grad():
+                for m in metrics:
+                    m.update_dict(preds, data_batch)
+        loss.backward()
+        if self.mode == "image":
+            next_batch = None      # no LiDAR branch, no index to build ahead
+        self._finish_step(next_batch, ready)
+        self.last = {"loss_" + tag: loss.detach()}
+        return preds
+
+    def _finish_step(self, next_batch, ready):
+        """What follows the backward in every mode: the gradient reduction, the next batch's index build, the optimizer."""
         if self.grad_reducer is not None:
             self.grad_reducer.finish()       # the remaining gradient buckets go out before anything else is issued
         if next_batch is not None:
@@ -142,5 +191,3 @@ class TrainStep:
             self._prefetch_misses = 0 if complete else self._prefetch_misses + 1
             if self._prefetch_misses >= 2:
                 self._prefetch_pause, self._prefetch_misses = 256, 0
-        self.last = {"loss_2d": loss_2d.detach(), "loss_3d": loss_3d.detach()}
-        return preds

@@ -405,6 +405,18 @@ size_t ftx_fusion_loss_workspace_bytes(void);
 int ftx_fusion_loss_mix(const float *lidar_logit, const float *img_logit, const float *lidar_logit2, const float *img_logit2, const int64_t *label, const float *class_weights, float ce_scale, float lambda_xm, int64_t n, int32_t c, int32_t ignore_index, float *losses, float *grad_lidar, float *grad_img, float *grad_lidar2, float *grad_img2, int64_t *conf3d, int64_t *conf2d, void *workspace, size_t workspace_bytes, void *stream);
 int ftx_fusion_loss(const float *lidar_logit, const float *img_logit, const float *lidar_logit2, const float *img_logit2, const int64_t *label, const float *class_weights, float lambda_xm, int64_t n, int32_t c, int32_t ignore_index, float *losses, float *grad_lidar, float *grad_img, float *grad_lidar2, float *grad_img2, int64_t *conf3d, int64_t *conf2d, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- one-head segmentation loss + metric: the LiDAR-only / image-only branches of modules/SemanticTrainer.py:180-186 and the
+ * per-batch validation loss of data/utils/validate.py:122-128 ----
+ * loss[0] = CE_w(logit, label): the weighted-mean cross-entropy term of ftx_fusion_loss, same conventions: class_weights (c) or
+ * NULL = ones; a label outside [0, c) has weight 0 and is not counted; NaN when the total weight is 0.
+ * grad (n,c) receives d loss / d logit = w/W * (softmax - onehot), fully written; grad = NULL selects a forward-only kernel that
+ * contains no gradient stores.  conf (c,c) int64 is ACCUMULATED: conf[label, argmax] += 1 for valid labels other than
+ * ignore_index, first maximum wins (NULL = no metric).  c % 4 == 0, 4 <= c <= 32, n >= 1.  Three launches, no host
+ * synchronisation, no floating-point atomics: two calls on the same inputs give the same bits, and the same bits as
+ * ftx_fusion_loss_mix gives for that head at lambda_xm = 0. */
+size_t ftx_seg_loss_workspace_bytes(void);
+int ftx_seg_loss(const float *logit, const int64_t *label, const float *class_weights, int64_t n, int32_t c, int32_t ignore_index, float *loss, float *grad, int64_t *conf, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- evaluation scatter-back: data/utils/validate.py:62-120 + data/utils/evaluate.py:12-26 ----
  * For every ORIGINAL point i (m of them, all frames of the batch concatenated): r = inverse[i] is the row of the
  * model point (voxel) it was quantised into (inverse_map of its frame + the frame's row offset, map_sparse_to_org);

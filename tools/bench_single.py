@@ -1,0 +1,162 @@
+"""Step time of the single-modality baselines (LidarSeg, ImageSegBilinear) and time of the single-head loss kernel.
+
+usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/single_modality_steps.json]
+
+* Steps: TrainStep on synthetic KITTI-shaped frames (data/synth.make_batch), two alternating resident batches as bench.py
+  uses, batch 4 and batch 1, HIP events around the timed loop after the warm-up, profiler off.  LidarSeg runs with the index
+  prefetch of the next batch (TrainStep(batch, next_batch)).
+* Kernel: ftx_seg_loss at n = 81 237, c = 20 with and without gradient, beside the only way the fused two-head kernel can
+  produce the same loss (ftx_fusion_loss_mix fed the same tensor as both heads, lambda_xm = 0).  The three are alternated in
+  one process over repeated windows; each window is 50 calls captured into one HIP graph (GPU time, back to back) and 50 eager
+  calls through the C ABI (includes the host's issue rate).  Median and min..max over the windows are written.
+
+There is no fallback: without a GPU the tool fails."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+N_KERNEL, C_KERNEL, CALLS, WINDOWS = 81237, 20, 50, 9
+
+
+def _inputs(batch, cycle, device):
+    from fusiontransformer_amd.data.synth import make_batch
+    from fusiontransformer_amd.models.image_models_billinear import pack_img_indices
+    from fusiontransformer_amd.sparse import SparseTensor
+    b = make_batch([1000 * cycle + i for i in range(batch)])
+    return int(b["coords"].shape[0]), {
+        "img": torch.from_numpy(b["img"]).to(device),
+        "img_indices": pack_img_indices(b["img_indices"], device),
+        "lidar": SparseTensor(torch.from_numpy(b["feats"]).to(device), torch.from_numpy(b["coords"]).int().to(device)),
+        "seg_label": torch.from_numpy(b["seg_label"]).to(device),
+    }
+
+
+def step_time(kind, batch, steps, warmup):
+    from fusiontransformer_amd import config
+    from fusiontransformer_amd.models.build import build_model
+    from fusiontransformer_amd.trainer import TrainStep
+    cfg = config.lidar_cfg() if kind == "LidarSeg" else config.image_cfg()
+    torch.manual_seed(0)
+    model, metric = build_model(cfg)
+    model = model.cuda().train()
+    step = TrainStep(cfg, model, metrics=metric)
+    assert step.fused_loss and type(step.optimizer).__module__.endswith("optim")
+    points, res = zip(*[_inputs(batch, cycle, "cuda") for cycle in (0, 1)])
+    seq = [res[i % 2] for i in range(warmup + steps + 1)]     # the index structures are consumed by each forward and rebuilt
+    for i in range(warmup):
+        step(seq[i], next_batch=seq[i + 1])
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(warmup, warmup + steps):
+        step(seq[i], next_batch=seq[i + 1])
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / steps
+    loss = next(iter(step.last.values())).item()
+    assert loss == loss, "the loss is NaN"
+    return {"model": kind, "batch": batch, "points_per_batch": list(points), "steps": steps, "warmup": warmup, "ms_per_step": ms,
+            "frames_per_s": batch * 1e3 / ms, "last_loss": loss}
+
+
+def kernel_times():
+    from fusiontransformer_amd import _lib
+    from fusiontransformer_amd._lib import check, ptr
+    L = _lib.load()
+    n, c = N_KERNEL, C_KERNEL
+    torch.manual_seed(0)
+    x = torch.randn(n, c, device="cuda")
+    label = torch.randint(0, c, (n,), device="cuda")
+    cw = torch.rand(c, device="cuda") + 0.5
+    g, g2 = torch.empty_like(x), torch.empty_like(x)
+    loss, losses = torch.zeros(1, device="cuda"), torch.zeros(2, device="cuda")
+    ws = torch.empty(max(int(L.ftx_seg_loss_workspace_bytes()), int(L.ftx_fusion_loss_workspace_bytes())), dtype=torch.uint8, device="cuda")
+
+    def seg(grad):
+        check(L.ftx_seg_loss(ptr(x), ptr(label), ptr(cw), n, c, 0, ptr(loss), ptr(g) if grad else None, None, ptr(ws), ws.numel(), _lib.stream()),
+              "ftx_seg_loss")
+
+    def two_head():
+        check(L.ftx_fusion_loss_mix(ptr(x), ptr(x), None, None, ptr(label), ptr(cw), 1.0, 0.0, n, c, 0, ptr(losses), ptr(g), ptr(g2), None, None,
+                                    None, None, ptr(ws), ws.numel(), _lib.stream()), "ftx_fusion_loss_mix")
+
+    variants = {"seg_loss_grad": lambda: seg(True), "seg_loss_forward_only": lambda: seg(False), "fusion_loss_mix_same_tensor_twice": two_head}
+    for fn in variants.values():
+        fn()
+    torch.cuda.synchronize()
+    two_head()
+    seg(True)
+    torch.cuda.synchronize()
+    assert loss.item() == losses[1].item() == losses[0].item(), "the two kernels disagree on the loss"
+    graphs = {}
+    for name, fn in variants.items():
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for _ in range(CALLS):
+                fn()
+        graphs[name] = gr
+
+    def timed(run):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / CALLS
+
+    def eager(fn):
+        for _ in range(CALLS):
+            fn()
+
+    for name in variants:          # warm-up window
+        timed(graphs[name].replay)
+        timed(lambda: eager(variants[name]))
+    us = {name: {"graph": [], "eager": []} for name in variants}
+    for _ in range(WINDOWS):       # alternated: one window of each variant after the other
+        for name in variants:
+            us[name]["graph"].append(timed(graphs[name].replay))
+        for name in variants:
+            us[name]["eager"].append(timed(lambda: eager(variants[name])))
+    out = {"n": n, "c": c, "calls_per_window": CALLS, "windows": WINDOWS, "unit": "us per call (3 launches)"}
+    for name, d in us.items():
+        out[name] = {how: {"median": statistics.median(v), "min": min(v), "max": max(v)} for how, v in d.items()}
+    a, b = out["seg_loss_grad"]["graph"], out["fusion_loss_mix_same_tensor_twice"]["graph"]
+    out["seg_loss_grad_not_slower_than_two_head_call"] = bool(a["median"] <= b["median"] + (b["max"] - b["min"]))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=15)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "single_modality_steps.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_single: needs a GPU (there is no fallback)")
+    if args.steps < 50:
+        raise SystemExit("bench_single: at least 50 timed steps")
+    result = {"what": "single-modality train steps on synthetic KITTI-shaped frames (two alternating resident batches, HIP events, "
+                      "profiler off) and the single-head loss kernel beside the fused two-head kernel fed one tensor twice",
+              "device": torch.cuda.get_device_name(0), "steps": []}
+    for kind in ("LidarSeg", "ImageSegBilinear"):
+        for batch in (4, 1):
+            r = step_time(kind, batch, args.steps, args.warmup)
+            print(json.dumps(r), flush=True)
+            result["steps"].append(r)
+    result["loss_kernel"] = kernel_times()
+    print(json.dumps(result["loss_kernel"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
