@@ -71,6 +71,7 @@ SIGNATURES = {
     "ftx_rows_gemm": (C.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "ftx_spconv_gemm_block_cols": (_i32, [_i32, _i64, _i32]),
     "ftx_spconv_reduce": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "ftx_spconv_reduce_bn_eval": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp]),
     "ftx_spconv_reduce_stats_blocks": (_i32, [_i64, _i32]),
     "ftx_spconv_reduce_stats": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
     "ftx_bn_train_fwd_totals": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -126,6 +127,14 @@ SIGNATURES = {
     "ftx_resize_coeffs_host": (C.c_int, [_i32, _i32, _vp, _vp]),
     "ftx_resize_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "ftx_resize_bilinear_u8": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ftx_rows_concat": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _vp]),
+    "ftx_rows_add": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "ftx_spvcnn_layer_bytes": (_i32, []),
+    "ftx_spvcnn_op_bytes": (_i32, []),
+    "ftx_spvcnn_map_bytes": (_i32, []),
+    "ftx_spvcnn_pv_bytes": (_i32, []),
+    "ftx_spvcnn_eval_arena_bytes": (_sz, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "ftx_spvcnn_eval": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <utility>
 #include "ftx_common.h"
+#include "ftx_bn_eval_op.h"
 #include "ftx_lastblock.h"
 
 using namespace ftx;
@@ -349,11 +350,7 @@ __global__ void bn_apply_eval_kernel(const float *__restrict__ x, const float *_
       rr[0] = t.x; rr[1] = t.y; rr[2] = t.z; rr[3] = t.w;
     }
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      float is = (float)(1.0 / sqrt((double)rv[col + v] + (double)eps));
-      float t = (o[v] - rm[col + v]) * is * gamma[col + v] + beta[col + v] + rr[v];
-      o[v] = (relu && !(t > 0.f)) ? 0.f : t;
-    }
+    for (int v = 0; v < 4; ++v) o[v] = bn_eval_elem(o[v], rm[col + v], rv[col + v], eps, gamma[col + v], beta[col + v], rr[v], relu);
     *(float4 *)&y[e * 4] = make_float4(o[0], o[1], o[2], o[3]);
   }
 }

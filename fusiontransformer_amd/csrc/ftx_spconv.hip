@@ -23,6 +23,7 @@
 #include <cstring>
 #include <cstdlib>
 #include "ftx_common.h"
+#include "ftx_bn_eval_op.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -486,6 +487,59 @@ extern "C" int ftx_spconv_reduce(const float *tmp, const int32_t *pos, int64_t n
   else
     spconv_reduce_kernel<0><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
   return check_launch("ftx_spconv_reduce");
+}
+
+// The same reduce with the eval-mode BatchNorm (+ residual) (+ ReLU) applied to the row before its one store: what ftx_spconv_reduce
+// followed by ftx_bn_eval_fwd computes, bit for bit (positions first, then the valid rows in ascending k, then bn_eval_elem on the
+// four sums), in one launch and without the (n, co) round trip through memory.
+template <int KVOL>
+__global__ void spconv_reduce_bn_eval_kernel(const float *__restrict__ tmp, const int32_t *__restrict__ pos, int64_t n, int co,
+                                             const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                             const float *__restrict__ rm, const float *__restrict__ rv, float eps, int relu,
+                                             float *__restrict__ out) {
+  const int cv = co >> 2;
+  const int64_t total = n * cv;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    int64_t r = e / cv;
+    int j = (int)(e - r * cv) * 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int32_t p[KVOL];
+#pragma unroll
+    for (int k = 0; k < KVOL; ++k) p[k] = pos[(int64_t)k * n + r];
+#pragma unroll
+    for (int k = 0; k < KVOL; ++k) {
+      if (p[k] >= 0) {
+        float4 v = *(const float4 *)&tmp[(int64_t)p[k] * co + j];
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+      }
+    }
+    float o[4] = {acc.x, acc.y, acc.z, acc.w};
+    float rr[4] = {0, 0, 0, 0};
+    if (res) {
+      float4 t = *(const float4 *)&res[r * co + j];
+      rr[0] = t.x; rr[1] = t.y; rr[2] = t.z; rr[3] = t.w;
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) o[v] = bn_eval_elem(o[v], rm[j + v], rv[j + v], eps, gamma[j + v], beta[j + v], rr[v], relu);
+    *(float4 *)&out[r * co + j] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+extern "C" int ftx_spconv_reduce_bn_eval(const float *tmp, const int32_t *pos, int64_t n, int32_t co, int32_t kvol, const float *residual,
+                                         const float *gamma, const float *beta, const float *running_mean, const float *running_var,
+                                         float eps, int32_t relu, float *out, void *stream) {
+  FTX_REQUIRE(n >= 0 && co >= 4 && co % 4 == 0, "ftx_spconv_reduce_bn_eval: bad size (n=%lld, co=%d must be a multiple of 4)", (long long)n, co);
+  FTX_REQUIRE(kvol == 27 || kvol == 8, "ftx_spconv_reduce_bn_eval: kvol must be 8 or 27, got %d", kvol);
+  if (n == 0) return FTX_OK;
+  FTX_REQUIRE(pos && out && gamma && beta && running_mean && running_var, "ftx_spconv_reduce_bn_eval: null pointer");
+  int64_t g = ceil_div(n * (co / 4), 256);
+  if (g > 8192) g = 8192;
+  hipStream_t st = (hipStream_t)stream;
+  if (kvol == 27)
+    spconv_reduce_bn_eval_kernel<27><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, residual, gamma, beta, running_mean, running_var, eps, relu, out);
+  else
+    spconv_reduce_bn_eval_kernel<8><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, residual, gamma, beta, running_mean, running_var, eps, relu, out);
+  return check_launch("ftx_spconv_reduce_bn_eval");
 }
 
 // The same reduce, also producing the BatchNorm statistics of its output (sum and sum of squares per channel, float64) as

@@ -989,6 +989,72 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum=0.1
     return _BatchNormEval.apply(x, residual, gamma, beta, running_mean, running_var, eps, relu)
 
 
+# ---------------------------------------------------------------- eval-mode Conv3d -> BatchNorm in two launches, row helpers of the executor
+def spconv_reduce_bn_eval(tmp, pos, n_out, gamma, beta, running_mean, running_var, eps=1e-5, residual=None, relu=False):
+    """relu?(BNeval(sum_k tmp[pos[k, o]]) (+ residual[o])) in ONE launch (ftx_spconv_reduce_bn_eval): bit-identical to ftx_spconv_reduce
+    followed by ftx_bn_eval_fwd.  tmp (P, co) pair rows, pos (kvol, n_out) int32 with kvol 8 or 27.  No autograd: eval mode only."""
+    L = _lib.load()
+    tmp = req(tmp, F32, "reduce_bn_eval tmp", 2)
+    req(pos, I32, "reduce_bn_eval pos", 2)
+    co, kvol = tmp.shape[1], pos.shape[0]
+    if pos.shape[1] != n_out:
+        raise ValueError("reduce_bn_eval: the position table does not match the output rows")
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        req(t, F32, "reduce_bn_eval " + nm, 1)
+        if t.shape[0] != co:
+            raise ValueError("reduce_bn_eval: BatchNorm parameter length != output channels")
+    if residual is not None:
+        residual = req(residual.contiguous(), F32, "reduce_bn_eval residual", 2)
+        if residual.shape != (n_out, co):
+            raise ValueError("reduce_bn_eval: residual shape mismatch")
+    out = _empty((n_out, co), F32, tmp)
+    _log_launch("spconv_reduce", dict(pairs=tmp.shape[0], n_out=n_out, ca=0, co=co, kvol=kvol), lambda: check(L.ftx_spconv_reduce_bn_eval(
+        ptr(tmp), ptr(pos), n_out, co, kvol, ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(eps), int(relu), ptr(out),
+        stream()), "ftx_spconv_reduce_bn_eval"))
+    return out
+
+
+def conv_bn_eval(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, eps=1e-5, residual=None, relu=False, bf16=False):
+    """Conv3d -> BatchNorm(eval) (+ residual) (+ ReLU) without autograd.  On the pair-list route (and for an empty map) the reduce carries
+    the BatchNorm in its epilogue: pair GEMM + ftx_spconv_reduce_bn_eval, two launches instead of three and one (n_out, co) round trip
+    less; the other routes run sparse_conv's launch and the eval BatchNorm pass.  Bit-identical to sparse_conv + batch_norm(training=False)."""
+    feats = req(feats.contiguous(), F32, "conv3d feats", 2)
+    kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
+    kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
+    route = _conv_route(km, transposed, ca, co, kvol, n_out, bf16)
+    if route in (_PAIRS, _EMPTY) and kvol in (8, 27):
+        src, _, _, dst_pos = _map_sides(km, transposed)
+        L = _lib.load()
+        tmp = _empty((km.n_pairs, co), F32, feats)
+        gemm, kind = _PAIRS_GEMM[bool(bf16)]
+        _log_launch(kind, dict(pairs=km.n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol), lambda: check(getattr(L, gemm)(
+            ptr(feats), n_in, ptr(src), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(tmp), stream()), gemm))
+        return spconv_reduce_bn_eval(tmp, dst_pos, n_out, gamma, beta, running_mean, running_var, eps, residual=residual, relu=relu)
+    with torch.no_grad():
+        return batch_norm(_conv_forward(feats, kernel, km, transposed, bool(bf16)), gamma, beta, running_mean, running_var, False, eps=eps,
+                          residual=residual, relu=relu)
+
+
+def rows_concat(a, b):
+    """torch.cat([a, b], 1) of (n, ca) and (n, cb) float32 rows (ftx_rows_concat; channel counts multiples of 4)."""
+    a, b = req(a, F32, "rows_concat a", 2), req(b, F32, "rows_concat b", 2)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("rows_concat: row counts differ")
+    out = _empty((a.shape[0], a.shape[1] + b.shape[1]), F32, a)
+    check(_lib.load().ftx_rows_concat(ptr(a), a.shape[1], ptr(b), b.shape[1], a.shape[0], ptr(out), stream()), "ftx_rows_concat")
+    return out
+
+
+def rows_add(a, b):
+    """a + b of two (n, c) float32 row matrices (ftx_rows_add; c a multiple of 4)."""
+    a, b = req(a, F32, "rows_add a", 2), req(b, F32, "rows_add b", 2)
+    if a.shape != b.shape:
+        raise ValueError("rows_add: shapes differ")
+    out = torch.empty_like(a)
+    check(_lib.load().ftx_rows_add(ptr(a), ptr(b), a.shape[0], a.shape[1], ptr(out), stream()), "ftx_rows_add")
+    return out
+
+
 # ---------------------------------------------------------------- 2D -> 3D lift, nearest resample
 def lift_segments(img_idx, point_batch, b, gh, gw, H, W) -> Segments:
     """Points sorted by the grid cell they read: turns the lift's backward into a gather-reduce."""

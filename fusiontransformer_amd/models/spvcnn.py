@@ -86,6 +86,19 @@ class ReLU(nn.ReLU):
         return F.relu(x)
 
 
+def _conv_map(conv, x):
+    """(kernel map, output coordinates, output stride) of a k > 1 Conv3d on x, as Conv3d.forward finds them."""
+    ks, s = conv.kernel_size, conv.stride
+    if not conv.t:
+        km = x.cm.kernel_map(ks, x.s, s)
+        return km, km.out_coords, x.s * s
+    original_stride = x.s // s
+    km = x.cm.kernel_maps.get((ks, original_stride, s))
+    if km is None:
+        raise RuntimeError("transposed Conv3d needs the kernel map of the paired strided Conv3d")
+    return km, x.cm.coords[original_stride], original_stride
+
+
 def _conv_bn(conv, bn, x, residual=None, relu=True):
     """Conv3d -> BatchNorm (-> + residual) (-> ReLU).  In training a k>1 convolution and its BatchNorm run as one autograd node whose
     reduce pass also produces the batch statistics (functional.conv_bn_train); eval and 1x1x1 layers run the two separately."""
@@ -104,6 +117,14 @@ def _conv_bn(conv, bn, x, residual=None, relu=True):
             bn.num_batches_tracked.add_(1)
         feats = spf.conv_bn_train(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
                                   residual=residual, relu=relu, bf16=getattr(conv, "ftx_bf16", False))
+        out = x.derive(feats, coords, stride)
+        out.check()
+        return out
+    if getattr(conv, "ftx_native_eval", False) and not bn.training and not torch.is_grad_enabled() and not (ks == 1 and s == 1) and x.F.is_cuda:
+        # SPVCNN.set_native_eval where the executor does not run (a layer option it refuses): the reduce carries the eval BatchNorm
+        km, coords, stride = _conv_map(conv, x)
+        feats = spf.conv_bn_eval(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, residual=residual,
+                                 relu=relu, bf16=getattr(conv, "ftx_bf16", False))
         out = x.derive(feats, coords, stride)
         out.check()
         return out
@@ -202,6 +223,9 @@ class SPVCNN(nn.Module):
         # cfg.MODEL.lidar_bf16: the LiDAR branch on bf16-operand kernels, see set_bf16
         self.lidar_bf16 = bool(kwargs.get("lidar_bf16", False))
         self.set_bf16(self.lidar_bf16)
+        # cfg.MODEL.lidar_native_eval: the eval-mode, no-gradient forward through the native executor, see set_native_eval
+        self._native = None
+        self.set_native_eval(bool(kwargs.get("lidar_native_eval", False)))
         # optional injected keep-masks {'y1': (N4,C), 'y3': (N2,C)} so a train-mode run can be
         # compared with the oracle (Dropout RNG streams differ between CPU and GPU)
         self.dropout_masks = None
@@ -222,6 +246,67 @@ class SPVCNN(nn.Module):
         for seq in seqs:
             seq[0].ftx_bf16 = bool(on)
         return self
+
+    def set_native_eval(self, on=True):
+        """Opt-in native executor for the eval-mode forward (include/ftx.h: ftx_spvcnn_eval).  With it on, a forward in eval mode, with
+        gradients disabled and features on the GPU, builds the batch's coordinate structures as before and then issues the whole network
+        -- first convolution of the stem to z3.F -- as one library call per segment (stem / encoder / decoder) over an arena this module
+        owns, instead of a few hundred calls through Python; pair-list convolutions run the reduce that carries the eval BatchNorm
+        (ftx_spconv_reduce_bn_eval).  The results are bit-identical to the switch being off.  In training mode, with gradients enabled,
+        on CPU tensors or for a layer option the executor refuses, the existing path runs exactly as with the switch off."""
+        self.lidar_native_eval = bool(on)
+        for m in self.modules():
+            if isinstance(m, Conv3d):
+                m.ftx_native_eval = bool(on)
+        if not on:
+            self._native = None
+        return self
+
+    def _native_executor(self, x):
+        """The executor when this forward is one it runs (see set_native_eval), else None."""
+        if not self.lidar_native_eval or self.training or torch.is_grad_enabled() or not x.F.is_cuda:
+            return None
+        if self._native is None:
+            from .. import native_eval
+            try:
+                self._native = native_eval.NativeEval(self)
+            except native_eval.Unsupported:
+                self._native = False
+        return self._native or None
+
+    def _native_steps(self, ex, x, fuse_early, fuse_middle):
+        """_backbone_steps through the executor: the same index build, then one call per segment; "need_early" / "need_middle" are
+        yielded where the image features are first touched, the stage tokens are the segment boundaries."""
+        prepared = getattr(x, "prepared", None)
+        if isinstance(prepared, PendingIndex):
+            while prepared.done is None:
+                yield "sync"
+                prepared.step()
+            prepared = prepared.done
+        if prepared is not None:
+            z, x0 = prepared.take(torch.cuda.current_stream())
+            x.prepared = None
+        else:
+            z, x0 = yield from self._index_steps(x, ahead=True)
+        yield "voxelized"
+        run = ex.begin(z, x0)
+        run.segments(0, 0)
+        early = middle = None
+        if fuse_early is not None:
+            yield "need_early"
+            early = fuse_early() if callable(fuse_early) else fuse_early
+        yield "stem"
+        run.segments(1, 1, add_early=early)
+        if fuse_middle is not None:
+            yield "need_middle"
+            middle = fuse_middle() if callable(fuse_middle) else fuse_middle
+        yield "stage4"
+        feats = run.segments(2, 2, add_middle=middle)
+        yield "up4"
+        cm = x0.cm
+        levels = {"x%d" % l: SparseTensor(None, cm.coords[s], s) for l, s in enumerate((1, 2, 4, 8, 16)) if l}
+        self.last_index = dict(x0=x0, z=z, **levels)
+        return feats
 
     def weight_initialization(self):
         for m in self.modules():
@@ -251,6 +336,9 @@ class SPVCNN(nn.Module):
         """The same forward as a generator that yields at stage boundaries, so a scheduler can interleave
         the issue of this branch with the image branch (see _fusion_common.run_fusion).  It yields
         "need_early" / "need_middle" right before it touches the image features."""
+        ex = self._native_executor(x)
+        if ex is not None:
+            return (yield from self._native_steps(ex, x, fuse_early, fuse_middle))
         prepared = getattr(x, "prepared", None)
         if isinstance(prepared, PendingIndex):
             # started ahead of this forward (prepare(wait=False)) and parked at a host read: finish it here, on its own stream

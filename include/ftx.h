@@ -232,6 +232,15 @@ int32_t ftx_spconv_gemm_block_cols(int32_t co, int64_t n_pairs, int32_t kvol);
 /* out[r,:] = sum over k (ascending) of tmp[pos[k,r],:] for pos >= 0; out (n, co) fully written. */
 int ftx_spconv_reduce(const float *tmp, const int32_t *pos, int64_t n, int32_t co, int32_t kvol, float *out, void *stream);
 
+/* The reduce with the eval-mode BatchNorm (+ residual) (+ ReLU) in its epilogue, one launch:
+ *   out[r,:] = relu?( (sum_k tmp[pos[k,r],:] - running_mean) * 1/sqrt(running_var + eps) * gamma + beta (+ residual[r,:]) )
+ * BIT-IDENTICAL to ftx_spconv_reduce followed by ftx_bn_eval_fwd on its output (same summation order, the same per-element expression:
+ * csrc/ftx_bn_eval_op.h), without the write and the read of the (n, co) convolution output in between.  What the eval forward of a
+ * Conv3d -> BatchNorm layer on the pair-list route runs (models/spvcnn.py:22-35,53-79 under model.eval()).
+ * co a multiple of 4; kvol must be 8 or 27; residual (n, co) may be NULL; relu != 0 applies max(., 0) as !(t > 0) ? 0 : t.
+ * tmp may be NULL when no entry of pos is >= 0.  No atomics, no host synchronisation, capturable. */
+int ftx_spconv_reduce_bn_eval(const float *tmp, const int32_t *pos, int64_t n, int32_t co, int32_t kvol, const float *residual, const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps, int32_t relu, float *out, void *stream);
+
 /* The reduce pass that also produces the BatchNorm statistics of its output: part (nb + 1, 2, co) float64 -- nb per-block
  * partial (sum, sum of squares) rows, nb = ftx_spconv_reduce_stats_blocks(n, co), then ONE row of column totals, summed in block
  * order by whichever block finishes last (no second launch; bit-reproducible).  Feed `part + nb*2*co` to
@@ -485,6 +494,78 @@ int32_t ftx_resize_ksize(int32_t in, int32_t out);
 int ftx_resize_coeffs_host(int32_t in, int32_t out, int32_t *bounds_host, int32_t *kk_host);
 size_t ftx_resize_workspace_bytes(int32_t n_frames, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w);
 int ftx_resize_bilinear_u8(const uint8_t *src, int64_t frame_stride, int64_t pitch, int32_t n_frames, int32_t in_h, int32_t in_w, int32_t channels, const int32_t *bounds_x, const int32_t *kk_x, int32_t ksize_x, const int32_t *bounds_y, const int32_t *kk_y, int32_t ksize_y, int32_t out_h, int32_t out_w, uint8_t *dst, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- native eval-mode executor of the SPVCNN LiDAR branch (models/spvcnn.py:191-233 under model.eval(), no gradients) ----
+ * ftx_spvcnn_eval issues the forward of one SPVCNN from the first convolution of the stem to the final point features (z3.F) on
+ * `stream`: the same per-op entry points, in the same order, as the Python path issues them one by one (ftx_spconv_pairs_gemm /
+ * _scatter / ftx_spconv_ostat, ftx_rows_gemm, ftx_bn_eval_fwd, ftx_spconv_reduce_bn_eval, ftx_voxelize_fwd_sorted, ftx_devoxelize_fwd)
+ * plus ftx_rows_concat / ftx_rows_add below where that path uses torch.cat and `+`.  The results are bit-identical to that path.
+ * Dropout is the identity in eval mode.  Building the coordinate structures of the batch and the segmentation heads stay with the caller.
+ *
+ * ftx_rows_concat: out (n, ca + cb) = a (n, ca) ++ b (n, cb) per row.  ftx_rows_add: out = a + b over (n, c), one fp32 add per element;
+ * out may alias a or b.  Channels multiples of 4, 16-byte accesses, n = 0 is a no-op.
+ *
+ * Tables.  All four are arrays of packed little-endian records in HOST memory (the pointers inside them are device pointers); the
+ * library reports each record size (ftx_spvcnn_*_bytes) so a binding can assert its layout.
+ *   layer (model table; built once per model, rebuilt when a parameter moves):
+ *     const float *weight  Conv3d kernel (kvol, ca, co), (ca, co) for kvol = 1; nn.Linear weight (co, ca)
+ *     const float *bias    nn.Linear bias (co) or NULL; NULL for a convolution
+ *     const float *gamma, *beta, *running_mean, *running_var   the BatchNorm behind the layer, (co) each
+ *     int32 ca, co, kvol (1, 8 or 27; 0 for a Linear), stride, transposed, bf16;  float eps;  int32 kind (FTX_SPVCNN_LAYER_*)
+ *     bf16 != 0: the layer's GEMM runs on the bf16-operand entry points (ftx_spconv_pairs_gemm_bf16 / _scatter_bf16, ftx_rows_gemm_bf16),
+ *     as SPVCNN.set_bf16 makes the Python path do; the flag is honoured here, nothing falls back.
+ *   op (the static program of the network, emitted once per model by the host; fusiontransformer_amd/native_eval.py emits SPVCNN's):
+ *     int32 kind (FTX_SPVCNN_OP_*), segment (0 stem, 1 encoder, 2 decoder; ascending), layer (index into the model table; for ADD_EXT
+ *     0 = the early-fusion addend, 1 = the middle-fusion addend), map (index into the kernel maps for CONV_BN with kvol > 1, into the
+ *     point-voxel indices for VOXELIZE / DEVOXELIZE, else -1), src, src2 (second operand of CONCAT / ADD, residual of CONV_BN or -1),
+ *     dst, relu, level (whose rows dst has: 0..4 the voxel levels of stride 1, 2, 4, 8, 16; 5 the points), channels (of dst), 2 x reserved.
+ *     src / src2 / dst number buffers ("slots"): FTX_SPVCNN_SLOT_INPUT is x0 (the voxelised input features, rows[0] rows),
+ *     FTX_SPVCNN_SLOT_OUTPUT is `out` (rows[5] rows), slots from FTX_SPVCNN_SLOT_FIRST up to 255 live in the arena.  Every slot is written
+ *     by exactly one op before it is read (ADD_EXT alone works in place).
+ *   map (batch table, one per kernel map): const int32 *nbr, *pos, *pos_t, *pair_in, *pair_out, *koff; int64 n_pairs, n_in, n_out;
+ *     int32 kvol, fine_bijective -- the arrays ftx_kernel_map_build / _count / _pairs produce.
+ *   pv (batch table, one per stride at which points and voxels exchange features): const int32 *vox_idx (n), *vox_counts (n_vox),
+ *     *vox_order (n), *vox_seg_off (n_vox + 1) [ftx_segment_build / ftx_level_segments]; const int32 *devox_idx (n, 8);
+ *     const float *devox_weights (n, 8) [ftx_kernel_map_build transposed, ftx_trilinear_weights]; int64 n_vox; int32 level, reserved.
+ *   rows_host: int64[6], the rows of the five levels and of the point set.
+ *   routes_host: int32[n_ops], for every CONV_BN / LINEAR_BN op how its GEMM runs (FTX_SPVCNN_ROUTE_*): chosen by the CALLER (the host's
+ *     one routing rule, functional._conv_route).  The library obeys and has no rule of its own; a route an op cannot take (the direct
+ *     route on a map that is not a bijection, the output-stationary route on a layer ftx_spconv_ostat_supported refuses, the empty
+ *     route on a map with pairs, anything but ROWS on a dense layer) is FTX_EINVAL.
+ * Segments.  A call runs the ops of segments [first_segment, last_segment]: 0 = the stem up to z0, 1 = stage1..stage4, point
+ * transform 0, z1, 2 = up1..up4, point transforms 1 and 2, z3.  Slots keep their place in the arena between the calls of one forward,
+ * so a fusion model runs one call per segment and produces the image-side addend in between: add_early (rows[5], channels of z0) is
+ * added to z0 by the ADD_EXT op that opens segment 1, add_middle to z1 by the one that opens segment 2; NULL skips the add.
+ * Arena.  Every intermediate lives in `arena` (device memory, 256-byte aligned, caller-owned): ftx_spvcnn_eval_arena_bytes is a host
+ * function of the tables alone (needs no GPU; 0 and an error text for tables it refuses), a multiple of 256, and never decreases when a
+ * row or pair count grows.  Buffers whose last reader has run are reused.  An arena that is too small is FTX_EWORKSPACE.
+ * Every table is validated before the first launch; a failing launch is reported with the op and layer index in ftx_last_error().
+ * No host synchronisation, no allocation, no state kept beyond the call. */
+#define FTX_SPVCNN_LAYER_CONV_BN 1
+#define FTX_SPVCNN_LAYER_LINEAR_BN 2
+#define FTX_SPVCNN_OP_CONV_BN 1
+#define FTX_SPVCNN_OP_LINEAR_BN 2
+#define FTX_SPVCNN_OP_VOXELIZE 3
+#define FTX_SPVCNN_OP_DEVOXELIZE 4
+#define FTX_SPVCNN_OP_CONCAT 5
+#define FTX_SPVCNN_OP_ADD 6
+#define FTX_SPVCNN_OP_ADD_EXT 7
+#define FTX_SPVCNN_ROUTE_EMPTY 0
+#define FTX_SPVCNN_ROUTE_DIRECT 1
+#define FTX_SPVCNN_ROUTE_OSTAT 2
+#define FTX_SPVCNN_ROUTE_PAIRS 3
+#define FTX_SPVCNN_ROUTE_ROWS 4
+#define FTX_SPVCNN_SLOT_INPUT 0
+#define FTX_SPVCNN_SLOT_OUTPUT 1
+#define FTX_SPVCNN_SLOT_FIRST 2
+int ftx_rows_concat(const float *a, int32_t ca, const float *b, int32_t cb, int64_t n, float *out, void *stream);
+int ftx_rows_add(const float *a, const float *b, int64_t n, int32_t c, float *out, void *stream);
+int32_t ftx_spvcnn_layer_bytes(void);
+int32_t ftx_spvcnn_op_bytes(void);
+int32_t ftx_spvcnn_map_bytes(void);
+int32_t ftx_spvcnn_pv_bytes(void);
+size_t ftx_spvcnn_eval_arena_bytes(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host);
+int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const float *x0, int32_t first_segment, int32_t last_segment, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,134 @@
+"""Eval-mode forward of the LiDAR-only and the middle-fusion model with the native executor of the LiDAR branch off and on
+(SPVCNN.set_native_eval), profiler off.  Two resident batches alternate, so every per-batch structure is rebuilt in every forward.
+
+Per (model, batch, switch) and over `--windows` windows of `--steps` forwards, the switch alternating window by window in one process:
+  wall ms / forward   host clock around the window, ending in a device synchronise
+  issue ms / forward  host clock until the last launch of the window has returned, before the synchronise (the forwards are issued
+                      back to back, so this is what the host needs per forward, host reads of the index build included)
+  lidar ms / forward  HIP events on the stream that runs the LiDAR branch, from the end of the previous forward's work to the end of
+                      this one's
+  arena / peak bytes  the executor's arena, and torch's peak allocation above the resident state during a window
+usage:
+  python tools/bench_eval.py [--models lidar,middle] [--batches 1,4] [--windows 5] [--steps 20] [--modes off,on]
+      --modes off also runs on a checkout that has no executor (the baseline of the comparison)
+  rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/bench_eval.py --mark-launches   # one marked forward per setting
+  python tools/bench_eval.py --count-launches DIR                                                     # kernel launches per forward
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+MARK = "cosh"        # a torch kernel nothing else in the program launches: one between forwards cuts the trace
+
+
+def count_launches(trace_dir):
+    kt = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)[0]
+    rows = sorted(csv.DictReader(open(kt)), key=lambda r: int(r["Start_Timestamp"]))
+    order = json.load(open(os.path.join(trace_dir, "order.json")))
+    marks = [i for i, r in enumerate(rows) if MARK in r["Kernel_Name"]]
+    assert len(marks) == 2 * len(order), (len(marks), len(order))
+    for j, what in enumerate(order):
+        lo, hi = marks[2 * j], marks[2 * j + 1]
+        ours = sum(1 for r in rows[lo + 1:hi] if "ftx" in r["Kernel_Name"] or "spconv" in r["Kernel_Name"] or "bn_" in r["Kernel_Name"])
+        print("%-28s %5d kernel launches per forward (%d with 'ftx' / 'spconv' / 'bn_' in the name)" % (what, hi - lo - 1, ours))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default="lidar,middle")
+    ap.add_argument("--batches", default="1,4")
+    ap.add_argument("--modes", default="off,on")
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--mark-launches", action="store_true")
+    ap.add_argument("--count-launches", metavar="DIR")
+    ap.add_argument("--order-file", default=None)
+    a = ap.parse_args()
+    if a.count_launches:
+        return count_launches(a.count_launches)
+
+    import torch
+    from bench import build_inputs
+    from fusiontransformer_amd import gemm_tuning
+    from fusiontransformer_amd.config import fusion_cfg, lidar_cfg
+    from fusiontransformer_amd.models._fusion_common import _branch_streams
+    from fusiontransformer_amd.models.build import build_model
+    assert torch.cuda.is_available(), "bench_eval measures on the GPU; there is no CPU figure"
+    gemm_tuning.enable(0)
+    dev = torch.device("cuda")
+    modes = a.modes.split(",")
+    order = []
+    marker = torch.zeros(8, device=dev)
+    for kind in a.models.split(","):
+        cfg = lidar_cfg() if kind == "lidar" else fusion_cfg(kind)
+        torch.manual_seed(0)
+        model = build_model(cfg)[0].cuda().eval()
+        net = model.backbone if kind == "lidar" else model.lidar_backbone
+        if "on" in modes and not hasattr(net, "set_native_eval"):
+            sys.exit("this checkout has no native executor: run with --modes off")
+        lidar_stream = torch.cuda.current_stream() if kind == "lidar" else _branch_streams(dev)[1]
+
+        def switch(mode):
+            if hasattr(net, "set_native_eval"):
+                net.set_native_eval(mode == "on")
+
+        for batch in (int(b) for b in a.batches.split(",")):
+            datas = [build_inputs(cfg, batch, "kitti", 0, dev, cycle=c)[1] for c in range(2)]
+            with torch.no_grad():
+                for mode in modes:
+                    switch(mode)
+                    for i in range(a.warmup):
+                        model(datas[i % 2])
+                torch.cuda.synchronize()
+                if a.mark_launches:
+                    for mode in modes:
+                        switch(mode)
+                        torch.cuda.synchronize()
+                        marker.cosh_()
+                        model(datas[0])
+                        torch.cuda.synchronize()
+                        marker.cosh_()
+                        order.append("%s batch %d %s" % (kind, batch, mode))
+                    continue
+                res = {m: {"wall": [], "issue": [], "lidar": [], "peak": 0} for m in modes}
+                for w in range(a.windows):
+                    for mode in (modes if w % 2 == 0 else modes[::-1]):
+                        switch(mode)
+                        model(datas[1])
+                        torch.cuda.synchronize()
+                        base = torch.cuda.memory_allocated()
+                        torch.cuda.reset_peak_memory_stats()
+                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+                        ev[0].record(lidar_stream)
+                        t0 = time.perf_counter()
+                        for i in range(a.steps):
+                            model(datas[i % 2])
+                            ev[i + 1].record(lidar_stream)
+                        t1 = time.perf_counter()
+                        torch.cuda.synchronize()
+                        t2 = time.perf_counter()
+                        r = res[mode]
+                        r["wall"].append((t2 - t0) / a.steps * 1e3)
+                        r["issue"].append((t1 - t0) / a.steps * 1e3)
+                        r["lidar"].append(ev[0].elapsed_time(ev[-1]) / a.steps)
+                        r["peak"] = max(r["peak"], torch.cuda.max_memory_allocated() - base)
+                for mode in modes:
+                    r = res[mode]
+                    arena = sum(b.shape[0] for b in net._native.arenas.values()) if (mode == "on" and getattr(net, "_native", None)) else 0
+                    fmt = lambda v: "%.3f (%.3f..%.3f)" % (statistics.median(v), min(v), max(v))
+                    print("%-6s batch %d native %-3s  wall %s ms  issue %s ms  lidar stream %s ms  arena %.1f MiB  torch peak %.1f MiB" % (
+                        kind, batch, mode, fmt(r["wall"]), fmt(r["issue"]), fmt(r["lidar"]), arena / 2 ** 20, r["peak"] / 2 ** 20), flush=True)
+        del model
+    if a.mark_launches:
+        json.dump(order, open(a.order_file or "order.json", "w"))
+
+
+if __name__ == "__main__":
+    main()
