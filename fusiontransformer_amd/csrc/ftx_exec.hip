@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "ftx_common.h"
+#include "ftx_spvcnn_tables.h"
 
 using namespace ftx;
 
@@ -63,17 +64,8 @@ struct Layer {
 struct Op {
   int32_t kind, segment, layer, map, src, src2, dst, relu, level, channels, reserved0, reserved1;
 };
-struct Map {
-  const int32_t *nbr, *pos, *pos_t, *pair_in, *pair_out, *koff;
-  int64_t n_pairs, n_in, n_out;
-  int32_t kvol, fine_bijective;
-};
-struct PV {
-  const int32_t *vox_idx, *vox_counts, *vox_order, *vox_seg_off, *devox_idx;
-  const float *devox_weights;
-  int64_t n_vox;
-  int32_t level, reserved;
-};
+using Map = ftx::SpvcnnMap;   // ftx_spvcnn_tables.h: shared with the index builder that writes them
+using PV = ftx::SpvcnnPV;
 static_assert(sizeof(Layer) == 80 && sizeof(Op) == 48 && sizeof(Map) == 80 && sizeof(PV) == 64, "table records are packed");
 
 constexpr int kLevels = 6;        // five voxel levels + the point set

@@ -226,6 +226,8 @@ class SPVCNN(nn.Module):
         # cfg.MODEL.lidar_native_eval: the eval-mode, no-gradient forward through the native executor, see set_native_eval
         self._native = None
         self.set_native_eval(bool(kwargs.get("lidar_native_eval", False)))
+        # cfg.MODEL.lidar_native_index: the coordinate structures of a batch through the native index build, see set_native_index
+        self.set_native_index(bool(kwargs.get("lidar_native_index", False)))
         # optional injected keep-masks {'y1': (N4,C), 'y3': (N2,C)} so a train-mode run can be
         # compared with the oracle (Dropout RNG streams differ between CPU and GPU)
         self.dropout_masks = None
@@ -260,6 +262,16 @@ class SPVCNN(nn.Module):
                 m.ftx_native_eval = bool(on)
         if not on:
             self._native = None
+        return self
+
+    def set_native_index(self, on=True):
+        """Opt-in native index build (include/ftx.h: ftx_spvcnn_index_levels / _maps / _pairs).  With it on, the coordinate structures of a
+        batch on the GPU -- level coordinates, hash tables, the nine kernel maps, the point <-> voxel indices of strides 1, 16 and 4 and
+        the voxelised input features -- come from three library calls with the same two host reads, instead of ~110 launches through
+        Python; with gradients enabled also the sorted segments of the devoxelise backward.  Every array is bit-identical to the per-op
+        build, in eval and in training, and independent of set_native_eval.  CPU tensors and batches the library refuses take the
+        existing path."""
+        self.lidar_native_index = bool(on)
         return self
 
     def _native_executor(self, x):
@@ -410,6 +422,12 @@ class SPVCNN(nn.Module):
         coordinates and kernel maps of the five U-Net levels and (ahead=True) the point <-> voxel index structures of the strides
         the network visits.  Each data-dependent size is read back after a "sync" yield (two per batch: all level sizes, then all
         pair counts), so a scheduler can issue image-branch work instead of waiting for it."""
+        if self.lidar_native_index and torch.is_tensor(x.F) and x.F.is_cuda:
+            from .. import native_index
+            try:
+                return (yield from native_index.index_steps(x, self.pres, self.vres))
+            except native_index.Refused:
+                pass          # refused before anything was launched: the per-op build below
         coords = x.C
         if coords.dtype != torch.float32:
             coords = coords.float()

@@ -567,6 +567,50 @@ int32_t ftx_spvcnn_pv_bytes(void);
 size_t ftx_spvcnn_eval_arena_bytes(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host);
 int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const float *x0, int32_t first_segment, int32_t last_segment, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, void *stream);
 
+/* ---- native index build of the SPVCNN LiDAR branch: from raw points to the batch tables ftx_spvcnn_eval reads ----
+ * Everything of a batch that depends on its coordinates only (SPVCNN._index_steps(ahead=True) in the Python package): the voxel sets of
+ * the five levels (strides 1, 2, 4, 8, 16), their coordinates and hash tables, the nine kernel maps (the 3^3 map of every level, then the
+ * strided 2^3 map between consecutive levels), the point <-> voxel structures at strides 1, 16 and 4 and the voxelised input features.
+ * Two sizes are data dependent, so the build is three calls with a host read between them; no call allocates, synchronises or blocks,
+ * and every argument is checked before the first launch (FTX_EINVAL / FTX_EWORKSPACE with a text in ftx_last_error()).
+ *   A  ftx_spvcnn_index_levels: coords (n, 4) float32 [x, y, z, batch].  Rescales x, y, z by init_res / after_res when the two differ
+ *      (float32: (x * init_res) * (1 / after_res)), floors, and finds every level's voxel set in one sort (ftx_levels_unique).  Queues
+ *      the copy of the 6 level offsets (int32; level l has offsets[l + 1] - offsets[l] voxels) into level_off_pinned and returns.
+ *   B  ftx_spvcnn_index_maps: level_off_host = those 6 values once the copy has arrived; feats (n, c_in) float32, c_in a multiple of 4.
+ *      Builds everything that does not depend on a pair count: per-level coordinates and hash tables; the stride-1 point -> voxel rows,
+ *      counts, sorted segments and the voxelised features x0; nbr, pos and koff of the five 3^3 maps; the four 2^3 maps complete (their
+ *      pair count is n_in); idx / counts / segments / corner rows / trilinear weights at strides 1, 16, 4; with
+ *      with_backward_segments != 0 also the (point, corner) entries sorted by voxel that the devoxelise backward reduces over.  Queues
+ *      the copy of the five 3^3 pair counts (int32) into pair_counts_pinned and returns.  coords, n, init_res, after_res as in phase A.
+ *   C  ftx_spvcnn_index_pairs: pair_counts_host = those 5 values.  Builds pos_t, pair_in and pair_out of the five 3^3 maps and writes
+ *      the host tables rows_host (int64[6]), maps_host (9 map records: the 3^3 maps of strides 1..16, then the 2^3 maps 1->2 .. 8->16)
+ *      and pvs_host (3 pv records: strides 1, 16, 4) in the layouts ftx_spvcnn_eval reads (ftx_spvcnn_map_bytes / ftx_spvcnn_pv_bytes
+ *      per record); *x0 (optional) receives the device pointer of the voxelised features (rows[0], c_in).  level_off_host, c_in and
+ *      with_backward_segments must be the values phase B was given.
+ * Each repeated step (level coordinates + hash-table insert, the neighbour tables of the nine maps and the corner queries, the
+ * validity scan, the pair compaction, the per-stride point queries / segments / weights) is one launch over all its instances.  The
+ * results equal those of the per-level entry points bit for bit.
+ * Memory.  One caller-owned device arena per phase, 256-byte aligned, every region inside 256-byte aligned; each is sized from the values
+ * known when its phase is issued by a host function that needs no GPU (0 and an error text for arguments it refuses), is a multiple of
+ * 256 and never decreases when n, a level size or a pair count grows.  Arena A is read by phases B and C, arena B by phase C; the batch's
+ * structures live in all three, so all three stay allocated while the batch is in use.  The tails of arenas A and B hold the sort and
+ * scan temporaries; the part of them that the sorting library sizes is reserved by a bound and checked against the library's own
+ * figure when the phase is issued (FTX_EWORKSPACE if the bound falls short: nothing is launched).
+ * ftx_spvcnn_index_layout: the byte offsets of every array inside its arena, ftx_spvcnn_index_layout_words() int64 words, for a binding
+ * that wants views of the arrays: a_total, b_total, c_total; arena A: coords (rescaled, n x 4 float), points (floored, n x 4 int32),
+ * uniq (5n int64), first (5n int32), sorted_keys (5 x n int64), order (5 x n int32); arena B: per level {coords, table keys, table
+ * values, table capacity (a count, not an offset)}; x0; per map (9) {nbr, pos, koff}; per 2^3 map (4) {pos_t, pair_in, pair_out}; per
+ * pv (3) {vox_idx, vox_counts, vox_seg_off, devox_idx, devox_weights, devox_bwd_order, devox_bwd_seg_off}; arena C: per 3^3 map (5)
+ * {pos_t, pair_in, pair_out}.  level_off_host / pair_counts_host may be NULL: the arenas that depend on them are reported as 0. */
+int32_t ftx_spvcnn_index_layout_words(void);
+int ftx_spvcnn_index_layout(int64_t n, int32_t c_in, const int32_t *level_off_host, const int32_t *pair_counts_host, int32_t with_backward_segments, int64_t *words_host);
+size_t ftx_spvcnn_index_levels_arena_bytes(int64_t n);
+size_t ftx_spvcnn_index_maps_arena_bytes(int64_t n, int32_t c_in, const int32_t *level_off_host, int32_t with_backward_segments);
+size_t ftx_spvcnn_index_pairs_arena_bytes(int64_t n, const int32_t *level_off_host, const int32_t *pair_counts_host);
+int ftx_spvcnn_index_levels(const float *coords, int64_t n, float init_res, float after_res, void *arena_a, size_t arena_a_bytes, int32_t *level_off_pinned, void *stream);
+int ftx_spvcnn_index_maps(const float *coords, int64_t n, float init_res, float after_res, const float *feats, int32_t c_in, const int32_t *level_off_host, int32_t with_backward_segments, void *arena_a, size_t arena_a_bytes, void *arena_b, size_t arena_b_bytes, int32_t *pair_counts_pinned, void *stream);
+int ftx_spvcnn_index_pairs(int64_t n, int32_t c_in, const int32_t *level_off_host, int32_t with_backward_segments, const int32_t *pair_counts_host, void *arena_a, void *arena_b, size_t arena_b_bytes, void *arena_c, size_t arena_c_bytes, int64_t *rows_host, void *maps_host, void *pvs_host, const float **x0, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

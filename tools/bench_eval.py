@@ -1,5 +1,6 @@
 """Eval-mode forward of the LiDAR-only and the middle-fusion model with the native executor of the LiDAR branch off and on
-(SPVCNN.set_native_eval), profiler off.  Two resident batches alternate, so every per-batch structure is rebuilt in every forward.
+(SPVCNN.set_native_eval), and -- mode `index` -- with the executor AND the native index build on (SPVCNN.set_native_index), profiler
+off.  Two resident batches alternate, so every per-batch structure is rebuilt in every forward.
 
 Per (model, batch, switch) and over `--windows` windows of `--steps` forwards, the switch alternating window by window in one process:
   wall ms / forward   host clock around the window, ending in a device synchronise
@@ -9,8 +10,9 @@ Per (model, batch, switch) and over `--windows` windows of `--steps` forwards, t
                       this one's
   arena / peak bytes  the executor's arena, and torch's peak allocation above the resident state during a window
 usage:
-  python tools/bench_eval.py [--models lidar,middle] [--batches 1,4] [--windows 5] [--steps 20] [--modes off,on]
+  python tools/bench_eval.py [--models lidar,middle] [--batches 1,4] [--windows 5] [--steps 20] [--modes off,on,index]
       --modes off also runs on a checkout that has no executor (the baseline of the comparison)
+      --mark-launches also traces one index build on its own per setting ("... index build" in the count)
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/bench_eval.py --mark-launches   # one marked forward per setting
   python tools/bench_eval.py --count-launches DIR                                                     # kernel launches per forward
 """
@@ -36,7 +38,15 @@ def count_launches(trace_dir):
     for j, what in enumerate(order):
         lo, hi = marks[2 * j], marks[2 * j + 1]
         ours = sum(1 for r in rows[lo + 1:hi] if "ftx" in r["Kernel_Name"] or "spconv" in r["Kernel_Name"] or "bn_" in r["Kernel_Name"])
-        print("%-28s %5d kernel launches per forward (%d with 'ftx' / 'spconv' / 'bn_' in the name)" % (what, hi - lo - 1, ours))
+        print("%-40s %5d kernel launches per forward (%d with 'ftx' / 'spconv' / 'bn_' in the name)" % (what, hi - lo - 1, ours))
+        if what.endswith("index build"):
+            names = {}
+            for r in rows[lo + 1:hi]:
+                k = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").split("<")[0][-40:]
+                names[k] = names.get(k, 0) + 1
+            busy = sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows[lo + 1:hi]) / 1e3
+            span = (int(rows[hi - 1]["End_Timestamp"]) - int(rows[lo + 1]["Start_Timestamp"])) / 1e3 if hi - lo > 1 else 0.0
+            print("    kernels busy %.1f us inside a span of %.1f us: %s" % (busy, span, ", ".join("%s x%d" % kv for kv in sorted(names.items(), key=lambda kv: -kv[1]))))
 
 
 def main():
@@ -75,9 +85,14 @@ def main():
             sys.exit("this checkout has no native executor: run with --modes off")
         lidar_stream = torch.cuda.current_stream() if kind == "lidar" else _branch_streams(dev)[1]
 
+        if "index" in modes and not hasattr(net, "set_native_index"):
+            sys.exit("this checkout has no native index build: run without the mode `index`")
+
         def switch(mode):
             if hasattr(net, "set_native_eval"):
-                net.set_native_eval(mode == "on")
+                net.set_native_eval(mode in ("on", "index"))
+            if hasattr(net, "set_native_index"):
+                net.set_native_index(mode == "index")
 
         for batch in (int(b) for b in a.batches.split(",")):
             datas = [build_inputs(cfg, batch, "kitti", 0, dev, cycle=c)[1] for c in range(2)]
@@ -96,6 +111,13 @@ def main():
                         torch.cuda.synchronize()
                         marker.cosh_()
                         order.append("%s batch %d %s" % (kind, batch, mode))
+                        # the index build alone (coordinate structures of one batch, both host reads included)
+                        from fusiontransformer_amd.sparse import drain
+                        marker.cosh_()
+                        drain(net._index_steps(datas[0]["lidar"], ahead=True))
+                        torch.cuda.synchronize()
+                        marker.cosh_()
+                        order.append("%s batch %d %s index build" % (kind, batch, mode))
                     continue
                 res = {m: {"wall": [], "issue": [], "lidar": [], "peak": 0} for m in modes}
                 for w in range(a.windows):
@@ -121,7 +143,7 @@ def main():
                         r["peak"] = max(r["peak"], torch.cuda.max_memory_allocated() - base)
                 for mode in modes:
                     r = res[mode]
-                    arena = sum(b.shape[0] for b in net._native.arenas.values()) if (mode == "on" and getattr(net, "_native", None)) else 0
+                    arena = sum(b.shape[0] for b in net._native.arenas.values()) if (mode != "off" and getattr(net, "_native", None)) else 0
                     fmt = lambda v: "%.3f (%.3f..%.3f)" % (statistics.median(v), min(v), max(v))
                     print("%-6s batch %d native %-3s  wall %s ms  issue %s ms  lidar stream %s ms  arena %.1f MiB  torch peak %.1f MiB" % (
                         kind, batch, mode, fmt(r["wall"]), fmt(r["issue"]), fmt(r["lidar"]), arena / 2 ** 20, r["peak"] / 2 ** 20), flush=True)

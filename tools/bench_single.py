@@ -1,6 +1,7 @@
 """Step time of the single-modality baselines (LidarSeg, ImageSegBilinear) and time of the single-head loss kernel.
 
 usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/single_modality_steps.json]
+       python tools/bench_single.py --native-index-ab [--steps 20]     # LidarSeg steps, native index build off / on, alternating windows
 
 * Steps: TrainStep on synthetic KITTI-shaped frames (data/synth.make_batch), two alternating resident batches as bench.py
   uses, batch 4 and batch 1, HIP events around the timed loop after the warm-up, profiler off.  LidarSeg runs with the index
@@ -64,6 +65,43 @@ def step_time(kind, batch, steps, warmup):
     assert loss == loss, "the loss is NaN"
     return {"model": kind, "batch": batch, "points_per_batch": list(points), "steps": steps, "warmup": warmup, "ms_per_step": ms,
             "frames_per_s": batch * 1e3 / ms, "last_loss": loss}
+
+
+def native_index_ab(batch, steps, warmup, windows=5):
+    """LidarSeg step time with the native index build (SPVCNN.set_native_index) off and on: two models from one seed in one process,
+    windows of `steps` steps alternating between them; median (min..max) ms per step."""
+    from fusiontransformer_amd import config
+    from fusiontransformer_amd.models.build import build_model
+    from fusiontransformer_amd.trainer import TrainStep
+    cfg = config.lidar_cfg()
+    _, res = zip(*[_inputs(batch, cycle, "cuda") for cycle in (0, 1)])
+    arms = {}
+    for mode in ("off", "on"):
+        torch.manual_seed(0)
+        model = build_model(cfg)[0].cuda().train()
+        model.backbone.set_native_index(mode == "on")
+        arms[mode] = TrainStep(cfg, model)
+
+    def window(step, n):
+        seq = [res[i % 2] for i in range(n + 1)]
+        for x in seq:
+            x["lidar"].prepared = None
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(n):
+            step(seq[i], next_batch=seq[i + 1])
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    for step in arms.values():
+        window(step, warmup)
+    ms = {m: [] for m in arms}
+    for w in range(windows):
+        for mode in (("off", "on") if w % 2 == 0 else ("on", "off")):
+            ms[mode].append(window(arms[mode], steps))
+    return {"model": "LidarSeg", "batch": batch, "steps_per_window": steps, "windows": windows,
+            "ms_per_step": {m: {"median": statistics.median(v), "min": min(v), "max": max(v)} for m, v in ms.items()}}
 
 
 def kernel_times():
@@ -137,9 +175,14 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "single_modality_steps.json"))
+    ap.add_argument("--native-index-ab", action="store_true", help="only: LidarSeg step time with SPVCNN.set_native_index off / on, batch 1 and 4")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_single: needs a GPU (there is no fallback)")
+    if args.native_index_ab:
+        for batch in (1, 4):
+            print(json.dumps(native_index_ab(batch, args.steps, args.warmup)), flush=True)
+        return
     if args.steps < 50:
         raise SystemExit("bench_single: at least 50 timed steps")
     result = {"what": "single-modality train steps on synthetic KITTI-shaped frames (two alternating resident batches, HIP events, "
