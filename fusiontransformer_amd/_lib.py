@@ -135,6 +135,12 @@ SIGNATURES = {
     "ftx_spvcnn_pv_bytes": (_i32, []),
     "ftx_spvcnn_eval_arena_bytes": (_sz, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
     "ftx_spvcnn_eval": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ftx_rows_split": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "ftx_spvcnn_train_layer_bytes": (_i32, []),
+    "ftx_spvcnn_train_pv_bytes": (_i32, []),
+    "ftx_spvcnn_train_arena_bytes": (_sz, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "ftx_spvcnn_train_fwd": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ftx_spvcnn_train_bwd": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
     "ftx_spvcnn_index_layout_words": (_i32, []),
     "ftx_spvcnn_index_layout": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _vp]),
     "ftx_spvcnn_index_levels_arena_bytes": (_sz, [_i64]),

@@ -55,15 +55,8 @@ extern "C" int ftx_rows_add(const float *a, const float *b, int64_t n, int32_t c
 // ---------------------------------------------------------------- tables (layouts documented in include/ftx.h)
 namespace {
 
-struct Layer {
-  const float *weight, *bias, *gamma, *beta, *mean, *var;
-  int32_t ca, co, kvol, stride, transposed, bf16;
-  float eps;
-  int32_t kind;
-};
-struct Op {
-  int32_t kind, segment, layer, map, src, src2, dst, relu, level, channels, reserved0, reserved1;
-};
+using Layer = ftx::SpvcnnLayer;   // ftx_spvcnn_tables.h: shared with the training executor
+using Op = ftx::SpvcnnOp;
 using Map = ftx::SpvcnnMap;   // ftx_spvcnn_tables.h: shared with the index builder that writes them
 using PV = ftx::SpvcnnPV;
 static_assert(sizeof(Layer) == 80 && sizeof(Op) == 48 && sizeof(Map) == 80 && sizeof(PV) == 64, "table records are packed");

@@ -1,5 +1,6 @@
-// Batch-table records of the SPVCNN entry points (layouts documented in include/ftx.h): read by ftx_spvcnn_eval (ftx_exec.hip), written by
-// ftx_spvcnn_index_pairs (ftx_native_index.hip).  ftx_spvcnn_map_bytes / ftx_spvcnn_pv_bytes report their sizes.
+// Table records of the SPVCNN entry points (layouts documented in include/ftx.h).  The batch tables (map, pv) are read by ftx_spvcnn_eval
+// (ftx_exec.hip) and ftx_spvcnn_train_fwd / _bwd (ftx_exec_train.hip) and written by ftx_spvcnn_index_pairs (ftx_native_index.hip); the model
+// table (layer), the program (op) and the train-only side tables are the two executors'.  ftx_spvcnn_*_bytes report their sizes.
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +17,25 @@ struct SpvcnnPV {
   int64_t n_vox;
   int32_t level, reserved;
 };
-static_assert(sizeof(SpvcnnMap) == 80 && sizeof(SpvcnnPV) == 64, "table records are packed");
+struct SpvcnnLayer {
+  const float *weight, *bias, *gamma, *beta, *mean, *var;
+  int32_t ca, co, kvol, stride, transposed, bf16;
+  float eps;
+  int32_t kind;
+};
+struct SpvcnnOp {
+  int32_t kind, segment, layer, map, src, src2, dst, relu, level, channels, reserved0, reserved1;
+};
+// train-only side tables, parallel to the model table and to the pv table
+struct SpvcnnTrainLayer {
+  float *dweight, *dbias, *dgamma, *dbeta;
+  float momentum;
+  int32_t reserved;
+};
+struct SpvcnnTrainPV {
+  const int32_t *devox_order, *devox_seg_off;
+};
+static_assert(sizeof(SpvcnnMap) == 80 && sizeof(SpvcnnPV) == 64 && sizeof(SpvcnnLayer) == 80 && sizeof(SpvcnnOp) == 48, "table records are packed");
+static_assert(sizeof(SpvcnnTrainLayer) == 40 && sizeof(SpvcnnTrainPV) == 16, "table records are packed");
 
 }  // namespace ftx

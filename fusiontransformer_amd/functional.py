@@ -1045,6 +1045,16 @@ def rows_concat(a, b):
     return out
 
 
+def rows_split(x, ca):
+    """(x[:, :ca], x[:, ca:]) of (n, ca + cb) float32 rows as two contiguous matrices in one launch (ftx_rows_split, the backward of
+    rows_concat; channel counts multiples of 4)."""
+    x = req(x, F32, "rows_split x", 2)
+    n, cb = x.shape[0], x.shape[1] - int(ca)
+    a, b = _empty((n, int(ca)), F32, x), _empty((n, cb), F32, x)
+    check(_lib.load().ftx_rows_split(ptr(x), n, int(ca), cb, ptr(a), ptr(b), stream()), "ftx_rows_split")
+    return a, b
+
+
 def rows_add(a, b):
     """a + b of two (n, c) float32 row matrices (ftx_rows_add; c a multiple of 4)."""
     a, b = req(a, F32, "rows_add a", 2), req(b, F32, "rows_add b", 2)

@@ -228,6 +228,9 @@ class SPVCNN(nn.Module):
         self.set_native_eval(bool(kwargs.get("lidar_native_eval", False)))
         # cfg.MODEL.lidar_native_index: the coordinate structures of a batch through the native index build, see set_native_index
         self.set_native_index(bool(kwargs.get("lidar_native_index", False)))
+        # cfg.MODEL.lidar_native_train: the training forward and backward through the native executor, see set_native_train
+        self._native_tr = None
+        self.set_native_train(bool(kwargs.get("lidar_native_train", False)))
         # optional injected keep-masks {'y1': (N4,C), 'y3': (N2,C)} so a train-mode run can be
         # compared with the oracle (Dropout RNG streams differ between CPU and GPU)
         self.dropout_masks = None
@@ -273,6 +276,58 @@ class SPVCNN(nn.Module):
         existing path."""
         self.lidar_native_index = bool(on)
         return self
+
+    def set_native_train(self, on=True):
+        """Opt-in native training executor (include/ftx.h: ftx_spvcnn_train_fwd / _bwd).  With it on, a forward in training mode, with
+        gradients enabled and features on the GPU, builds the batch's coordinate structures as before and then runs the network -- first
+        convolution of the stem to z3.F -- as five segments, each ONE autograd node whose forward and backward are one library call
+        (stem | encoder | z1 -> y1 | up1, up2, z2 -> y3 | up3, up4, z3: a segment ends where a Dropout follows, which stays torch's),
+        over one arena per forward instead of ~200 nodes through Python.  Same kernels in the same order: logits, every gradient and
+        every running statistic are bit-identical to the switch being off.  Independent of set_native_eval, set_native_index and
+        set_bf16.  In eval mode, without gradients, on CPU tensors, with a frozen parameter, for a module tree the emitter refuses or
+        a batch the library refuses, the existing path runs exactly as with the switch off."""
+        self.lidar_native_train = bool(on)
+        if not on:
+            self._native_tr = None
+        return self
+
+    def _native_trainer(self, x):
+        """The training executor when this forward is one it runs (see set_native_train), else None."""
+        if not self.lidar_native_train or not self.training or not torch.is_grad_enabled() or not torch.is_tensor(x.F) or not x.F.is_cuda \
+                or x.F.requires_grad:
+            return None
+        if self._native_tr is None:
+            from .. import native_train
+            try:
+                self._native_tr = native_train.NativeTrain(self)
+            except native_train.Unsupported:
+                self._native_tr = False
+        if not self._native_tr or not self._native_tr.trainable():
+            return None
+        return self._native_tr
+
+    def _native_train_steps(self, run, z, x0, fuse_early, fuse_middle):
+        """_backbone_steps from "voxelized" on through the training executor: one autograd node per segment, Dropout between them."""
+        z0 = run.segment(0, x0.F)
+        early = middle = None
+        if fuse_early is not None:
+            yield "need_early"
+            early = fuse_early() if callable(fuse_early) else fuse_early
+        yield "stem"
+        z1 = run.segment(1, z0, early)
+        if fuse_middle is not None:
+            yield "need_middle"
+            middle = fuse_middle() if callable(fuse_middle) else fuse_middle
+        yield "stage4"
+        y1 = self._drop(run.segment(2, z1, middle), "y1")
+        y3 = self._drop(run.segment(3, y1), "y3")
+        yield "up2"
+        feats = run.segment(4, y3)
+        yield "up4"
+        cm = x0.cm
+        levels = {"x%d" % l: SparseTensor(None, cm.coords[s], s) for l, s in enumerate((1, 2, 4, 8, 16)) if l}
+        self.last_index = dict(x0=x0, z=z, **levels)
+        return feats
 
     def _native_executor(self, x):
         """The executor when this forward is one it runs (see set_native_eval), else None."""
@@ -351,6 +406,7 @@ class SPVCNN(nn.Module):
         ex = self._native_executor(x)
         if ex is not None:
             return (yield from self._native_steps(ex, x, fuse_early, fuse_middle))
+        trainer = self._native_trainer(x)
         prepared = getattr(x, "prepared", None)
         if isinstance(prepared, PendingIndex):
             # started ahead of this forward (prepare(wait=False)) and parked at a host read: finish it here, on its own stream
@@ -363,8 +419,16 @@ class SPVCNN(nn.Module):
             z, x0 = prepared.take(torch.cuda.current_stream() if x.F.is_cuda else None)
             x.prepared = None
         else:
-            z, x0 = yield from self._index_steps(x)
+            z, x0 = yield from self._index_steps(x, ahead=trainer is not None)
         yield "voxelized"
+        if trainer is not None:
+            from ..native_train import Refused
+            try:
+                run = trainer.begin(z, x0)
+            except Refused:
+                run = None        # refused before anything was launched: the per-op path below
+            if run is not None:
+                return (yield from self._native_train_steps(run, z, x0, fuse_early, fuse_middle))
         x0 = self._stem(x0)
         z0 = voxel_to_point(x0, z, nearest=False)
         if fuse_early is not None:

@@ -101,7 +101,7 @@ class Program:
         if ca % 4 or co % 4 or (ks == 1 and max(ca, co) > 512):
             raise Unsupported(f"Conv3d {ca} -> {co}: the kernels take channel counts that are multiples of 4")
         self.layers.append(dict(kind=LAYER_CONV_BN, refs=_refs((conv, "kernel"), None, bn), ca=ca, co=co,
-                                kvol=conv.k, stride=s, transposed=int(bool(conv.t)), eps=float(bn.eps), module=conv))
+                                kvol=conv.k, stride=s, transposed=int(bool(conv.t)), eps=float(bn.eps), module=conv, bn=bn))
         return self._op(OP_CONV_BN, seg, src, out_level, co, layer=len(self.layers) - 1, map_=map_, src2=residual, relu=relu), out_level
 
     def linear_bn_relu(self, seg, seq, src, dst=None):
@@ -114,7 +114,7 @@ class Program:
         if ca % 4 or co % 4 or max(ca, co) > 512:
             raise Unsupported(f"Linear {ca} -> {co}: the rows kernel takes multiples of 4 up to 512")
         self.layers.append(dict(kind=LAYER_LINEAR_BN, refs=_refs((lin, "weight"), (lin, "bias") if lin.bias is not None else None, bn), ca=ca, co=co,
-                                kvol=0, stride=1, transposed=0, eps=float(bn.eps), module=lin))
+                                kvol=0, stride=1, transposed=0, eps=float(bn.eps), module=lin, bn=bn))
         return self._op(OP_LINEAR_BN, seg, src, POINTS, co, layer=len(self.layers) - 1, relu=True, dst=dst)
 
     def block(self, seg, blk, src, level):
@@ -132,49 +132,53 @@ class Program:
         return np.array(self.ops, dtype=OP)
 
 
-def emit_program(net) -> Program:
-    """The eval forward of SPVCNN._backbone_steps from "voxelized" on, op by op in the order that method issues them."""
+def emit_program(net, segments=(SEG_STEM, SEG_ENCODER, SEG_DECODER, SEG_DECODER, SEG_DECODER)) -> Program:
+    """The forward of SPVCNN._backbone_steps from "voxelized" on, op by op in the order that method issues them.  `segments`: the
+    segment number of the stem, of the encoder, of the voxelise that feeds the first Dropout (with the middle-fusion add in front of
+    it), of the decoder up to the voxelise that feeds the second Dropout, and of the rest.  Dropout is the identity in eval mode, so the
+    eval program runs the last three as one; the training program (native_train.py) ends a segment at each."""
     P = Program()
+    s_stem, s_enc, s_y1, s_dec, s_rest = segments
     cs = net.cs
     pv = {s: i for i, s in enumerate(PV_STRIDES)}
     # ---- stem, z0
-    x0, _ = P.conv_bn(SEG_STEM, net.stem[0], net.stem[1], SLOT_INPUT, 0)
-    x0, _ = P.conv_bn(SEG_STEM, net.stem[3], net.stem[4], x0, 0)
-    z0 = P._op(OP_DEVOXELIZE, SEG_STEM, x0, POINTS, cs[0], map_=pv[1])
+    x0, _ = P.conv_bn(s_stem, net.stem[0], net.stem[1], SLOT_INPUT, 0)
+    x0, _ = P.conv_bn(s_stem, net.stem[3], net.stem[4], x0, 0)
+    z0 = P._op(OP_DEVOXELIZE, s_stem, x0, POINTS, cs[0], map_=pv[1])
     # ---- encoder
-    P._op(OP_ADD_EXT, SEG_ENCODER, z0, POINTS, cs[0], layer=0, dst=z0)
-    cur = P._op(OP_VOXELIZE, SEG_ENCODER, z0, 0, cs[0], map_=pv[1])
+    P._op(OP_ADD_EXT, s_enc, z0, POINTS, cs[0], layer=0, dst=z0)
+    cur = P._op(OP_VOXELIZE, s_enc, z0, 0, cs[0], map_=pv[1])
     level, skips = 0, [(x0, cs[0])]
     for i, stage in enumerate((net.stage1, net.stage2, net.stage3, net.stage4)):
-        cur, level = P.block(SEG_ENCODER, stage[0], cur, level)
-        cur, level = P.residual(SEG_ENCODER, stage[1], cur, level)
-        cur, level = P.residual(SEG_ENCODER, stage[2], cur, level)
+        cur, level = P.block(s_enc, stage[0], cur, level)
+        cur, level = P.residual(s_enc, stage[1], cur, level)
+        cur, level = P.residual(s_enc, stage[2], cur, level)
         skips.append((cur, cs[i + 1]))
     x4 = cur
-    z1v = P._op(OP_DEVOXELIZE, SEG_ENCODER, x4, POINTS, cs[4], map_=pv[16])
-    t = P.linear_bn_relu(SEG_ENCODER, net.point_transforms[0], z0)
-    z1 = P._op(OP_ADD, SEG_ENCODER, z1v, POINTS, cs[4], src2=t)
+    z1v = P._op(OP_DEVOXELIZE, s_enc, x4, POINTS, cs[4], map_=pv[16])
+    t = P.linear_bn_relu(s_enc, net.point_transforms[0], z0)
+    z1 = P._op(OP_ADD, s_enc, z1v, POINTS, cs[4], src2=t)
     # ---- decoder
-    P._op(OP_ADD_EXT, SEG_DECODER, z1, POINTS, cs[4], layer=1, dst=z1)
-    cur = P._op(OP_VOXELIZE, SEG_DECODER, z1, 4, cs[4], map_=pv[16])
+    P._op(OP_ADD_EXT, s_y1, z1, POINTS, cs[4], layer=1, dst=z1)
+    cur = P._op(OP_VOXELIZE, s_y1, z1, 4, cs[4], map_=pv[16])
 
-    def up(mod, cur, level, skip, o):
-        cur, level = P.block(SEG_DECODER, mod[0], cur, level)
-        cur = P._op(OP_CONCAT, SEG_DECODER, cur, level, o + skip[1], src2=skip[0])
-        cur, level = P.residual(SEG_DECODER, mod[1][0], cur, level)
-        return P.residual(SEG_DECODER, mod[1][1], cur, level)
+    def up(seg, mod, cur, level, skip, o):
+        cur, level = P.block(seg, mod[0], cur, level)
+        cur = P._op(OP_CONCAT, seg, cur, level, o + skip[1], src2=skip[0])
+        cur, level = P.residual(seg, mod[1][0], cur, level)
+        return P.residual(seg, mod[1][1], cur, level)
 
-    cur, level = up(net.up1, cur, 4, skips[3], cs[5])
-    cur, level = up(net.up2, cur, level, skips[2], cs[6])
-    z2v = P._op(OP_DEVOXELIZE, SEG_DECODER, cur, POINTS, cs[6], map_=pv[4])
-    t = P.linear_bn_relu(SEG_DECODER, net.point_transforms[1], z1)
-    z2 = P._op(OP_ADD, SEG_DECODER, z2v, POINTS, cs[6], src2=t)
-    cur = P._op(OP_VOXELIZE, SEG_DECODER, z2, 2, cs[6], map_=pv[4])
-    cur, level = up(net.up3, cur, 2, skips[1], cs[7])
-    cur, level = up(net.up4, cur, level, skips[0], cs[8])
-    z3v = P._op(OP_DEVOXELIZE, SEG_DECODER, cur, POINTS, cs[8], map_=pv[1])
-    t = P.linear_bn_relu(SEG_DECODER, net.point_transforms[2], z2)
-    P._op(OP_ADD, SEG_DECODER, z3v, POINTS, cs[8], src2=t, dst=SLOT_OUTPUT)
+    cur, level = up(s_dec, net.up1, cur, 4, skips[3], cs[5])
+    cur, level = up(s_dec, net.up2, cur, level, skips[2], cs[6])
+    z2v = P._op(OP_DEVOXELIZE, s_dec, cur, POINTS, cs[6], map_=pv[4])
+    t = P.linear_bn_relu(s_dec, net.point_transforms[1], z1)
+    z2 = P._op(OP_ADD, s_dec, z2v, POINTS, cs[6], src2=t)
+    cur = P._op(OP_VOXELIZE, s_dec, z2, 2, cs[6], map_=pv[4])
+    cur, level = up(s_rest, net.up3, cur, 2, skips[1], cs[7])
+    cur, level = up(s_rest, net.up4, cur, level, skips[0], cs[8])
+    z3v = P._op(OP_DEVOXELIZE, s_rest, cur, POINTS, cs[8], map_=pv[1])
+    t = P.linear_bn_relu(s_rest, net.point_transforms[2], z2)
+    P._op(OP_ADD, s_rest, z3v, POINTS, cs[8], src2=t, dst=SLOT_OUTPUT)
     P.early_channels, P.middle_channels, P.out_channels = cs[0], cs[4], cs[8]
     if level != 0 or P.n_slots > 256:
         raise Unsupported("unexpected topology")

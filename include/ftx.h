@@ -567,6 +567,47 @@ int32_t ftx_spvcnn_pv_bytes(void);
 size_t ftx_spvcnn_eval_arena_bytes(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host);
 int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const float *x0, int32_t first_segment, int32_t last_segment, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, void *stream);
 
+/* ---- native training executor of the SPVCNN LiDAR branch (models/spvcnn.py:191-233 under model.train(), gradients enabled) ----
+ * ftx_spvcnn_train_fwd issues the train-mode forward of the segments [first_segment, last_segment] of the program ftx_spvcnn_eval
+ * takes, ftx_spvcnn_train_bwd their backward: the program in reverse, for every op what its autograd node issues on the per-op path and
+ * in that node's order (CONV_BN: ftx_bn_train_bwd, the data gradient, ftx_spconv_pairs_wgrad; dense layers: ftx_bn_train_bwd,
+ * ftx_rows_gemm, the dense ftx_spconv_pairs_wgrad, ftx_colsum; ftx_voxelize_bwd, ftx_devoxelize_bwd(_sorted); ftx_rows_split for CONCAT).
+ * The forward runs the statistics-producing forms (ftx_spconv_reduce_stats / ftx_spconv_ostat with partials + ftx_bn_train_fwd_totals,
+ * else ftx_bn_train_fwd) and updates the running statistics through them.  Results are bit-identical to the per-op path.
+ *
+ * ftx_rows_split: a (n, ca), b (n, cb) = the two column blocks of in (n, ca + cb), the backward of ftx_rows_concat; channels multiples
+ * of 4, 16-byte accesses, n = 0 is a no-op.
+ *
+ * Tables: layer, op, map, pv, rows_host and routes_host as ftx_spvcnn_eval reads them (records unchanged), except that segments are
+ * numbered 0 .. 7 without a gap (Dropout is the caller's: a segment ends where one follows) and every level needs at least one row.
+ *   grad_routes_host: int32[n_ops], for every CONV_BN op with kvol > 1 whose input needs a gradient how the data gradient runs:
+ *     FTX_SPVCNN_ROUTE_EMPTY (zero fill), _DIRECT or _PAIRS, the caller's choice as in routes_host (functional._conv_route(grad=True)).
+ *     An op that reads FTX_SPVCNN_SLOT_INPUT computes no data gradient.
+ *   train layer (parallel to the model table; ftx_spvcnn_train_layer_bytes): float *dweight, *dbias (NULL without a bias), *dgamma,
+ *     *dbeta -- where the backward writes the layer's parameter gradients, in the parameters' shapes; float momentum; int32 reserved.
+ *   train pv (parallel to the pv table; ftx_spvcnn_train_pv_bytes): const int32 *devox_order (8 n), *devox_seg_off (n_vox + 1), the sorted
+ *     segments of the devoxelise backward [ftx_segment_build]; NULL: ftx_devoxelize_bwd.  A pv record with NULL vox_order runs
+ *     ftx_voxelize_fwd.
+ * Buffers.  seg_in stands for the input of first_segment: the voxelised features x0 for segment 0, else the buffer the previous
+ * segment returned in *seg_out or -- where only first_segment reads it -- a replacement of it (what Dropout returned); the backward
+ * of a segment takes the same seg_in as its forward.  *seg_out receives the address of last_segment's result: inside the arena, or
+ * `out` (rows[5] x channels, the caller's) for the last segment of the program.  grad_out is the gradient of that result;
+ * *grad_in receives the address, inside the arena, of the gradient of seg_in (NULL for segment 0), which is also the gradient of the
+ * fusion addend a segment opened with.  A slot read by two ops has its two gradients added by one ftx_rows_add; a program in which a
+ * slot would receive more than two, or in which an operand of ADD has another reader, is FTX_EINVAL.
+ * Arena.  ftx_spvcnn_train_arena_bytes is a host function of the tables alone with the properties of ftx_spvcnn_eval_arena_bytes.  One
+ * region per slot, per slot gradient, per layer output and per layer statistics, none shared, plus one shared region for per-op
+ * temporaries: nothing the backward reads is written again while the caller keeps the arena.  The caller keeps it, unchanged, from the
+ * first forward call of a step to its last backward call and runs the backward of the segments in descending order.
+ * Every table is validated before the first launch.  No host synchronisation, no allocation, no state kept beyond the call; the
+ * stream's ticket buffer (ftx_stream_scratch_attach) is the caller's as for the per-op entry points. */
+int ftx_rows_split(const float *in, int64_t n, int32_t ca, int32_t cb, float *a, float *b, void *stream);
+int32_t ftx_spvcnn_train_layer_bytes(void);
+int32_t ftx_spvcnn_train_pv_bytes(void);
+size_t ftx_spvcnn_train_arena_bytes(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host);
+int ftx_spvcnn_train_fwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, float **seg_out, void *stream);
+int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, const void *train_pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in, void *stream);
+
 /* ---- native index build of the SPVCNN LiDAR branch: from raw points to the batch tables ftx_spvcnn_eval reads ----
  * Everything of a batch that depends on its coordinates only (SPVCNN._index_steps(ahead=True) in the Python package): the voxel sets of
  * the five levels (strides 1, 2, 4, 8, 16), their coordinates and hash tables, the nine kernel maps (the 3^3 map of every level, then the

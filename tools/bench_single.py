@@ -2,6 +2,8 @@
 
 usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/single_modality_steps.json]
        python tools/bench_single.py --native-index-ab [--steps 20]     # LidarSeg steps, native index build off / on, alternating windows
+       python tools/bench_single.py --native-train-ab [--steps 20] [--ab-model LidarSeg|middle]   # the same for the training executor
+       python tools/bench_single.py --native-train-steps on|off --steps N     # N untimed batch-1 steps, to count launches under a kernel trace
 
 * Steps: TrainStep on synthetic KITTI-shaped frames (data/synth.make_batch), two alternating resident batches as bench.py
   uses, batch 4 and batch 1, HIP events around the timed loop after the warm-up, profiler off.  LidarSeg runs with the index
@@ -67,6 +69,77 @@ def step_time(kind, batch, steps, warmup):
             "frames_per_s": batch * 1e3 / ms, "last_loss": loss}
 
 
+def _graph_nodes(t):
+    """Number of autograd nodes under tensor t."""
+    seen, todo = set(), [t.grad_fn]
+    while todo:
+        f = todo.pop()
+        if f is not None and f not in seen:
+            seen.add(f)
+            todo += [g for g, _ in f.next_functions]
+    return len(seen)
+
+
+def _switch_ab(switch, batch, steps, warmup, windows=5, model_kind="LidarSeg"):
+    """Step time with one switch of the SPVCNN (`set_<switch>`) off and on: two models from one seed in one process, windows of `steps`
+    steps alternating between them; median (min..max) ms per step, and per arm `host_issue_ms` (wall clock of the loop before the
+    synchronise, per step: an UPPER bound on the issue time, since it includes the blocking host reads of an index build that the
+    prefetch did not finish), the autograd nodes under the LiDAR logits and the peak of torch's allocator above what was resident."""
+    import time
+    from fusiontransformer_amd import config
+    from fusiontransformer_amd.models.build import build_model
+    from fusiontransformer_amd.trainer import TrainStep
+    cfg = config.lidar_cfg() if model_kind == "LidarSeg" else config.fusion_cfg(model_kind)
+    _, res = zip(*[_inputs(batch, cycle, "cuda") for cycle in (0, 1)])
+    arms, nets = {}, {}
+    for mode in ("off", "on"):
+        torch.manual_seed(0)
+        model = build_model(cfg)[0].cuda().train()
+        nets[mode] = model.backbone if model_kind == "LidarSeg" else model.lidar_backbone
+        getattr(nets[mode], "set_" + switch)(mode == "on")
+        arms[mode] = TrainStep(cfg, model)
+    info = {m: {} for m in arms}
+
+    def window(mode, n):
+        step = arms[mode]
+        seq = [res[i % 2] for i in range(n + 1)]
+        for x in seq:
+            x["lidar"].prepared = None
+        torch.cuda.synchronize()
+        resident = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        for i in range(n):
+            preds = step(seq[i], next_batch=seq[i + 1])
+        e1.record()
+        host = (time.perf_counter() - t0) * 1e3 / n
+        torch.cuda.synchronize()
+        info[mode].setdefault("host_issue_ms", []).append(host)
+        info[mode]["autograd_nodes"] = _graph_nodes(preds["lidar_seg_logit"])
+        info[mode]["peak_above_resident_bytes"] = int(torch.cuda.max_memory_allocated() - resident)
+        return e0.elapsed_time(e1) / n
+
+    for mode in arms:
+        window(mode, warmup)
+        info[mode]["host_issue_ms"] = []
+    ms = {m: [] for m in arms}
+    for w in range(windows):
+        for mode in (("off", "on") if w % 2 == 0 else ("on", "off")):
+            ms[mode].append(window(mode, steps))
+    spread = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    out = {"model": model_kind, "switch": switch, "batch": batch, "steps_per_window": steps, "windows": windows,
+           "ms_per_step": {m: spread(v) for m, v in ms.items()}}
+    for m in arms:
+        out[m] = dict(info[m], host_issue_ms=spread(info[m]["host_issue_ms"]))
+    tr = getattr(nets["on"], "_native_tr", None)
+    if switch == "native_train" and tr:
+        out["on"]["arena_bytes"] = int(tr.last_arena_bytes)
+    out["every_on_window_beats_every_off_window"] = bool(max(ms["on"]) < min(ms["off"]))
+    return out
+
+
 def native_index_ab(batch, steps, warmup, windows=5):
     """LidarSeg step time with the native index build (SPVCNN.set_native_index) off and on: two models from one seed in one process,
     windows of `steps` steps alternating between them; median (min..max) ms per step."""
@@ -102,6 +175,29 @@ def native_index_ab(batch, steps, warmup, windows=5):
             ms[mode].append(window(arms[mode], steps))
     return {"model": "LidarSeg", "batch": batch, "steps_per_window": steps, "windows": windows,
             "ms_per_step": {m: {"median": statistics.median(v), "min": min(v), "max": max(v)} for m, v in ms.items()}}
+
+
+def native_train_ab(batch, steps, warmup, windows=5, model_kind="LidarSeg"):
+    """Step time with the native training executor (SPVCNN.set_native_train) off and on."""
+    return _switch_ab("native_train", batch, steps, warmup, windows, model_kind)
+
+
+def native_train_steps(mode, steps):
+    """`steps` untimed LidarSeg steps at batch 1 with the training executor on / off: run under a kernel trace with two step counts, the
+    difference of the two launch counts is the launches of the extra steps."""
+    from fusiontransformer_amd import config
+    from fusiontransformer_amd.models.build import build_model
+    from fusiontransformer_amd.trainer import TrainStep
+    cfg = config.lidar_cfg()
+    torch.manual_seed(0)
+    model = build_model(cfg)[0].cuda().train()
+    model.backbone.set_native_train(mode == "on")
+    step = TrainStep(cfg, model)
+    _, res = zip(*[_inputs(1, cycle, "cuda") for cycle in (0, 1)])
+    for i in range(steps):
+        step(res[i % 2], next_batch=res[(i + 1) % 2])
+    torch.cuda.synchronize()
+    return {"native_train": mode, "steps": steps, "last_loss": next(iter(step.last.values())).item()}
 
 
 def kernel_times():
@@ -176,9 +272,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "single_modality_steps.json"))
     ap.add_argument("--native-index-ab", action="store_true", help="only: LidarSeg step time with SPVCNN.set_native_index off / on, batch 1 and 4")
+    ap.add_argument("--native-train-ab", action="store_true", help="only: step time with SPVCNN.set_native_train off / on, batch 1 and 4")
+    ap.add_argument("--ab-model", default="LidarSeg", choices=["LidarSeg", "middle"], help="the model of --native-train-ab")
+    ap.add_argument("--native-train-steps", choices=["on", "off"], help="only: --steps untimed LidarSeg batch-1 steps with the switch on / off")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_single: needs a GPU (there is no fallback)")
+    if args.native_train_ab:
+        for batch in (1, 4):
+            print(json.dumps(native_train_ab(batch, args.steps, args.warmup, model_kind=args.ab_model)), flush=True)
+        return
+    if args.native_train_steps:
+        print(json.dumps(native_train_steps(args.native_train_steps, args.steps)), flush=True)
+        return
     if args.native_index_ab:
         for batch in (1, 4):
             print(json.dumps(native_index_ab(batch, args.steps, args.warmup)), flush=True)
