@@ -14,10 +14,9 @@
 // The reduction index of the first products is permuted (lane half h takes d = 8t+4h+s) so operand
 // fragments are one ds_read_b128 / one 16-byte global load per 4 MFMAs.
 #include "ftx_common.h"
+#include "ftx_mfma.h"
 
 using namespace ftx;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int HD = 64;          // head dim (fixed)
 constexpr int TS = 68;          // LDS row stride in floats (16-byte aligned, conflict-free b128)
@@ -583,9 +582,6 @@ extern "C" int ftx_attn_bwd(const float *qkv, const float *out, const float *gra
 //              of X, converted pairwise, are k-step s with element j <-> row 16s + 8(j>>2) + 4h + (j&3) of X, so the A element j is read
 //              from those tokens: two ds_read_b64.
 // =======================================================================================
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int RS = 72;   // row image stride in bf16 (144 B: 16-byte aligned, conflict-free ds_read_b128)
 constexpr int CS = 36;   // col image stride in bf16 (72 B: 8-byte aligned, conflict-free ds_read_b64 over 32 lanes)
 constexpr int IMG = 32 * RS;   // bf16 per image (32 * RS == 64 * CS)
@@ -616,9 +612,6 @@ __device__ inline bf16x8 acc_frag(const f32x16 &x, int s) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) r[j] = (__bf16)x[8 * s + j];
   return r;
-}
-__device__ inline f32x16 mfma_bf16(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 // acc[row][col=lane] += sum_d RowImg[row][d] * frag[d]
 __device__ inline void mfma_rowimg_x_frag(const __bf16 *img, int l31, int h, const bf16x8 (&frag)[4], f32x16 &acc) {

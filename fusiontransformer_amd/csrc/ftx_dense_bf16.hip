@@ -12,31 +12,20 @@
 // both fragments of a 16-wide k-step, read with one ds_read_b128 from a bf16 LDS image whose rows are k-contiguous.  mfma(F1, F2)
 // leaves C[row of F1][row of F2] with F2's row on the lane and four consecutive F1 rows in accumulator registers 4q..4q+3
 // ((g&3) + 8(g>>2) + 4h), so every store below is a float4 along the output row.
-#include "ftx_common.h"
+//
+// The epilogue, the tile and split rules and the host layer are shared with ftx_dense_split.hip: ftx_dense_common.h.  This file also
+// holds the one definition of what that header only declares (the last section).
+#include "ftx_dense_common.h"
 
 using namespace ftx;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 __device__ inline bf16x4 round4(float4 v) { return (bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
 
-__device__ inline f32x16 mfma_bf16(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// nn.GELU() (approximate="none") and its derivative, in fp32
-__device__ inline float gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ inline float dgelu(float x) {
-  return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * (0.39894228040143268f * expf(-0.5f * x * x));
-}
-
 constexpr int DB_BK = 64;       // reduction elements staged per step: four k-steps of 16
 constexpr int DB_STRIDE = 72;   // bf16 per LDS row (144 B): conflict-free ds_read_b128 (WB_STRIDE of ftx_spconv_bf16.hip)
+static_assert(kDenseGranule % DB_BK == 0, "the entry admits every multiple of kDenseGranule as the reduction");
 
 }  // namespace
 
@@ -163,84 +152,10 @@ __global__ __launch_bounds__(256) void dense_gemm_bf16_kernel(const float *__res
       for (int q = 0; q < 4; ++q) {
         const int n = n0 + wn * 32 * NI + j * 32 + 8 * q + 4 * half;
         if (n >= N) continue;
-        float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        const int64_t o = m * N + n;
-        if (EPI == FTX_EPI_BIAS || EPI == FTX_EPI_BIAS_GELU) {
-          const float4 b = *(const float4 *)&bias[n];
-          v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-        }
-        if (EPI == FTX_EPI_BIAS_GELU) {
-          *(float4 *)&pre_out[o] = v;
-          v = make_float4(gelu(v.x), gelu(v.y), gelu(v.z), gelu(v.w));
-        }
-        if (EPI == FTX_EPI_DGELU) {
-          const float4 p = *(const float4 *)&pre_in[o];
-          v = make_float4(v.x * dgelu(p.x), v.y * dgelu(p.y), v.z * dgelu(p.z), v.w * dgelu(p.w));
-        }
-        *(float4 *)&out[o] = v;
+        dense_epilogue<EPI>(make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]), m * N + n, n, bias,
+                            pre_in, out, pre_out);
       }
   }
-}
-
-// Tile per shape: the largest of 128 x 128, 64 x 128, 64 x 64 that still gives one block per CU (256 tiles); else 64 x 64.
-// A function of the shape alone; ftx_dense_bf16_tile reports it.
-constexpr int DENSE_BF16_CUS = 256;   // MI355X; a constant of the tiling, not a device query
-static void gemm_tile(int64_t M, int N, int *mi, int *ni) {
-  static const int cand[3][2] = {{2, 2}, {1, 2}, {1, 1}};
-  for (const auto &c : cand) {
-    if (ceil_div(M, 64 * c[0]) * ceil_div(N, 64 * c[1]) >= DENSE_BF16_CUS) {
-      *mi = c[0];
-      *ni = c[1];
-      return;
-    }
-  }
-  *mi = 1;
-  *ni = 1;
-}
-
-template <int MI, int NI, bool WKN>
-static void launch_gemm_epi(int epi, dim3 grid, hipStream_t st, const float *A, const float *W, const float *bias, const float *pre_in, int64_t M, int N,
-                            int K, float *out, float *pre_out) {
-  switch (epi) {
-    case FTX_EPI_NONE: dense_gemm_bf16_kernel<MI, NI, FTX_EPI_NONE, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-    case FTX_EPI_BIAS: dense_gemm_bf16_kernel<MI, NI, FTX_EPI_BIAS, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-    case FTX_EPI_BIAS_GELU: dense_gemm_bf16_kernel<MI, NI, FTX_EPI_BIAS_GELU, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-    default: dense_gemm_bf16_kernel<MI, NI, FTX_EPI_DGELU, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-  }
-}
-
-template <int MI, int NI>
-static void launch_gemm(int w_kn, int epi, dim3 grid, hipStream_t st, const float *A, const float *W, const float *bias, const float *pre_in, int64_t M,
-                        int N, int K, float *out, float *pre_out) {
-  if (w_kn) launch_gemm_epi<MI, NI, true>(epi, grid, st, A, W, bias, pre_in, M, N, K, out, pre_out);
-  else launch_gemm_epi<MI, NI, false>(epi, grid, st, A, W, bias, pre_in, M, N, K, out, pre_out);
-}
-
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-extern "C" int ftx_dense_gemm_bf16(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n,
-                                   int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream) {
-  FTX_REQUIRE(m >= 0 && n >= 4 && k >= DB_BK, "ftx_dense_gemm_bf16: bad size (m=%lld n=%d k=%d)", (long long)m, n, k);
-  FTX_REQUIRE(k % DB_BK == 0, "ftx_dense_gemm_bf16: k must be a multiple of 64 (k=%d)", k);
-  FTX_REQUIRE(n % 4 == 0, "ftx_dense_gemm_bf16: n must be a multiple of 4 (n=%d)", n);
-  FTX_REQUIRE(w_kn == 0 || w_kn == 1, "ftx_dense_gemm_bf16: w_kn must be 0 or 1");
-  FTX_REQUIRE(epilogue >= FTX_EPI_NONE && epilogue <= FTX_EPI_DGELU, "ftx_dense_gemm_bf16: unknown epilogue %d", epilogue);
-  FTX_REQUIRE(m <= 0x7fffffff / 2 && (int64_t)n * k <= 0x7fffffff, "ftx_dense_gemm_bf16: too large");
-  if (m == 0) return FTX_OK;
-  FTX_REQUIRE(A && W && out, "ftx_dense_gemm_bf16: null pointer");
-  FTX_REQUIRE(epilogue == FTX_EPI_NONE || epilogue == FTX_EPI_DGELU || bias, "ftx_dense_gemm_bf16: null pointer (bias)");
-  FTX_REQUIRE(epilogue != FTX_EPI_BIAS_GELU || pre_out, "ftx_dense_gemm_bf16: null pointer (pre_out)");
-  FTX_REQUIRE(epilogue != FTX_EPI_DGELU || pre_in, "ftx_dense_gemm_bf16: null pointer (pre_in)");
-  FTX_REQUIRE(aligned16(A) && aligned16(W) && aligned16(out) && aligned16(bias) && aligned16(pre_in) && aligned16(pre_out),
-              "ftx_dense_gemm_bf16: pointers must be 16-byte aligned");
-  int mi, ni;
-  gemm_tile(m, n, &mi, &ni);
-  dim3 grid((unsigned)ceil_div(n, 64 * ni), (unsigned)ceil_div(m, 64 * mi));
-  hipStream_t st = (hipStream_t)stream;
-  if (mi == 2) launch_gemm<2, 2>(w_kn, epilogue, grid, st, A, W, bias, pre_in, m, n, k, out, pre_out);
-  else if (ni == 2) launch_gemm<1, 2>(w_kn, epilogue, grid, st, A, W, bias, pre_in, m, n, k, out, pre_out);
-  else launch_gemm<1, 1>(w_kn, epilogue, grid, st, A, W, bias, pre_in, m, n, k, out, pre_out);
-  return check_launch("ftx_dense_gemm_bf16");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -252,7 +167,7 @@ extern "C" int ftx_dense_gemm_bf16(const float *A, const float *W, int32_t w_kn,
 // A split count of 1 writes dW directly; otherwise each split writes its own (N x K) partial and dense_wgrad_reduce_kernel adds them.
 // ---------------------------------------------------------------------------------------
 constexpr int DW_BR = 64;    // rows (reduction) staged per step: four k-steps of 16
-constexpr int DW_T = 128;    // dW tile side
+constexpr int DW_T = kDenseDwTile;
 
 __global__ __launch_bounds__(256) void dense_wgrad_bf16_kernel(const float *__restrict__ G, const float *__restrict__ X, int64_t M, int N, int K,
                                                                int64_t split_len, float *__restrict__ part, float *__restrict__ dW) {
@@ -355,6 +270,36 @@ __global__ __launch_bounds__(256) void dense_wgrad_bf16_kernel(const float *__re
   }
 }
 
+struct DenseBf16 {
+  static constexpr const char *gemm_name = "ftx_dense_gemm_bf16", *wgrad_name = "ftx_dense_wgrad_bf16";
+  template <int MI, int NI, int EPI, bool WKN>
+  static void gemm(dim3 grid, hipStream_t st, const DenseGemmArgs &a) {
+    dense_gemm_bf16_kernel<MI, NI, EPI, WKN><<<grid, 256, 0, st>>>(a.A, a.W, a.bias, a.pre_in, a.M, a.N, a.K, a.out, a.pre_out);
+  }
+  static void wgrad(dim3 grid, hipStream_t st, const float *G, const float *X, int64_t M, int N, int K, int64_t len, float *part, float *dW) {
+    dense_wgrad_bf16_kernel<<<grid, 256, 0, st>>>(G, X, M, N, K, len, part, dW);
+  }
+};
+
+extern "C" int ftx_dense_gemm_bf16(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n,
+                                   int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream) {
+  return dense_gemm_entry<DenseBf16>(A, W, w_kn, bias, pre_in, m, n, k, epilogue, out, pre_out, stream);
+}
+
+extern "C" size_t ftx_dense_wgrad_bf16_workspace_bytes(int64_t m, int32_t n, int32_t k) { return dense_wgrad_workspace_bytes(m, n, k); }
+
+extern "C" int ftx_dense_wgrad_bf16(const float *G, const float *X, int64_t m, int32_t n, int32_t k, float *dW, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+  return dense_wgrad_entry<DenseBf16>(G, X, m, n, k, dW, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ftx_dense_bf16_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host) {
+  return dense_tile_entry("ftx_dense_bf16_tile", form, m, n, k, tile_m_host, tile_n_host, split_host);
+}
+
+// ---------------------------------------------------------------------------------------
+// The one definition of what ftx_dense_common.h declares for both families.
+// ---------------------------------------------------------------------------------------
 // dW = part[0] + part[1] + ... + part[S-1], added in split order: a fixed summation order, bit-reproducible.
 __global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(const float *__restrict__ part, int splits, int64_t n4, float *__restrict__ dW) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
@@ -367,76 +312,65 @@ __global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(const float *__
   }
 }
 
-// Splits of the rows: enough (N/128 x K/128 x S) blocks for one per CU, at least 256 rows per split, at most 8 splits; the split length
-// a multiple of DW_BR.  A function of the shape alone; ftx_dense_bf16_tile reports it.
-static int64_t wgrad_split_len(int64_t M, int N, int K, int *splits) {
-  const int64_t tiles = ceil_div(N, DW_T) * ceil_div(K, DW_T);
-  int64_t s = ceil_div(DENSE_BF16_CUS, tiles);
+namespace ftx {
+
+void dense_gemm_tile(int64_t M, int N, int *mi, int *ni) {
+  static const int cand[3][2] = {{2, 2}, {1, 2}, {1, 1}};
+  for (const auto &c : cand) {
+    if (ceil_div(M, 64 * c[0]) * ceil_div(N, 64 * c[1]) >= kDenseCUs) {
+      *mi = c[0];
+      *ni = c[1];
+      return;
+    }
+  }
+  *mi = 1;
+  *ni = 1;
+}
+
+int64_t dense_wgrad_split_len(int64_t M, int N, int K, int *splits) {
+  const int64_t tiles = ceil_div(N, kDenseDwTile) * ceil_div(K, kDenseDwTile);
+  int64_t s = ceil_div(kDenseCUs, tiles);
   int64_t cap = M / 256;
   if (cap > 8) cap = 8;
   if (s > cap) s = cap;
   if (s < 1) s = 1;
-  int64_t len = ceil_div(ceil_div(M, s), DW_BR) * DW_BR;
-  if (len < DW_BR) len = DW_BR;
+  int64_t len = ceil_div(ceil_div(M, s), kDenseGranule) * kDenseGranule;
+  if (len < kDenseGranule) len = kDenseGranule;
   *splits = (int)ceil_div(M, len);
   if (*splits < 1) *splits = 1;
   return len;
 }
 
-extern "C" size_t ftx_dense_wgrad_bf16_workspace_bytes(int64_t m, int32_t n, int32_t k) {
+void dense_wgrad_reduce(const float *part, int splits, int64_t n4, float *dW, hipStream_t st) {
+  dense_wgrad_reduce_kernel<<<grid_for(n4, 256), 256, 0, st>>>(part, splits, n4, dW);
+}
+
+size_t dense_wgrad_workspace_bytes(int64_t m, int32_t n, int32_t k) {
   if (m <= 0 || n <= 0 || k <= 0) return 256;
   int splits;
-  wgrad_split_len(m, n, k, &splits);
-  const size_t need = splits > 1 ? sizeof(float) * (size_t)splits * n * k : 0;
+  dense_wgrad_split_len(m, n, k, &splits);
+  const size_t need = dense_wgrad_partial_bytes(splits, n, k);
   return need > 256 ? need : 256;
 }
 
-extern "C" int ftx_dense_wgrad_bf16(const float *G, const float *X, int64_t m, int32_t n, int32_t k, float *dW, void *workspace, size_t workspace_bytes,
-                                    void *stream) {
-  FTX_REQUIRE(m >= 0 && n >= 4 && k >= 4, "ftx_dense_wgrad_bf16: bad size (m=%lld n=%d k=%d)", (long long)m, n, k);
-  FTX_REQUIRE(n % 4 == 0 && k % 4 == 0, "ftx_dense_wgrad_bf16: n and k must be multiples of 4 (n=%d k=%d)", n, k);
-  FTX_REQUIRE((int64_t)n * k <= 0x7fffffff / 8 && m <= 0x7fffffff / 2, "ftx_dense_wgrad_bf16: too large");
-  FTX_REQUIRE(dW, "ftx_dense_wgrad_bf16: null pointer (dW)");
-  FTX_REQUIRE(aligned16(dW) && aligned16(G) && aligned16(X) && aligned16(workspace), "ftx_dense_wgrad_bf16: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (m == 0) {
-    if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)n * k, st) != hipSuccess) return check_launch("ftx_dense_wgrad_bf16 memset");
-    return FTX_OK;
-  }
-  FTX_REQUIRE(G && X, "ftx_dense_wgrad_bf16: null pointer");
-  int splits;
-  const int64_t len = wgrad_split_len(m, n, k, &splits);
-  const size_t need = splits > 1 ? sizeof(float) * (size_t)splits * n * k : 0;
-  if (need > 0 && (!workspace || workspace_bytes < need)) {
-    set_error("ftx_dense_wgrad_bf16: workspace %zu < required %zu", workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
-  float *part = (float *)workspace;
-  dim3 grid((unsigned)ceil_div(k, DW_T), (unsigned)ceil_div(n, DW_T), (unsigned)splits);
-  dense_wgrad_bf16_kernel<<<grid, 256, 0, st>>>(G, X, m, n, k, len, part, dW);
-  if (splits > 1) {
-    const int64_t n4 = (int64_t)n * k / 4;
-    dense_wgrad_reduce_kernel<<<grid_for(n4, 256), 256, 0, st>>>(part, splits, n4, dW);
-  }
-  return check_launch("ftx_dense_wgrad_bf16");
-}
-
-extern "C" int ftx_dense_bf16_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host) {
-  FTX_REQUIRE(tile_m_host && tile_n_host && split_host, "ftx_dense_bf16_tile: null pointer");
-  FTX_REQUIRE(m >= 1 && n >= 4 && k >= 4, "ftx_dense_bf16_tile: bad size (m=%lld n=%d k=%d)", (long long)m, n, k);
+int dense_tile_entry(const char *me, int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host) {
+  FTX_REQUIRE(tile_m_host && tile_n_host && split_host, "%s: null pointer", me);
+  FTX_REQUIRE(m >= 1 && n >= 4 && k >= 4, "%s: bad size (m=%lld n=%d k=%d)", me, (long long)m, n, k);
   if (form == 0) {
     int mi, ni;
-    gemm_tile(m, n, &mi, &ni);
+    dense_gemm_tile(m, n, &mi, &ni);
     *tile_m_host = 64 * mi;
     *tile_n_host = 64 * ni;
     *split_host = 1;
     return FTX_OK;
   }
-  FTX_REQUIRE(form == 1, "ftx_dense_bf16_tile: form must be 0 (GEMM) or 1 (weight gradient)");
+  FTX_REQUIRE(form == 1, "%s: form must be 0 (GEMM) or 1 (weight gradient)", me);
   int splits;
-  wgrad_split_len(m, n, k, &splits);
-  *tile_m_host = DW_T;
-  *tile_n_host = DW_T;
+  dense_wgrad_split_len(m, n, k, &splits);
+  *tile_m_host = kDenseDwTile;
+  *tile_n_host = kDenseDwTile;
   *split_host = splits;
   return FTX_OK;
 }
+
+}  // namespace ftx

@@ -7,10 +7,10 @@
 //             x == h + m + l for finite |x| < 2^127 whose pieces stay at or above 2^-126; h not finite: m = l = 0.
 //   products  hh, hm, mh, hl, lh, mm (first letter: the A / dY piece).  ml, lm, ll are dropped: each below 2.01 * 2^-24 |a b|.
 //   order     TWO accumulators per output element (the form that shipped): `hh` takes the hh products alone, k ascending; `corr` takes,
-//             per 16-wide k-step, mm, hl, lh, hm, mh in that order (smallest first).  out = hh + corr, one fp32 add in the epilogue,
-//             then bias / GELU / GELU derivative exactly as ftx_dense_bf16.hip.  The corrections are 2^-8 of the result and smaller, so
+//             per 16-wide k-step, mm, hl, lh, hm, mh in that order (smallest first).  out = hh + corr, one fp32 add after the last k-step,
+//             then bias / GELU / GELU derivative by dense_epilogue (ftx_dense_common.h).  The corrections are 2^-8 of the result and smaller, so
 //             their chain's rounding is far below the hh chain's, which is that of a bf16-operand GEMM's fp32 accumulator.
-//             No atomics; the partial tiles of a split weight gradient are added by dense_split_reduce_kernel in split order.
+//             No atomics; the partial tiles of a split weight gradient are added by dense_wgrad_reduce_kernel in split order.
 //
 // LDS: three bf16 images per operand.  The stage is 32 reduction elements deep with a 40-element (80 B) row stride: 6 x 128 x 80 B
 // = 61 440 B at the 128 x 128 tile, under the 64 KB a static __shared__ array may take without a function attribute, two blocks per CU.
@@ -18,17 +18,14 @@
 // rows of a quarter wave start at 16 distinct multiples of four banks.  __launch_bounds__(256, 2) keeps the 128 x 128 kernels at or
 // under 256 registers so that two blocks do share a CU (measured: 13 % less time per block of Linears at batch 4 than one block per CU).
 //
-// Operand maps, tiles and the epilogue are those of ftx_dense_bf16.hip: lane (r = lane & 31, h = lane >> 5) holds row r, k = 8h + j of
+// The operand maps are those of ftx_dense_bf16.hip: lane (r = lane & 31, h = lane >> 5) holds row r, k = 8h + j of
 // both fragments of a 16-wide k-step; mfma(F1, F2) leaves C[row of F1][row of F2] with F2's row on the lane and four consecutive F1
 // rows in accumulator registers 4q..4q+3, so every store is a float4 along the output row.
-#include "ftx_common.h"
+//
+// The epilogue, the tile and split rules and the host layer are shared with ftx_dense_bf16.hip: ftx_dense_common.h.
+#include "ftx_dense_common.h"
 
 using namespace ftx;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -56,19 +53,9 @@ __device__ inline Pieces4 split4(float4 v) {
   return p;
 }
 
-__device__ inline f32x16 mfma_bf16(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// nn.GELU() (approximate="none") and its derivative, in fp32: the expressions of ftx_dense_bf16.hip
-__device__ inline float gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ inline float dgelu(float x) {
-  return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * (0.39894228040143268f * expf(-0.5f * x * x));
-}
-
 constexpr int DS_BK = 32;       // reduction elements staged per step: two k-steps of 16
 constexpr int DS_STRIDE = 40;   // bf16 per LDS row (80 B): conflict-free ds_read_b128
-constexpr int DS_KALIGN = 64;   // the reduction must be a multiple of this (the bf16 twins' rule, kept so both take the same shapes)
+static_assert(kDenseGranule % DS_BK == 0, "the entry admits every multiple of kDenseGranule as the reduction");
 
 }  // namespace
 
@@ -225,85 +212,11 @@ __global__ __launch_bounds__(256, 2) void dense_gemm_split_kernel(const float *_
       for (int q = 0; q < 4; ++q) {
         const int n = n0 + wn * 32 * NI + j * 32 + 8 * q + 4 * half;
         if (n >= N) continue;
-        float4 v = make_float4(hh[i][j][4 * q] + corr[i][j][4 * q], hh[i][j][4 * q + 1] + corr[i][j][4 * q + 1],
-                               hh[i][j][4 * q + 2] + corr[i][j][4 * q + 2], hh[i][j][4 * q + 3] + corr[i][j][4 * q + 3]);
-        const int64_t o = m * N + n;
-        if (EPI == FTX_EPI_BIAS || EPI == FTX_EPI_BIAS_GELU) {
-          const float4 b = *(const float4 *)&bias[n];
-          v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-        }
-        if (EPI == FTX_EPI_BIAS_GELU) {
-          *(float4 *)&pre_out[o] = v;
-          v = make_float4(gelu(v.x), gelu(v.y), gelu(v.z), gelu(v.w));
-        }
-        if (EPI == FTX_EPI_DGELU) {
-          const float4 p = *(const float4 *)&pre_in[o];
-          v = make_float4(v.x * dgelu(p.x), v.y * dgelu(p.y), v.z * dgelu(p.z), v.w * dgelu(p.w));
-        }
-        *(float4 *)&out[o] = v;
+        dense_epilogue<EPI>(make_float4(hh[i][j][4 * q] + corr[i][j][4 * q], hh[i][j][4 * q + 1] + corr[i][j][4 * q + 1],
+                                        hh[i][j][4 * q + 2] + corr[i][j][4 * q + 2], hh[i][j][4 * q + 3] + corr[i][j][4 * q + 3]),
+                            m * N + n, n, bias, pre_in, out, pre_out);
       }
   }
-}
-
-// Tile per shape: the largest of 128 x 128, 64 x 128, 64 x 64 that still gives one block per CU (256 tiles); else 64 x 64 (the bf16
-// kernels' rule).  A function of the shape alone; ftx_dense_split_tile reports it.
-constexpr int DENSE_SPLIT_CUS = 256;   // MI355X; a constant of the tiling, not a device query
-static void split_gemm_tile(int64_t M, int N, int *mi, int *ni) {
-  static const int cand[3][2] = {{2, 2}, {1, 2}, {1, 1}};
-  for (const auto &c : cand) {
-    if (ceil_div(M, 64 * c[0]) * ceil_div(N, 64 * c[1]) >= DENSE_SPLIT_CUS) {
-      *mi = c[0];
-      *ni = c[1];
-      return;
-    }
-  }
-  *mi = 1;
-  *ni = 1;
-}
-
-template <int MI, int NI, bool WKN>
-static void launch_split_epi(int epi, dim3 grid, hipStream_t st, const float *A, const float *W, const float *bias, const float *pre_in, int64_t M, int N,
-                             int K, float *out, float *pre_out) {
-  switch (epi) {
-    case FTX_EPI_NONE: dense_gemm_split_kernel<MI, NI, FTX_EPI_NONE, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-    case FTX_EPI_BIAS: dense_gemm_split_kernel<MI, NI, FTX_EPI_BIAS, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-    case FTX_EPI_BIAS_GELU: dense_gemm_split_kernel<MI, NI, FTX_EPI_BIAS_GELU, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-    default: dense_gemm_split_kernel<MI, NI, FTX_EPI_DGELU, WKN><<<grid, 256, 0, st>>>(A, W, bias, pre_in, M, N, K, out, pre_out); break;
-  }
-}
-
-template <int MI, int NI>
-static void launch_split(int w_kn, int epi, dim3 grid, hipStream_t st, const float *A, const float *W, const float *bias, const float *pre_in, int64_t M,
-                         int N, int K, float *out, float *pre_out) {
-  if (w_kn) launch_split_epi<MI, NI, true>(epi, grid, st, A, W, bias, pre_in, M, N, K, out, pre_out);
-  else launch_split_epi<MI, NI, false>(epi, grid, st, A, W, bias, pre_in, M, N, K, out, pre_out);
-}
-
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-extern "C" int ftx_dense_gemm_split(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n,
-                                    int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream) {
-  FTX_REQUIRE(m >= 0 && n >= 4 && k >= DS_KALIGN, "ftx_dense_gemm_split: bad size (m=%lld n=%d k=%d)", (long long)m, n, k);
-  FTX_REQUIRE(k % DS_KALIGN == 0, "ftx_dense_gemm_split: k must be a multiple of 64 (k=%d)", k);
-  FTX_REQUIRE(n % 4 == 0, "ftx_dense_gemm_split: n must be a multiple of 4 (n=%d)", n);
-  FTX_REQUIRE(w_kn == 0 || w_kn == 1, "ftx_dense_gemm_split: w_kn must be 0 or 1");
-  FTX_REQUIRE(epilogue >= FTX_EPI_NONE && epilogue <= FTX_EPI_DGELU, "ftx_dense_gemm_split: unknown epilogue %d", epilogue);
-  FTX_REQUIRE(m <= 0x7fffffff / 2 && (int64_t)n * k <= 0x7fffffff, "ftx_dense_gemm_split: too large");
-  if (m == 0) return FTX_OK;
-  FTX_REQUIRE(A && W && out, "ftx_dense_gemm_split: null pointer");
-  FTX_REQUIRE(epilogue == FTX_EPI_NONE || epilogue == FTX_EPI_DGELU || bias, "ftx_dense_gemm_split: null pointer (bias)");
-  FTX_REQUIRE(epilogue != FTX_EPI_BIAS_GELU || pre_out, "ftx_dense_gemm_split: null pointer (pre_out)");
-  FTX_REQUIRE(epilogue != FTX_EPI_DGELU || pre_in, "ftx_dense_gemm_split: null pointer (pre_in)");
-  FTX_REQUIRE(aligned16(A) && aligned16(W) && aligned16(out) && aligned16(bias) && aligned16(pre_in) && aligned16(pre_out),
-              "ftx_dense_gemm_split: pointers must be 16-byte aligned");
-  int mi, ni;
-  split_gemm_tile(m, n, &mi, &ni);
-  dim3 grid((unsigned)ceil_div(n, 64 * ni), (unsigned)ceil_div(m, 64 * mi));
-  hipStream_t st = (hipStream_t)stream;
-  if (mi == 2) launch_split<2, 2>(w_kn, epilogue, grid, st, A, W, bias, pre_in, m, n, k, out, pre_out);
-  else if (ni == 2) launch_split<1, 2>(w_kn, epilogue, grid, st, A, W, bias, pre_in, m, n, k, out, pre_out);
-  else launch_split<1, 1>(w_kn, epilogue, grid, st, A, W, bias, pre_in, m, n, k, out, pre_out);
-  return check_launch("ftx_dense_gemm_split");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -313,11 +226,10 @@ extern "C" int ftx_dense_gemm_split(const float *A, const float *W, int32_t w_kn
 // Block = (128-column tile of k, 128-row tile of n, split s of the rows); 4 waves as 2 x 2, each 64 x 64.  Each step stages DSW_BR rows:
 // float4 loads along the channels, split, and stored TRANSPOSED as m-contiguous bf16 images [piece][channel][m] with two rows packed per
 // 32-bit LDS write (the register stage of dense_wgrad_bf16_kernel).  Rows past the split are zeroed on the block-uniform last step.
-// A split count of 1 writes dW directly; otherwise each split writes its own (N x K) partial and dense_split_reduce_kernel adds them.
+// A split count of 1 writes dW directly; otherwise each split writes its own (N x K) partial and dense_wgrad_reduce_kernel adds them.
 // ---------------------------------------------------------------------------------------
 constexpr int DSW_BR = 32;    // rows (reduction) staged per step: two k-steps of 16
-constexpr int DSW_T = 128;    // dW tile side
-constexpr int DSW_LEN = 64;   // a split's length is a multiple of this (the bf16 twin's rule)
+constexpr int DSW_T = kDenseDwTile;
 
 __global__ __launch_bounds__(256, 2) void dense_wgrad_split_kernel(const float *__restrict__ G, const float *__restrict__ X, int64_t M, int N, int K,
                                                                 int64_t split_len, float *__restrict__ part, float *__restrict__ dW) {
@@ -438,88 +350,29 @@ __global__ __launch_bounds__(256, 2) void dense_wgrad_split_kernel(const float *
   }
 }
 
-// dW = part[0] + part[1] + ... + part[S-1], added in split order: a fixed summation order, bit-reproducible.
-__global__ __launch_bounds__(256) void dense_split_reduce_kernel(const float *__restrict__ part, int splits, int64_t n4, float *__restrict__ dW) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
-    float4 s = ((const float4 *)part)[e];
-    for (int t = 1; t < splits; ++t) {
-      const float4 v = ((const float4 *)part)[t * n4 + e];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    ((float4 *)dW)[e] = s;
+struct DenseSplit {
+  static constexpr const char *gemm_name = "ftx_dense_gemm_split", *wgrad_name = "ftx_dense_wgrad_split";
+  template <int MI, int NI, int EPI, bool WKN>
+  static void gemm(dim3 grid, hipStream_t st, const DenseGemmArgs &a) {
+    dense_gemm_split_kernel<MI, NI, EPI, WKN><<<grid, 256, 0, st>>>(a.A, a.W, a.bias, a.pre_in, a.M, a.N, a.K, a.out, a.pre_out);
   }
+  static void wgrad(dim3 grid, hipStream_t st, const float *G, const float *X, int64_t M, int N, int K, int64_t len, float *part, float *dW) {
+    dense_wgrad_split_kernel<<<grid, 256, 0, st>>>(G, X, M, N, K, len, part, dW);
+  }
+};
+
+extern "C" int ftx_dense_gemm_split(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n,
+                                    int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream) {
+  return dense_gemm_entry<DenseSplit>(A, W, w_kn, bias, pre_in, m, n, k, epilogue, out, pre_out, stream);
 }
 
-// Splits of the rows: enough (N/128 x K/128 x S) blocks for one per CU, at least 256 rows per split, at most 8 splits; the split length
-// a multiple of DSW_LEN.  A function of the shape alone; ftx_dense_split_tile reports it.
-static int64_t split_wgrad_len(int64_t M, int N, int K, int *splits) {
-  const int64_t tiles = ceil_div(N, DSW_T) * ceil_div(K, DSW_T);
-  int64_t s = ceil_div(DENSE_SPLIT_CUS, tiles);
-  int64_t cap = M / 256;
-  if (cap > 8) cap = 8;
-  if (s > cap) s = cap;
-  if (s < 1) s = 1;
-  int64_t len = ceil_div(ceil_div(M, s), DSW_LEN) * DSW_LEN;
-  if (len < DSW_LEN) len = DSW_LEN;
-  *splits = (int)ceil_div(M, len);
-  if (*splits < 1) *splits = 1;
-  return len;
-}
-
-extern "C" size_t ftx_dense_wgrad_split_workspace_bytes(int64_t m, int32_t n, int32_t k) {
-  if (m <= 0 || n <= 0 || k <= 0) return 256;
-  int splits;
-  split_wgrad_len(m, n, k, &splits);
-  const size_t need = splits > 1 ? sizeof(float) * (size_t)splits * n * k : 0;
-  return need > 256 ? need : 256;
-}
+extern "C" size_t ftx_dense_wgrad_split_workspace_bytes(int64_t m, int32_t n, int32_t k) { return dense_wgrad_workspace_bytes(m, n, k); }
 
 extern "C" int ftx_dense_wgrad_split(const float *G, const float *X, int64_t m, int32_t n, int32_t k, float *dW, void *workspace, size_t workspace_bytes,
                                      void *stream) {
-  FTX_REQUIRE(m >= 0 && n >= 4 && k >= 4, "ftx_dense_wgrad_split: bad size (m=%lld n=%d k=%d)", (long long)m, n, k);
-  FTX_REQUIRE(n % 4 == 0 && k % 4 == 0, "ftx_dense_wgrad_split: n and k must be multiples of 4 (n=%d k=%d)", n, k);
-  FTX_REQUIRE((int64_t)n * k <= 0x7fffffff / 8 && m <= 0x7fffffff / 2, "ftx_dense_wgrad_split: too large");
-  FTX_REQUIRE(dW, "ftx_dense_wgrad_split: null pointer (dW)");
-  FTX_REQUIRE(aligned16(dW) && aligned16(G) && aligned16(X) && aligned16(workspace), "ftx_dense_wgrad_split: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (m == 0) {
-    if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)n * k, st) != hipSuccess) return check_launch("ftx_dense_wgrad_split memset");
-    return FTX_OK;
-  }
-  FTX_REQUIRE(G && X, "ftx_dense_wgrad_split: null pointer");
-  int splits;
-  const int64_t len = split_wgrad_len(m, n, k, &splits);
-  const size_t need = splits > 1 ? sizeof(float) * (size_t)splits * n * k : 0;
-  if (need > 0 && (!workspace || workspace_bytes < need)) {
-    set_error("ftx_dense_wgrad_split: workspace %zu < required %zu", workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
-  float *part = (float *)workspace;
-  dim3 grid((unsigned)ceil_div(k, DSW_T), (unsigned)ceil_div(n, DSW_T), (unsigned)splits);
-  dense_wgrad_split_kernel<<<grid, 256, 0, st>>>(G, X, m, n, k, len, part, dW);
-  if (splits > 1) {
-    const int64_t n4 = (int64_t)n * k / 4;
-    dense_split_reduce_kernel<<<grid_for(n4, 256), 256, 0, st>>>(part, splits, n4, dW);
-  }
-  return check_launch("ftx_dense_wgrad_split");
+  return dense_wgrad_entry<DenseSplit>(G, X, m, n, k, dW, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ftx_dense_split_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host) {
-  FTX_REQUIRE(tile_m_host && tile_n_host && split_host, "ftx_dense_split_tile: null pointer");
-  FTX_REQUIRE(m >= 1 && n >= 4 && k >= 4, "ftx_dense_split_tile: bad size (m=%lld n=%d k=%d)", (long long)m, n, k);
-  if (form == 0) {
-    int mi, ni;
-    split_gemm_tile(m, n, &mi, &ni);
-    *tile_m_host = 64 * mi;
-    *tile_n_host = 64 * ni;
-    *split_host = 1;
-    return FTX_OK;
-  }
-  FTX_REQUIRE(form == 1, "ftx_dense_split_tile: form must be 0 (GEMM) or 1 (weight gradient)");
-  int splits;
-  split_wgrad_len(m, n, k, &splits);
-  *tile_m_host = DSW_T;
-  *tile_n_host = DSW_T;
-  *split_host = splits;
-  return FTX_OK;
+  return dense_tile_entry("ftx_dense_split_tile", form, m, n, k, tile_m_host, tile_n_host, split_host);
 }

@@ -24,12 +24,11 @@
 #include <cstdlib>
 #include "ftx_common.h"
 #include "ftx_bn_eval_op.h"
+#include "ftx_mfma.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 using namespace ftx;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------
 // pair lists

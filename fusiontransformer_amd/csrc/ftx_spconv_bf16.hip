@@ -14,22 +14,14 @@
 // the same layout as the f32 MFMA, so both kernels keep the epilogues of their fp32 twins.  Both operands are staged as bf16 LDS images
 // in which the reduction index is contiguous: one ds_read_b128 per operand and k-step.
 #include "ftx_common.h"
+#include "ftx_mfma.h"
 #include "ftx_spconv_wgrad_reduce.h"
 
 using namespace ftx;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 __device__ inline bf16x4 round4(float4 v) { return (bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
-
-__device__ inline f32x16 mfma_bf16(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 // Tile -> (offset, first pair, pair count) of an upper-bound grid of `tile`-pair tiles: wave 0 scans the per-offset tile counts
 // (the scan of pairs_gemm_kernel).  s_tile[0] = -1 for a surplus block.

@@ -10,6 +10,7 @@ the GPU, index tensors are int32 (torchsparse returns int64 and immediately
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -1298,9 +1299,9 @@ def attention(qkv, scale, tiling=(0, 0), bf16=False):
 # ---------------------------------------------------------------- bf16-operand ViT Linears
 # Epilogues of ftx_dense_gemm_bf16 (include/ftx.h FTX_EPI_*)
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU = 0, 1, 2, 3
-# mode of the kernels -> the C entries' suffix.  "bf16": operands rounded to bf16.  "split": every operand split into three bf16 pieces,
-# six piece products summed in fp32 (fp32-class accuracy; the contract is stated in include/ftx.h).
-_DENSE_MODES = {"bf16": "bf16", "split": "split"}
+# modes of the kernels; the mode is the C entries' suffix.  "bf16": operands rounded to bf16.  "split": every operand split into three
+# bf16 pieces, six piece products summed in fp32 (fp32-class accuracy; the contract is stated in include/ftx.h).
+_DENSE_MODES = ("bf16", "split")
 
 
 def vit_linear_supported(x, weight):
@@ -1315,42 +1316,39 @@ def _dense_gemm(a, w, w_kn, epi, bias=None, pre_in=None, with_pre=False, mode="b
     """ftx_dense_gemm_bf16 (mode "bf16") or ftx_dense_gemm_split (mode "split"): a (m, kr) times W ((n, kr) for w_kn = 0, (kr, n) for
     w_kn = 1) -> (out, pre_out or None), fp32."""
     L = _lib.load()
-    entry = _DENSE_MODES[mode]
     m, kr = a.shape
     n = w.shape[1] if w_kn else w.shape[0]
     out = _empty((m, n), F32, a)
     pre = _empty((m, n), F32, a) if with_pre else None
-    _log_launch("vit_gemm_" + mode, dict(m=m, n=n, k=kr, w_kn=w_kn, epi=epi), lambda: check(getattr(L, "ftx_dense_gemm_" + entry)(
-        ptr(a), ptr(w), w_kn, ptr(bias), ptr(pre_in), m, n, kr, epi, ptr(out), ptr(pre), stream()), "ftx_dense_gemm_" + entry))
+    _log_launch("vit_gemm_" + mode, dict(m=m, n=n, k=kr, w_kn=w_kn, epi=epi), lambda: check(getattr(L, "ftx_dense_gemm_" + mode)(
+        ptr(a), ptr(w), w_kn, ptr(bias), ptr(pre_in), m, n, kr, epi, ptr(out), ptr(pre), stream()), "ftx_dense_gemm_" + mode))
     return out, pre
 
 
 def _dense_wgrad(g, x, mode="bf16"):
     """ftx_dense_wgrad_bf16 / ftx_dense_wgrad_split: dW (n, k) = g (m, n)^T x (m, k)."""
     L = _lib.load()
-    entry = _DENSE_MODES[mode]
     m, n = g.shape
     k = x.shape[1]
     dw = _empty((n, k), F32, g)
-    ws_bytes = _ws_bytes(f"ftx_dense_wgrad_{entry}_workspace_bytes", m, n, k)
+    ws_bytes = _ws_bytes(f"ftx_dense_wgrad_{mode}_workspace_bytes", m, n, k)
     ws = _scratch(ws_bytes, g)
-    _log_launch("vit_wgrad_" + mode, dict(m=m, n=n, k=k), lambda: check(getattr(L, "ftx_dense_wgrad_" + entry)(
-        ptr(g), ptr(x), m, n, k, ptr(dw), ptr(ws), ws_bytes, stream()), "ftx_dense_wgrad_" + entry))
+    _log_launch("vit_wgrad_" + mode, dict(m=m, n=n, k=k), lambda: check(getattr(L, "ftx_dense_wgrad_" + mode)(
+        ptr(g), ptr(x), m, n, k, ptr(dw), ptr(ws), ws_bytes, stream()), "ftx_dense_wgrad_" + mode))
     return dw
 
 
-def dense_bf16_tile(form, m, n, k):
-    """(tile rows, tile columns, row splits) that ftx_dense_gemm_bf16 (form 0) or ftx_dense_wgrad_bf16 (form 1) picks: host only."""
+def dense_tile(mode, form, m, n, k):
+    """(tile rows, tile columns, row splits) that ftx_dense_gemm_<mode> (form 0) or ftx_dense_wgrad_<mode> (form 1) picks: host only."""
+    entry = f"ftx_dense_{mode}_tile"
     tm, tn, sp = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    check(_lib.load().ftx_dense_bf16_tile(form, m, n, k, ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(sp)), "ftx_dense_bf16_tile")
+    check(getattr(_lib.load(), entry)(form, m, n, k, ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(sp)), entry)
     return tm.value, tn.value, sp.value
 
 
-def dense_split_tile(form, m, n, k):
-    """(tile rows, tile columns, row splits) that ftx_dense_gemm_split (form 0) or ftx_dense_wgrad_split (form 1) picks: host only."""
-    tm, tn, sp = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    check(_lib.load().ftx_dense_split_tile(form, m, n, k, ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(sp)), "ftx_dense_split_tile")
-    return tm.value, tn.value, sp.value
+# the per-family names the tests and callers written before dense_tile use
+dense_bf16_tile = functools.partial(dense_tile, "bf16")
+dense_split_tile = functools.partial(dense_tile, "split")
 
 
 class _VitLinear(torch.autograd.Function):
@@ -1416,15 +1414,10 @@ def vit_linear(x, w, b=None, bf16=True, mode="bf16"):
     `bf16` is then ignored, and a shape the kernels do not take runs the FP32 library path (_LinearFn(..., False))."""
     if mode not in _DENSE_MODES:
         raise ValueError(f"vit_linear mode must be 'bf16' or 'split', got {mode!r}")
-    if mode == "split":
-        if vit_linear_supported(x, w):
-            return _VitLinear.apply(x, w, b, "split")
-        from .models.transformers import _LinearFn
-        return _LinearFn.apply(x, w, b, False)
-    if bf16 and vit_linear_supported(x, w):
-        return _VitLinear.apply(x, w, b)
+    if (mode == "split" or bf16) and vit_linear_supported(x, w):
+        return _VitLinear.apply(x, w, b, mode)
     from .models.transformers import _LinearFn
-    return _LinearFn.apply(x, w, b, bool(bf16))
+    return _LinearFn.apply(x, w, b, mode != "split" and bool(bf16))
 
 
 def vit_mlp(x, w1, b1, w2, b2=None, mode="bf16"):
@@ -1435,7 +1428,7 @@ def vit_mlp(x, w1, b1, w2, b2=None, mode="bf16"):
         raise ValueError(f"vit_mlp mode must be 'bf16' or 'split', got {mode!r}")
     if (b1 is not None and vit_linear_supported(x, w1) and w2.is_cuda and w2.dtype == F32 and w2.shape[1] == w1.shape[0]
             and w2.shape[0] % 64 == 0):
-        return _VitMlp.apply(x, w1, b1, w2, b2, mode) if mode == "split" else _VitMlp.apply(x, w1, b1, w2, b2)
+        return _VitMlp.apply(x, w1, b1, w2, b2, mode)
     from .models.transformers import _LinearFn
     lib_bf16 = mode != "split"
     return _LinearFn.apply(torch.nn.functional.gelu(_LinearFn.apply(x, w1, b1, lib_bf16)), w2, b2, lib_bf16)
