@@ -60,6 +60,7 @@ def get_cfg_defaults() -> CfgNode:
             "TYPE": "", "SAVE": True, "CKPT_PATH": "", "NUM_CLASSES": 20, "DUAL_HEAD": False,
             "USE_IMAGE": False, "USE_LIDAR": False, "USE_FUSION": False, "IMAGE_PRETRAINED_PATH": "",
             "middle_feat_block_number": None, "late_feat_block_number": None,
+            "image_stn": False,      # build_model builds TYPE="ImageSeg" only when this is set (image_stn_cfg())
         },
         "OPTIMIZER": {"TYPE": "", "BASE_LR": 0.001, "WEIGHT_DECAY": 0.0, "Adam": {"betas": (0.9, 0.999)}},
         "TRAIN": {"BATCH_SIZE": 0, "CLASS_WEIGHTS": [], "FusionTransformer": {"lambda_xm": 0.0}},
@@ -106,3 +107,9 @@ def image_cfg() -> CfgNode:
     """The image-only baseline (the reference's configs/semantic_kitti/imageBilinear.yaml): the ViT trunk tapped after its last
     block, lifted onto the points, one linear head."""
     return _single_cfg(dict(TYPE="ImageSegBilinear", USE_IMAGE=True, late_feat_block_number=11))
+
+
+def image_stn_cfg() -> CfgNode:
+    """The spatial-transformer image-only baseline (the reference's configs/semantic_kitti/image.yaml): learned affine resampling to
+    the ViT and back (models/image_models_stn.py), one linear head."""
+    return _single_cfg(dict(TYPE="ImageSeg", USE_IMAGE=True, late_feat_block_number=11, image_stn=True))

@@ -1145,6 +1145,138 @@ def resample_nearest(x, size):
     return _ResampleNearest.apply(x, size[0], size[1])
 
 
+# ---------------------------------------------------------------- affine grid sampling (spatial transformers)
+def _affine_operands(src, theta, who):
+    """(b, c, ih, iw, host stride array) of a strided float32 source and its (b, 2, 3) theta, checked before anything is launched."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise ValueError(f"{who} src: expected a CUDA (HIP) tensor; the product path has no CPU fallback")
+    if src.dtype != F32 or src.dim() != 4:
+        raise ValueError(f"{who} src: expected a 4-d float32 tensor, got {src.dtype} {tuple(src.shape)}")
+    b, c, ih, iw = src.shape
+    if min(b, c, ih, iw) < 1 or b > 128:
+        raise ValueError(f"{who} src: empty tensor or more than 128 frames: {tuple(src.shape)}")
+    # any layout whose elements are distinct (NCHW, channels-last, a slice): an expanded tensor would alias its gradient
+    if any(st <= 0 and sz > 1 for st, sz in zip(src.stride(), src.shape)):
+        raise ValueError(f"{who} src: strides {src.stride()} alias elements")
+    req(theta, F32, who + " theta", 3)
+    if theta.shape != (b, 2, 3):
+        raise ValueError(f"{who} theta: expected ({b}, 2, 3), got {tuple(theta.shape)}")
+    if theta.device != src.device:
+        raise ValueError(f"{who}: src and theta live on different devices")
+    return b, c, ih, iw, (ctypes.c_int64 * 4)(*src.stride())
+
+
+def _affine_size(h, w, who):
+    h, w = int(h), int(w)
+    if h < 1 or w < 1 or h * w >= 2 ** 31:
+        raise ValueError(f"{who}: bad target size ({h}, {w})")
+    return h, w
+
+
+class _AffineSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, theta, oh, ow):
+        L = _lib.load()
+        b, c, ih, iw, strides = _affine_operands(src, theta, "affine_sample")
+        out = _empty((b, c, oh, ow), F32, src)
+        check(L.ftx_affine_sample_fwd(ptr(src), strides, b, c, ih, iw, ptr(theta), oh, ow, ptr(out), stream()), "ftx_affine_sample_fwd")
+        ctx.save_for_backward(src, theta)
+        ctx.size = (oh, ow)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        L = _lib.load()
+        src, theta = ctx.saved_tensors
+        oh, ow = ctx.size
+        b, c, ih, iw, strides = _affine_operands(src, theta, "affine_sample")
+        go = req(go.contiguous(), F32, "affine_sample grad", 4)
+        if go.shape != (b, c, oh, ow):
+            raise ValueError("affine_sample: gradient shape differs from the output's")
+        gt = _empty((b, 2, 3), F32, theta)
+        ws_bytes = _ws_bytes("ftx_affine_theta_workspace_bytes", b)
+        ws = _scratch(ws_bytes, theta)
+        check(L.ftx_affine_sample_bwd_theta(ptr(src), strides, b, c, ih, iw, ptr(theta), ptr(go), oh, ow, ptr(gt), ptr(ws), ws_bytes, stream()),
+              "ftx_affine_sample_bwd_theta")
+        return None, gt, None, None
+
+
+def affine_sample(src, theta, size):
+    """F.grid_sample(src, F.affine_grid(theta, (b, c) + size, align_corners=False), align_corners=False) -- bilinear, zero padding --
+    for src (b, c, ih, iw) of any non-aliasing strides and theta (b, 2, 3); NCHW result.  The grid is never stored.  Differentiable in
+    theta only (bit-reproducible): like sample_down, this dense form is for the input image and refuses a source that needs a gradient."""
+    if src.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("affine_sample: the dense form does not produce a gradient for src (affine_lift does)")
+    oh, ow = _affine_size(size[0], size[1], "affine_sample")
+    return _AffineSample.apply(src, theta, oh, ow)
+
+
+def _affine_points(img_idx, point_batch, src, who):
+    req(img_idx, I64, who + " img_idx", 2)
+    req(point_batch, I32, who + " point_batch", 1)
+    n = img_idx.shape[0]
+    if img_idx.shape != (n, 2) or point_batch.shape[0] != n:
+        raise ValueError(f"{who}: img_idx must be (N, 2), point_batch (N,)")
+    if img_idx.device != src.device or point_batch.device != src.device:
+        raise ValueError(f"{who}: the point indices live on another device than src")
+    return n
+
+
+class _AffineLift(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, theta, img_idx, point_batch, H, W):
+        L = _lib.load()
+        b, c, ih, iw, strides = _affine_operands(src, theta, "affine_lift")
+        n = _affine_points(img_idx, point_batch, src, "affine_lift")
+        out = _empty((n, c), F32, src)
+        check(L.ftx_affine_lift_fwd(ptr(src), strides, b, c, ih, iw, ptr(theta), ptr(img_idx), ptr(point_batch), n, H, W, ptr(out), stream()),
+              "ftx_affine_lift_fwd")
+        ctx.save_for_backward(src, theta, img_idx, point_batch)
+        ctx.size = (H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        L = _lib.load()
+        src, theta, img_idx, point_batch = ctx.saved_tensors
+        H, W = ctx.size
+        b, c, ih, iw, strides = _affine_operands(src, theta, "affine_lift")
+        n = img_idx.shape[0]
+        go = req(go.contiguous(), F32, "affine_lift grad", 2)
+        if go.shape != (n, c):
+            raise ValueError("affine_lift: gradient shape differs from the output's")
+        want_src, want_theta = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gs = gt = seg = None
+        if want_src:
+            # theta is data: the sort of the points by source cell belongs to this call alone (nothing to share between taps or to prefetch)
+            cells = _empty((n,), I32, point_batch)
+            check(L.ftx_affine_lift_cells(ptr(theta), ptr(img_idx), ptr(point_batch), n, b, ih, iw, H, W, ptr(cells), stream()),
+                  "ftx_affine_lift_cells")
+            seg = Segments(cells, b * (ih + 1) * (iw + 1))
+            gs = torch.empty_strided(src.shape, src.stride(), dtype=F32, device=src.device)
+        ws_bytes = 0
+        if want_theta:
+            gt = _empty((b, 2, 3), F32, theta)
+            ws_bytes = _ws_bytes("ftx_affine_theta_workspace_bytes", b)
+        ws = _scratch(ws_bytes, theta) if want_theta else None
+        if want_src or want_theta:
+            check(L.ftx_affine_lift_bwd(ptr(src), strides, b, c, ih, iw, ptr(theta), ptr(img_idx), ptr(point_batch), ptr(go), n, H, W,
+                                        ptr(seg.order) if seg is not None else 0, ptr(seg.seg_off) if seg is not None else 0,
+                                        ptr(gs), ptr(gt), ptr(ws), ws_bytes, stream()), "ftx_affine_lift_bwd")
+        return gs, gt, None, None, None, None
+
+
+def affine_lift(src, theta, img_idx, point_batch, H, W):
+    """The rows affine_sample(src, theta, (H, W))[point_batch, :, row, col] for img_idx (N, 2) int64 (row, col), bit for bit, without
+    the (H, W) map: (N, c).  A point whose frame or pixel is out of range gives a zero row and takes no gradient.  Differentiable in
+    src (same strides as src, every element written; the points are sorted by source cell inside the backward) and in theta; no
+    float atomics, so both gradients repeat bit for bit."""
+    H, W = _affine_size(H, W, "affine_lift")
+    return _AffineLift.apply(src, theta, img_idx, point_batch, H, W)
+
+
 # ---------------------------------------------------------------- LayerNorm (+ the residual add in front of it)
 def layer_norm_supported(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == F32 and x.shape[-1] % 256 == 0 and 256 <= x.shape[-1] <= 1024

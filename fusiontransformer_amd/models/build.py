@@ -1,7 +1,7 @@
 """build_model(cfg): mirror of FusionTransformer/models/build.py:9-88 (same dispatch on
 cfg.MODEL.USE_FUSION / USE_LIDAR / USE_IMAGE and cfg.MODEL.TYPE, same return tuples)."""
 from .early_fusion import EarlyFusionTransformer
-from .image_models import ImageSegBilinear
+from .image_models import ImageSeg, ImageSegBilinear
 from .late_fusion import LateFusionTransformer
 from .lidar_model import LidarSeg
 from .metric import SegIoU
@@ -37,6 +37,11 @@ def build_lidar_model(cfg):
     return LidarSeg(num_classes=cfg.MODEL.NUM_CLASSES, backbone_3d_kwargs=cfg.MODEL), train_3d_metric
 
 
+def build_image_model(cfg):
+    train_2d_metric = SegIoU(num_classes=cfg.MODEL.NUM_CLASSES, name="seg_iou_2d")
+    return ImageSeg(num_classes=cfg.MODEL.NUM_CLASSES, dual_head=cfg.MODEL.DUAL_HEAD, backbone_2d_kwargs=cfg.MODEL), train_2d_metric
+
+
 def build_image_bilinear_model(cfg):
     train_2d_metric = SegIoU(num_classes=cfg.MODEL.NUM_CLASSES, name="seg_iou_2d")
     return ImageSegBilinear(num_classes=cfg.MODEL.NUM_CLASSES, dual_head=cfg.MODEL.DUAL_HEAD, backbone_2d_kwargs=cfg.MODEL), train_2d_metric
@@ -57,5 +62,9 @@ def build_model(cfg):
         if cfg.MODEL.TYPE == "ImageSegBilinear":
             return build_image_bilinear_model(cfg)
         if cfg.MODEL.TYPE == "ImageSeg":
-            raise NotImplementedError("ImageSeg (spatial-transformer variant) is out of scope: no fusion model uses it")
+            # the spatial-transformer baseline is opt-in: cfg.MODEL.image_stn (config.image_stn_cfg() sets it)
+            if cfg.MODEL.get("image_stn", False):
+                return build_image_model(cfg)
+            raise NotImplementedError("TYPE=ImageSeg (the spatial-transformer baseline) is built only when cfg.MODEL.image_stn is true "
+                                      "(config.image_stn_cfg()); or call build_image_model(cfg) directly")
     raise ValueError("unsupported MODEL configuration: TYPE=%s" % cfg.MODEL.TYPE)

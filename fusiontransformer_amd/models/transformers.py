@@ -9,7 +9,10 @@ restated here with the same attribute names, so DeiT checkpoints keyed
 The dense contractions (patch-embed conv, qkv / proj / MLP linears) go through
 torch's hipBLASLt GEMMs; softmax(QK^T/8)V runs in libftx's fused attention
 kernel when `attn_impl == "ftx"` (exact fp32) or `"ftx_bf16"` (bf16 operands, fp32 accumulation and softmax:
-functional.attention(bf16=True)), otherwise as the three explicit ops timm uses."""
+functional.attention(bf16=True)), otherwise as the three explicit ops timm uses.
+
+`SpatialTransformer` / `ScaleUpModule` (reference models/transformers.py:102-156) are at the end of the file: learned affine
+resampling on libftx's affine-sampling kernels (functional.affine_sample / affine_lift)."""
 from __future__ import annotations
 
 import contextlib
@@ -21,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-__all__ = ["Image2DTransformer", "image_2d_distilled_transformer"]
+__all__ = ["Image2DTransformer", "image_2d_distilled_transformer", "SpatialTransformer", "ScaleUpModule"]
 
 
 _ONES = {}
@@ -587,3 +590,85 @@ def image_2d_distilled_transformer(pretrained=False, **kwargs):
     model_kwargs = dict(patch_size=16, embed_dim=768, depth=12, num_heads=12, img_size=384, distilled=True)
     model_kwargs.update(kwargs)
     return Image2DTransformer(**model_kwargs)
+
+
+class SpatialTransformer(nn.Module):
+    """reference models/transformers.py:102-135, same attribute names / state_dict keys and the same identity initialisation.
+
+    The localisation net (Conv 7x7 -> MaxPool -> ReLU -> Conv 5x5 -> MaxPool -> ReLU -> global average -> two Linears) runs on torch's
+    own ops; the resampling F.grid_sample(x, F.affine_grid(theta, ...)) runs on libftx without the grid: `forward` is the dense form
+    (every pixel of the target; differentiable in theta only), `lift` the point form (only the pixels the points pick; differentiable
+    in x and theta)."""
+
+    def __init__(self, in_channels):
+        super().__init__()
+        self.localization = nn.Sequential(
+            nn.Conv2d(in_channels, 8, kernel_size=7),
+            nn.MaxPool2d(2, stride=2),
+            nn.ReLU(True),
+            nn.Conv2d(8, 10 * 3 * 3, kernel_size=5),
+            nn.MaxPool2d(2, stride=2),
+            nn.ReLU(True),
+            nn.AdaptiveAvgPool2d(1))
+        self.fc_loc = nn.Sequential(
+            nn.Linear(10 * 3 * 3, 32),
+            nn.ReLU(True),
+            nn.Linear(32, 3 * 2))
+        self.fc_loc[2].weight.data.zero_()
+        self.fc_loc[2].bias.data.copy_(torch.tensor([1, 0, 0, 0, 1, 0], dtype=torch.float))
+
+    def theta(self, x):
+        """The (B, 2, 3) affine matrices the localisation net reads off x."""
+        # localization[6] is AdaptiveAvgPool2d(1): the plain mean is the same number, and its backward is a broadcast, not the
+        # adaptive pool's scatter
+        xs = self.localization[:6](x).mean((2, 3))
+        return self.fc_loc(xs).view(-1, 2, 3)
+
+    def forward(self, x, output_shape):
+        theta = self.theta(x)
+        size = tuple(int(v) for v in output_shape[-2:])
+        if not x.is_cuda:   # host-side checks of the module tree only; the product path is the kernel
+            grid = F.affine_grid(theta, (x.shape[0], x.shape[1]) + size, align_corners=False)
+            return F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+        from .. import functional as spf
+        return spf.affine_sample(x, theta.contiguous(), size)
+
+    def lift(self, x, img_idx, point_batch, H, W):
+        """Rows (N, C) of forward(x, (C, H, W)) at (point_batch, :, row, col) without forming the (H, W) map."""
+        from .. import functional as spf
+        return spf.affine_lift(x, self.theta(x).contiguous(), img_idx, point_batch, H, W)
+
+
+class ScaleUpModule(nn.Module):
+    """reference models/transformers.py:137-156: ConvTranspose2d(kernel = stride) then a SpatialTransformer to the output size.
+
+    `forward(x, output_shape)` keeps the reference signature and returns the dense map.  The reference then keeps ~20 k pixels of that
+    96 x 370 x 1226 map (174 MB per frame, written in the forward and again in the backward); `lift` is what the model calls instead: the
+    up-convolved map exists once (the localisation net reads it), the resampled map never."""
+
+    def __init__(self, input_features: int, output_features: int, kernel_size: int, stride: int):
+        super().__init__()
+        self.up_conv = nn.ConvTranspose2d(input_features, output_features, kernel_size=(kernel_size, kernel_size), stride=(stride, stride))
+        self.up_stn = SpatialTransformer(in_channels=output_features)
+
+    def up(self, x):
+        """up_conv(x) as NCHW.  kernel == stride: the output patches do not overlap, so it is one GEMM over the input pixels plus a
+        permute (the mirror image of PatchEmbed.forward), without a convolution-library search."""
+        conv = self.up_conv
+        k = conv.kernel_size
+        if (k != conv.stride or conv.padding != (0, 0) or conv.output_padding != (0, 0) or conv.dilation != (1, 1) or conv.groups != 1):
+            return conv(x)
+        B, C, gh, gw = x.shape
+        co = conv.out_channels
+        rows = x.permute(0, 2, 3, 1).reshape(B * gh * gw, C)
+        y = rows @ conv.weight.view(C, co * k[0] * k[1])
+        y = y.view(B, gh, gw, co, k[0], k[1]).permute(0, 3, 1, 4, 2, 5).reshape(B, co, gh * k[0], gw * k[1])
+        return y + conv.bias.view(1, -1, 1, 1) if conv.bias is not None else y
+
+    def forward(self, x: torch.Tensor, output_shape: tuple) -> torch.Tensor:
+        """The dense map, reference signature.  On the GPU the dense kernel gives its source no gradient and refuses one that needs it:
+        call this under torch.no_grad(); training goes through `lift`."""
+        return self.up_stn(self.up(x), output_shape)
+
+    def lift(self, x, img_idx, point_batch, H, W):
+        return self.up_stn.lift(self.up(x), img_idx, point_batch, H, W)

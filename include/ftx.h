@@ -190,6 +190,32 @@ size_t ftx_sample_down_workspace_bytes(void);
 int ftx_sample_down_fwd(const float *img, int32_t b, int32_t h, int32_t w, int32_t oh, int32_t ow, const float *conv_w, const float *conv_b, const float *gamma, const float *beta, float *running_mean, float *running_var, float momentum, float eps, int32_t training, float *out, double *saved, void *workspace, size_t workspace_bytes, void *stream);
 int ftx_sample_down_bwd(const float *img, const float *grad_out, int32_t b, int32_t h, int32_t w, int32_t oh, int32_t ow, const float *conv_w, const float *conv_b, const float *gamma, const double *saved, float *grad_conv_w, float *grad_conv_b, float *grad_gamma, float *grad_beta, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- affine grid sampling (the spatial transformers of ImageSeg) ---------
+ * F.grid_sample(src, F.affine_grid(theta, (b, ., H, W), align_corners=False), mode="bilinear", padding_mode="zeros",
+ * align_corners=False) of models/transformers.py:133-134 without the grid: output pixel (r, c) of an (H, W) target reads the source at
+ *   ix = ((t00 xn + t01 yn + t02 + 1) iw - 1) / 2,  iy likewise from row 1 of theta,  xn = (2c+1)/W - 1, yn = (2r+1)/H - 1,
+ * as the four-corner bilinear sum; corners outside the source count as 0.  src is (b, c, ih, iw) float32 addressed through
+ * src_strides = the four element strides (frame, channel, row, column) in HOST memory, all >= 0: NCHW and channels-last are the same
+ * code.  theta (b, 2, 3) float32.  b <= 128.  The dense and the point form share one device function and agree bit for bit.
+ *
+ * Dense form (SpatialTransformer.forward): out (b, c, oh, ow) NCHW, fully written. */
+int ftx_affine_sample_fwd(const float *src, const int64_t *src_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const float *theta, int32_t oh, int32_t ow, float *out, void *stream);
+/* Workspace of the two theta gradients below (per-block float64 partial rows; the last block to finish adds them in block order). */
+size_t ftx_affine_theta_workspace_bytes(int32_t b);
+/* grad_theta (b, 2, 3) from grad_out (b, c, oh, ow); no float atomics, bit-reproducible.  The dense form has no gradient for src. */
+int ftx_affine_sample_bwd_theta(const float *src, const int64_t *src_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const float *theta, const float *grad_out, int32_t oh, int32_t ow, float *grad_theta, void *workspace, size_t workspace_bytes, void *stream);
+/* Point form (ScaleUpModule + get_img_feats, models/image_models_stn.py:88-98): img_idx (n, 2) int64 (row, col) in the (H, W) target,
+ * point_batch (n) int32; out (n, c) = the rows the dense result would hold at (point_batch, :, row, col).  A point whose frame or
+ * pixel is out of range gives a zero row and takes no gradient.  The (H, W) map is never materialised. */
+int ftx_affine_lift_fwd(const float *src, const int64_t *src_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const float *theta, const int64_t *img_idx, const int32_t *point_batch, int64_t n, int32_t H, int32_t W, float *out, void *stream);
+/* cells[i] = flat key ((frame, y0 + 1, x0 + 1) in (b, ih + 1, iw + 1)) of the top-left source cell (y0, x0) of point i's sample, so a
+ * sample that is half outside still has a key; -1 for a point that contributes nothing.  Keys for ftx_segment_build. */
+int ftx_affine_lift_cells(const float *theta, const int64_t *img_idx, const int32_t *point_batch, int64_t n, int32_t b, int32_t ih, int32_t iw, int32_t H, int32_t W, int32_t *cells, void *stream);
+/* Backward of the point form from grad_out (n, c).  grad_src (NULL: skipped): same shape and strides as src, every element written
+ * once -- each gathers from the four segments (order, seg_off: ftx_segment_build over ftx_affine_lift_cells' keys, m = b (ih+1) (iw+1))
+ * that can touch it, in a fixed order.  grad_theta (NULL: skipped): (b, 2, 3), needs the workspace.  No float atomics. */
+int ftx_affine_lift_bwd(const float *src, const int64_t *src_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const float *theta, const int64_t *img_idx, const int32_t *point_batch, const float *grad_out, int64_t n, int32_t H, int32_t W, const int32_t *order, const int32_t *seg_off, float *grad_src, float *grad_theta, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sparse convolution (spnn.Conv3d fwd/bwd) ----------------------------
  * Pair-list gather-GEMM + ordered reduce (exact-fp32 MFMA, no float atomics, bit-reproducible):
  *   forward       tmp = pairs_gemm(A=in,   gather=pair_in,  W, 0);  out = reduce(tmp, pos,   n_out)

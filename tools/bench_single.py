@@ -1,6 +1,7 @@
-"""Step time of the single-modality baselines (LidarSeg, ImageSegBilinear) and time of the single-head loss kernel.
+"""Step time of the single-modality baselines (LidarSeg, ImageSegBilinear, ImageSeg) and time of the single-head loss kernel.
 
 usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/single_modality_steps.json]
+       python tools/bench_single.py --image-stn [--steps 60] [--out profiles/image_stn_steps.json]   # only: ImageSeg beside ImageSegBilinear
        python tools/bench_single.py --native-index-ab [--steps 20]     # LidarSeg steps, native index build off / on, alternating windows
        python tools/bench_single.py --native-train-ab [--steps 20] [--ab-model LidarSeg|middle]   # the same for the training executor
        python tools/bench_single.py --native-train-steps on|off --steps N     # N untimed batch-1 steps, to count launches under a kernel trace
@@ -45,7 +46,7 @@ def step_time(kind, batch, steps, warmup):
     from fusiontransformer_amd import config
     from fusiontransformer_amd.models.build import build_model
     from fusiontransformer_amd.trainer import TrainStep
-    cfg = config.lidar_cfg() if kind == "LidarSeg" else config.image_cfg()
+    cfg = {"LidarSeg": config.lidar_cfg, "ImageSegBilinear": config.image_cfg, "ImageSeg": config.image_stn_cfg}[kind]()
     torch.manual_seed(0)
     model, metric = build_model(cfg)
     model = model.cuda().train()
@@ -271,6 +272,7 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "single_modality_steps.json"))
+    ap.add_argument("--image-stn", action="store_true", help="only: step time of ImageSeg (spatial transformers) beside ImageSegBilinear, batch 4 and 1")
     ap.add_argument("--native-index-ab", action="store_true", help="only: LidarSeg step time with SPVCNN.set_native_index off / on, batch 1 and 4")
     ap.add_argument("--native-train-ab", action="store_true", help="only: step time with SPVCNN.set_native_train off / on, batch 1 and 4")
     ap.add_argument("--ab-model", default="LidarSeg", choices=["LidarSeg", "middle"], help="the model of --native-train-ab")
@@ -291,6 +293,22 @@ def main():
         return
     if args.steps < 50:
         raise SystemExit("bench_single: at least 50 timed steps")
+    if args.image_stn:
+        result = {"what": "image-only train steps on synthetic KITTI-shaped frames (two alternating resident batches, HIP events, profiler "
+                          "off): ImageSeg (learned affine resampling, eager trunk, torch convolutions in the localisation nets) beside "
+                          "ImageSegBilinear (fixed nearest resampling, trunk as HIP graphs)",
+                  "device": torch.cuda.get_device_name(0), "steps": []}
+        for kind in ("ImageSegBilinear", "ImageSeg"):
+            for batch in (4, 1):
+                r = step_time(kind, batch, args.steps, args.warmup)
+                print(json.dumps(r), flush=True)
+                result["steps"].append(r)
+        out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "image_stn_steps.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+        print("wrote", out)
+        return
     result = {"what": "single-modality train steps on synthetic KITTI-shaped frames (two alternating resident batches, HIP events, "
                       "profiler off) and the single-head loss kernel beside the fused two-head kernel fed one tensor twice",
               "device": torch.cuda.get_device_name(0), "steps": []}
