@@ -155,6 +155,17 @@ SIGNATURES = {
     "ftx_spvcnn_index_levels": (C.c_int, [_vp, _i64, _f32, _f32, _vp, _sz, _vp, _vp]),
     "ftx_spvcnn_index_maps": (C.c_int, [_vp, _i64, _f32, _f32, _vp, _i32, _vp, _i32, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ftx_spvcnn_index_pairs": (C.c_int, [_i64, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ftx_vit_patch_embed_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_vit_patch_embed_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_vit_tap_stem_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_vit_tap_stem_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_rows_add_bias": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "ftx_vit_model_bytes": (_i32, []),
+    "ftx_vit_block_bytes": (_i32, []),
+    "ftx_vit_tap_bytes": (_i32, []),
+    "ftx_vit_eval_arena_bytes": (_sz, [_vp, _i32, _i32]),
+    "ftx_vit_eval_release": (C.c_int, [_vp]),
+    "ftx_vit_eval": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -66,9 +66,12 @@ static_assert(kDenseGranule % DS_BK == 0, "the entry admits every multiple of kD
 // Block = 4 waves as 2 x 2, tile (64 MI) x (64 NI); wave (wm, wn) owns MI x NI 32 x 32 sub-tiles.  Three LDS images per operand,
 // [piece][row][k] bf16; the next step's global loads are issued before this step's MFMAs (register staging).
 // Rows past M and columns past N load clamped, always-valid addresses and are never stored.
+// AF (ftx_dense_common.h) says where A's rows live and what the epilogue does: DenseRows is the (M, K) matrix with dense_epilogue<EPI>,
+// DensePatches the patch embedding's unfold of an image, DenseTapRows the token buffer behind its leading rows.  Nothing else here
+// depends on it, so every form sums the same products in the same order.
 // ---------------------------------------------------------------------------------------
-template <int MI, int NI, int EPI, bool WKN>
-__global__ __launch_bounds__(256, 2) void dense_gemm_split_kernel(const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
+template <int MI, int NI, int EPI, bool WKN, class AF>
+__global__ __launch_bounds__(256, 2) void dense_gemm_split_kernel(const AF af, const float *__restrict__ W, const float *__restrict__ bias,
                                                                const float *__restrict__ pre_in, int64_t M, int N, int K, float *__restrict__ out,
                                                                float *__restrict__ pre_out) {
   constexpr int BM = 64 * MI, BN = 64 * NI;
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(256, 2) void dense_gemm_split_kernel(const float *_
 #pragma unroll
   for (int p = 0; p < AP; ++p) {
     int64_t r = m0 + p * 32 + srow;
-    arow[p] = A + (r < M ? r : M - 1) * K + sk4;
+    arow[p] = af.row(r < M ? r : M - 1);
   }
   const float *brow[BP];
   // WKN: item e = (k pair kp, column float4 n4); two float4 per item (rows 2kp, 2kp+1), stored as packed k pairs
@@ -123,8 +126,9 @@ __global__ __launch_bounds__(256, 2) void dense_gemm_split_kernel(const float *_
 
   float4 ra[AP], rb[BP];
   auto load_step = [&](int c0) {
+    const int64_t ak = af.koff(c0 + sk4);   // where the form keeps reduction index c0 + sk4 of a row
 #pragma unroll
-    for (int p = 0; p < AP; ++p) ra[p] = *(const float4 *)(arow[p] + c0);
+    for (int p = 0; p < AP; ++p) ra[p] = *(const float4 *)(arow[p] + ak);
     if constexpr (!WKN) {
 #pragma unroll
       for (int p = 0; p < BP; ++p) rb[p] = *(const float4 *)(brow[p] + c0);
@@ -212,9 +216,9 @@ __global__ __launch_bounds__(256, 2) void dense_gemm_split_kernel(const float *_
       for (int q = 0; q < 4; ++q) {
         const int n = n0 + wn * 32 * NI + j * 32 + 8 * q + 4 * half;
         if (n >= N) continue;
-        dense_epilogue<EPI>(make_float4(hh[i][j][4 * q] + corr[i][j][4 * q], hh[i][j][4 * q + 1] + corr[i][j][4 * q + 1],
-                                        hh[i][j][4 * q + 2] + corr[i][j][4 * q + 2], hh[i][j][4 * q + 3] + corr[i][j][4 * q + 3]),
-                            m * N + n, n, bias, pre_in, out, pre_out);
+        af.template store<EPI>(make_float4(hh[i][j][4 * q] + corr[i][j][4 * q], hh[i][j][4 * q + 1] + corr[i][j][4 * q + 1],
+                                           hh[i][j][4 * q + 2] + corr[i][j][4 * q + 2], hh[i][j][4 * q + 3] + corr[i][j][4 * q + 3]),
+                               m, n, N, bias, pre_in, out, pre_out);
       }
   }
 }
@@ -352,9 +356,10 @@ __global__ __launch_bounds__(256, 2) void dense_wgrad_split_kernel(const float *
 
 struct DenseSplit {
   static constexpr const char *gemm_name = "ftx_dense_gemm_split", *wgrad_name = "ftx_dense_wgrad_split";
-  template <int MI, int NI, int EPI, bool WKN>
-  static void gemm(dim3 grid, hipStream_t st, const DenseGemmArgs &a) {
-    dense_gemm_split_kernel<MI, NI, EPI, WKN><<<grid, 256, 0, st>>>(a.A, a.W, a.bias, a.pre_in, a.M, a.N, a.K, a.out, a.pre_out);
+  static constexpr const char *patch_name = "ftx_vit_patch_embed_split", *tap_name = "ftx_vit_tap_stem_split";
+  template <int MI, int NI, int EPI, bool WKN, class AF>
+  static void gemm(dim3 grid, hipStream_t st, const AF &af, const DenseGemmArgs &a) {
+    dense_gemm_split_kernel<MI, NI, EPI, WKN, AF><<<grid, 256, 0, st>>>(af, a.W, a.bias, a.pre_in, a.M, a.N, a.K, a.out, a.pre_out);
   }
   static void wgrad(dim3 grid, hipStream_t st, const float *G, const float *X, int64_t M, int N, int K, int64_t len, float *part, float *dW) {
     dense_wgrad_split_kernel<<<grid, 256, 0, st>>>(G, X, M, N, K, len, part, dW);
@@ -364,6 +369,17 @@ struct DenseSplit {
 extern "C" int ftx_dense_gemm_split(const float *A, const float *W, int32_t w_kn, const float *bias, const float *pre_in, int64_t m, int32_t n,
                                     int32_t k, int32_t epilogue, float *out, float *pre_out, void *stream) {
   return dense_gemm_entry<DenseSplit>(A, W, w_kn, bias, pre_in, m, n, k, epilogue, out, pre_out, stream);
+}
+
+extern "C" int ftx_vit_patch_embed_split(const float *img, const float *W, const float *bias, const float *cls, const float *dist, const float *pos,
+                                       int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim, int32_t t0, float *tokens, void *stream) {
+  return dense_patch_embed_entry<DenseSplit>(img, W, bias, cls, dist, pos, b, c, h, w, patch, dim, t0, tokens, stream);
+}
+
+extern "C" int ftx_vit_tap_stem_split(const float *tokens, const float *W, const float *bias, const float *gamma, const float *beta,
+                                    const float *running_mean, const float *running_var, float eps, int32_t b, int32_t g, int32_t t0, int32_t dim,
+                                    int32_t co, float *out, void *stream) {
+  return dense_tap_stem_entry<DenseSplit>(tokens, W, bias, gamma, beta, running_mean, running_var, eps, b, g, t0, dim, co, out, stream);
 }
 
 extern "C" size_t ftx_dense_wgrad_split_workspace_bytes(int64_t m, int32_t n, int32_t k) { return dense_wgrad_workspace_bytes(m, n, k); }

@@ -24,7 +24,7 @@ void set_error(const char *fmt, ...) {
 
 using namespace ftx;
 
-extern "C" int ftx_version(void) { return 101; }
+extern "C" int ftx_version(void) { return 102; }
 extern "C" const char *ftx_last_error(void) { return ftx::g_err.c_str(); }
 
 // ---------------------------------------------------------------- hashing

@@ -162,6 +162,55 @@ class Net2DBillinear(nn.Module):
         self.dual_head = dual_head
         if dual_head:
             self.linear2 = nn.Linear(self.feat_channels, num_classes)
+        # cfg.MODEL.image_native_eval: the eval-mode, no-gradient forward of the trunk through the native executor, see set_native_eval
+        self._native = None
+        self._native_reason = "the switch is off"
+        self.set_native_eval(bool(kw.get("image_native_eval", False)))
+
+    def set_native_eval(self, on=True):
+        """Opt-in native executor for the eval-mode forward of the image branch (include/ftx.h: ftx_vit_eval).  With it on, a forward in
+        eval mode, with gradients disabled, on the GPU and with fp32 parameters runs sample_down as before and then the patch embedding,
+        the live blocks and the tap stems as one library call per trunk segment (up to the middle tap, up to the late tap) over an arena
+        this module owns; the lift and the heads stay where they are.  It engages only when every live block runs the linears the library
+        owns (vit_linear_impl "ftx_split", or "ftx" with set_bf16) and one attention impl ("ftx" or "ftx_bf16"); anything else -- training
+        mode, gradients, CPU tensors, vit_linear_impl="library" -- takes the existing path exactly as with the switch off, and
+        native_eval_reason() says why."""
+        self.image_native_eval = bool(on)
+        if not on:
+            if self._native is not None:
+                self._native.release()
+            self._native = None
+            self._native_reason = "the switch is off"
+        return self
+
+    def native_eval_reason(self):
+        """Why the last forward did not run the native executor; None when it did."""
+        return self._native_reason
+
+    def _native_executor(self, img):
+        """The executor when this forward is one it runs (see set_native_eval), else None (and the reason is kept)."""
+        why = None
+        if not self.image_native_eval:
+            why = "the switch is off"
+        elif self.training or self.backbone.training or any(m.training for m in self.up.values()) or self.sample_down.training:
+            why = "training mode"
+        elif torch.is_grad_enabled():
+            why = "gradients are enabled"
+        elif not img.is_cuda:
+            why = "the image is not on the GPU"
+        elif torch.cuda.is_current_stream_capturing():
+            why = "the stream is being captured"
+        else:
+            from .. import native_image
+            try:
+                if self._native is None:
+                    native_image.modes(self)      # a trunk the executor does not run builds nothing
+                    self._native = native_image.NativeImage(self)
+                self._native.ready()      # one pass over the live modules; tables and modes are cached behind it
+            except native_image.Unsupported as err:
+                why = str(err)
+        self._native_reason = why
+        return self._native if why is None else None
 
     def _lift_hw(self, image_shape, lift_size=None):
         """Size of the (never materialised) up-sampled map.  The reference hard-codes (370, 1226)
@@ -208,6 +257,9 @@ class Net2DBillinear(nn.Module):
         stream, only waits for this and not for the rest of the ViT); `on_step()` after every issued
         chunk of work (the scheduler uses it to interleave the other branch's kernel launches)."""
         img_indices = pack_img_indices(img_indices, img.device)
+        ex = self._native_executor(img)
+        if ex is not None:
+            return self._forward_native(ex, img, img_indices, on_middle, on_step, lift_size)
         lift_ctx = {}     # per-forward: both taps share one sort of the points by source cell
         x = self.sample_down(img)
         if on_step is not None:
@@ -231,4 +283,39 @@ class Net2DBillinear(nn.Module):
             preds["img_seg_logit2"] = spf.linear(late_feats, self.linear2.weight, self.linear2.bias)
         if self.middle_feat_block_number:
             preds["img_middle_feats"] = middle["feats"]
+        return preds
+
+    def _forward_native(self, ex, img, img_indices, on_middle, on_step, lift_size):
+        """forward through the native executor: one call up to the middle tap (its lifted features go to on_middle at once), one up to
+        the late tap; the same callbacks and the same preds."""
+        idx, frame = img_indices
+        H, W = self._lift_hw(img.shape, lift_size)
+        x = self.sample_down(img)
+        if on_step is not None:
+            on_step()
+        run = ex.begin(x)
+        late = int(self.late_feat_block_number)
+        mid = self.middle_feat_block_number
+        has_mid = mid is not None and mid in self.up
+        middle_feats, first = None, 0
+        if has_mid and int(mid) != late:
+            middle_feats = spf.lift_gather(run.run(0, int(mid))[int(mid)], idx, frame, H, W)
+            if on_middle is not None:
+                on_middle(middle_feats)
+            if on_step is not None:
+                on_step()
+            first = int(mid) + 1
+        grid = run.run(first, late)[late]
+        if has_mid and int(mid) == late:
+            middle_feats = spf.lift_gather(grid, idx, frame, H, W)
+            if on_middle is not None:
+                on_middle(middle_feats)
+        if on_step is not None:
+            on_step()
+        late_feats = spf.lift_gather(grid, idx, frame, H, W)
+        preds = {"img_feats": late_feats, "img_seg_logit": spf.linear(late_feats, self.linear.weight, self.linear.bias)}
+        if self.dual_head:
+            preds["img_seg_logit2"] = spf.linear(late_feats, self.linear2.weight, self.linear2.bias)
+        if self.middle_feat_block_number:
+            preds["img_middle_feats"] = middle_feats
         return preds

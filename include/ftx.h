@@ -684,6 +684,73 @@ int ftx_spvcnn_index_levels(const float *coords, int64_t n, float init_res, floa
 int ftx_spvcnn_index_maps(const float *coords, int64_t n, float init_res, float after_res, const float *feats, int32_t c_in, const int32_t *level_off_host, int32_t with_backward_segments, void *arena_a, size_t arena_a_bytes, void *arena_b, size_t arena_b_bytes, int32_t *pair_counts_pinned, void *stream);
 int ftx_spvcnn_index_pairs(int64_t n, int32_t c_in, const int32_t *level_off_host, int32_t with_backward_segments, const int32_t *pair_counts_host, void *arena_a, void *arena_b, size_t arena_b_bytes, void *arena_c, size_t arena_c_bytes, int64_t *rows_host, void *maps_host, void *pvs_host, const float **x0, void *stream);
 
+/* ---- the ViT image branch in eval mode: patch embedding, tap stems and the trunk executor (models/transformers.py:16-45,90-100,
+ *      models/image_models_billinear.py:8-24,88-126) (csrc/ftx_dense_common.h, csrc/ftx_exec_vit.hip) ----
+ * Two A-addressing forms of the dense GEMM families above.  The tile rule, the piece split, the accumulator order and the reduction
+ * order are those of ftx_dense_gemm_split / ftx_dense_gemm_bf16 (the precision contracts above hold unchanged), so each form returns
+ * the bits of that entry run with FTX_EPI_BIAS on a materialised copy of its A, followed by its own epilogue.
+ *
+ * ftx_vit_patch_embed_<split|bf16>: tokens (b, t0 + gh gw, dim) from img (b, c, h, w) float32 (what ftx_sample_down_fwd wrote), gh = h /
+ * patch, gw = w / patch.  A is never materialised: row (frame, gy, gx), reduction index k = (ci, py, px) reads img[frame][ci][gy patch +
+ * py][gx patch + px].  W: the Conv2d weight (dim, c, patch, patch) viewed (dim, c patch patch); bias (dim).  Epilogue, in this rounding
+ * order: tokens[frame][t0 + patch] = (sum + bias) + pos[t0 + patch], pos (t0 + gh gw, dim).  One more small launch writes the leading
+ * rows: tokens[frame][0] = cls + pos[0] and, with t0 = 2, tokens[frame][1] = dist + pos[1] (cls, dist (dim); dist may be NULL only with
+ * t0 = 1).  Refused before anything is launched: c patch patch % 64 != 0, dim % 4 != 0, patch % 4 != 0, h or w not whole patches, t0
+ * outside {1, 2}, null or not 16-byte aligned pointers.  b == 0 returns FTX_OK without launching.
+ *
+ * ftx_vit_tap_stem_<split|bf16>: BilinearModule's stem on the token grid in eval mode, one launch: out (b, g, co) = BatchNorm(ReLU(
+ * tokens[:, t0:] W^T + bias)), tokens (b, t0 + g, dim), W (co, dim).  Row r of A is token row (r / g) (t0 + g) + t0 + r % g.  Epilogue
+ * order: bias, ReLU, then the eval-mode BatchNorm with the rounding sequence of ftx_bn_eval_fwd.  out is (b, gh, gw, co) channels-last:
+ * what ftx_lift_gather_fwd reads.  dim % 64 == 0, co % 4 == 0, t0 in {0, 1, 2}.
+ *
+ * ftx_rows_add_bias: out (n, c) = r + (p + pb), pb (c) broadcast over the rows, in that rounding order (the residual stream of the
+ * trunk as one tensor).  p and pb NULL together: out = r.  c % 4 == 0, 16-byte aligned pointers. */
+int ftx_vit_patch_embed_split(const float *img, const float *W, const float *bias, const float *cls, const float *dist, const float *pos, int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim, int32_t t0, float *tokens, void *stream);
+int ftx_vit_patch_embed_bf16(const float *img, const float *W, const float *bias, const float *cls, const float *dist, const float *pos, int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim, int32_t t0, float *tokens, void *stream);
+int ftx_vit_tap_stem_split(const float *tokens, const float *W, const float *bias, const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *out, void *stream);
+int ftx_vit_tap_stem_bf16(const float *tokens, const float *W, const float *bias, const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *out, void *stream);
+int ftx_rows_add_bias(const float *r, const float *p, const float *pb, int64_t n, int32_t c, float *out, void *stream);
+
+/* ftx_vit_eval: the eval-mode, no-gradient forward of blocks [block_first, block_last] of the trunk, with the tap stems behind the
+ * tapped blocks.  Tables: packed little-endian records in HOST memory holding device pointers (float32, contiguous); the library
+ * reports each record size (ftx_vit_*_bytes).
+ *   model (one record): const float *patch_w (dim, in_chans patch patch), *patch_b (dim), *cls (dim), *dist (dim, NULL with t0 = 1),
+ *     *pos (t0 + grid grid, dim); int32 dim, heads, hidden (the MLP width), patch, grid (patches per side: the image is (in_chans,
+ *     grid patch, grid patch)), t0 (1, or 2 for a distilled trunk), in_chans; float eps (of every LayerNorm).
+ *   block (n_blocks records): const float *norm1_w, *norm1_b, *qkv_w (3 dim, dim), *qkv_b, *proj_w (dim, dim), *proj_b, *norm2_w,
+ *     *norm2_b, *fc1_w (hidden, dim), *fc1_b, *fc2_w (dim, hidden), *fc2_b.
+ *   tap (n_taps records, ascending by block): const float *stem_w (co, dim), *stem_b, *gamma, *beta, *running_mean, *running_var (co);
+ *     int32 block, co; float eps; int32 reserved.  tap_out_host[i]: where tap i goes, (b, grid, grid, co) float32 on the device.
+ * A call with block_first = 0 starts from tokens_in (b, t0 + grid grid, dim) if it is given, else from img (b, in_chans, grid patch, grid
+ * patch) through ftx_vit_patch_embed_*; a call with block_first > 0 continues from the residual state the previous call left in the
+ * arena (which must have ended at block_first - 1, for the same b), so a fusion caller runs to the middle tap, hands the lifted features
+ * to the LiDAR stream and continues.  Per block the call issues what transformers.Block.chain issues: ftx_add_layernorm_fwd (y NULL on
+ * the first block, else the previous block's MLP output with fc2's bias as y_bias), the qkv GEMM with FTX_EPI_BIAS, attention (scale
+ * 1/8), the proj GEMM with FTX_EPI_NONE, ftx_add_layernorm_fwd with y_bias = proj's bias, fc1 with FTX_EPI_BIAS_GELU, fc2 with
+ * FTX_EPI_NONE.  linear_mode: 0 = ftx_dense_gemm_split, 1 = ftx_dense_gemm_bf16 (and the matching patch embedding and tap stem);
+ * attn_mode: 0 = ftx_attn_fwd_tiled(..., 0, 0) (the automatic tiling, what ftx_attn_fwd runs), 1 = ftx_attn_fwd_bf16(..., 0, 0).  At a tap the stream r + (p + pb) becomes one tensor (ftx_rows_add_bias) and
+ * ftx_vit_tap_stem_* writes tap_out_host[i]; both residual forms round in that order, so the results do not depend on where a caller
+ * materialises.  Taps in front of block_first are skipped (an earlier call wrote them).
+ * Refused before the first launch (FTX_EINVAL): heads * 64 != dim, dim outside {256, 512, 768, 1024}, hidden % 64 != 0, taps not
+ * ascending or past block_last, a null or not 16-byte aligned parameter of a block or tap the call runs (the tap's BatchNorm vectors
+ * need no alignment), a misaligned tap output, block_first > 0 on an arena that holds no state for this b; an arena that is too small
+ * is FTX_EWORKSPACE.  b == 0 returns FTX_OK.
+ * Arena: device memory, 256-byte aligned, caller-owned; ftx_vit_eval_arena_bytes(model, n_blocks, b) is a host function (needs no GPU;
+ * 0 and an error text for a record it refuses), a multiple of 256, and grows with b.  No host synchronisation and no allocation: a call
+ * can be captured into a HIP graph.  The one thing the library keeps beyond a call is a host-side note, per arena address, of the b and
+ * the block its residual state stands in front of: the signature above has no other place for it, and the state itself is device
+ * memory the host must not read.  The note is written when a call is ISSUED.  It vouches for the order of the calls a host makes, not
+ * for the arena's contents: a captured continuation (block_first > 0) is checked once, at capture, and a replay runs on whatever the
+ * arena then holds, so a caller that replays it must replay (or issue) the calls in front of it on that arena first, with nothing else
+ * using the arena in between.  ftx_vit_eval_release(arena) drops the note (host only, always FTX_OK): call it before freeing an arena
+ * or giving its memory another use, otherwise a later buffer at the same address with the same b would pass for a continuation. */
+int32_t ftx_vit_model_bytes(void);
+int32_t ftx_vit_block_bytes(void);
+int32_t ftx_vit_tap_bytes(void);
+size_t ftx_vit_eval_arena_bytes(const void *model_host, int32_t n_blocks, int32_t b);
+int ftx_vit_eval_release(const void *arena);
+int ftx_vit_eval(const void *model_host, const void *blocks_host, int32_t n_blocks, const void *taps_host, int32_t n_taps, int32_t b, const float *img, const float *tokens_in, int32_t block_first, int32_t block_last, int32_t linear_mode, int32_t attn_mode, float *const *tap_out_host, void *arena, size_t arena_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,12 @@ Per (model, batch, switch) and over `--windows` windows of `--steps` forwards, t
   lidar ms / forward  HIP events on the stream that runs the LiDAR branch, from the end of the previous forward's work to the end of
                       this one's
   arena / peak bytes  the executor's arena, and torch's peak allocation above the resident state during a window
+Mode `image` is a measurement of its own: the same eval workload on the fusion models with vit_linear_impl="ftx_split" (the fp32
+linears the library owns), the native executor of the IMAGE branch (Net2DBillinear.set_native_eval) off and on, the LiDAR branch on its
+default path.  It reports wall and issue ms as above and the HIP-event time of the stream that runs the image branch.
 usage:
   python tools/bench_eval.py [--models lidar,middle] [--batches 1,4] [--windows 5] [--steps 20] [--modes off,on,index]
+  python tools/bench_eval.py --modes image [--models middle] [--batches 1,4]       # A/B of the image branch's switch
       --modes off also runs on a checkout that has no executor (the baseline of the comparison)
       --mark-launches also traces one index build on its own per setting ("... index build" in the count)
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/bench_eval.py --mark-launches   # one marked forward per setting
@@ -49,6 +53,64 @@ def count_launches(trace_dir):
             print("    kernels busy %.1f us inside a span of %.1f us: %s" % (busy, span, ", ".join("%s x%d" % kv for kv in sorted(names.items(), key=lambda kv: -kv[1]))))
 
 
+def image_ab(a):
+    """Mode `image`: Net2DBillinear.set_native_eval off / on, alternating window by window in one process."""
+    import torch
+    from bench import build_inputs
+    from fusiontransformer_amd import gemm_tuning
+    from fusiontransformer_amd.config import fusion_cfg
+    from fusiontransformer_amd.models._fusion_common import _branch_streams
+    from fusiontransformer_amd.models.build import build_model
+    assert torch.cuda.is_available(), "bench_eval measures on the GPU; there is no CPU figure"
+    gemm_tuning.enable(0)
+    dev = torch.device("cuda")
+    fmt = lambda v: "%.3f (%.3f..%.3f)" % (statistics.median(v), min(v), max(v))
+    for kind in (k for k in a.models.split(",") if k != "lidar"):
+        cfg = fusion_cfg(kind)
+        cfg.MODEL.vit_linear_impl = "ftx_split"
+        torch.manual_seed(0)
+        model = build_model(cfg)[0].cuda().eval()
+        net = model.image_backbone
+        if not hasattr(net, "set_native_eval"):
+            sys.exit("this checkout has no native executor of the image branch")
+        image_stream = _branch_streams(dev)[0]
+        for batch in (int(b) for b in a.batches.split(",")):
+            datas = [build_inputs(cfg, batch, "kitti", 0, dev, cycle=c)[1] for c in range(2)]
+            with torch.no_grad():
+                for on in (False, True):
+                    net.set_native_eval(on)
+                    for i in range(a.warmup):
+                        model(datas[i % 2])
+                    assert not on or net.native_eval_reason() is None, net.native_eval_reason()
+                torch.cuda.synchronize()
+                res = {on: {"wall": [], "issue": [], "image": []} for on in (False, True)}
+                for w in range(a.windows):
+                    for on in ((False, True) if w % 2 == 0 else (True, False)):
+                        net.set_native_eval(on)
+                        model(datas[1])
+                        torch.cuda.synchronize()
+                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                        ev[0].record(image_stream)
+                        t0 = time.perf_counter()
+                        for i in range(a.steps):
+                            model(datas[i % 2])
+                        ev[1].record(image_stream)
+                        t1 = time.perf_counter()
+                        torch.cuda.synchronize()
+                        t2 = time.perf_counter()
+                        r = res[on]
+                        r["wall"].append((t2 - t0) / a.steps * 1e3)
+                        r["issue"].append((t1 - t0) / a.steps * 1e3)
+                        r["image"].append(ev[0].elapsed_time(ev[1]) / a.steps)
+                        r["arena"] = sum(b.shape[0] for b in net._native.arenas.values()) if (on and net._native) else 0
+                for on in (False, True):
+                    r = res[on]
+                    arena = r.get("arena", 0)
+                    print("%-6s batch %d image native %-3s  wall %s ms  issue %s ms  image stream %s ms  arena %.1f MiB" % (
+                        kind, batch, "on" if on else "off", fmt(r["wall"]), fmt(r["issue"]), fmt(r["image"]), arena / 2 ** 20), flush=True)
+        del model
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="lidar,middle")
@@ -63,6 +125,8 @@ def main():
     a = ap.parse_args()
     if a.count_launches:
         return count_launches(a.count_launches)
+    if a.modes == "image":
+        return image_ab(a)
 
     import torch
     from bench import build_inputs
