@@ -21,6 +21,9 @@ inline int check_launch(const char *what) {
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Arena pieces start on 256-byte boundaries.
+inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
+
 // Grid for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8, no more.
 inline unsigned grid_for(int64_t work, int block) {
   int64_t g = ceil_div(work, block);

@@ -62,7 +62,6 @@ static_assert(sizeof(Model) == 72 && sizeof(Block) == 96 && sizeof(Tap) == 64, "
 constexpr int kMaxBlocks = 64;
 constexpr int kMaxBatch = 4096;
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // Where everything lives, in bytes from the arena's start.  A function of (model sizes, b) alone.
@@ -71,24 +70,16 @@ struct Plan {
   int64_t r[2] = {0, 0}, m = 0, h = 0, qkv = 0, att = 0, proj = 0, pre = 0, act = 0, x = 0, lse = 0, stats = 0, total = 0;
 };
 
-#define VIT_REQUIRE(cond, ...)  \
-  do {                          \
-    if (!(cond)) {              \
-      set_error(__VA_ARGS__);   \
-      return FTX_EINVAL;        \
-    }                           \
-  } while (0)
-
 int check_model(const char *who, const Model *M, int32_t n_blocks, int32_t b) {
-  VIT_REQUIRE(M, "%s: null model record", who);
-  VIT_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "%s: block count %d outside [1, %d]", who, n_blocks, kMaxBlocks);
-  VIT_REQUIRE(b >= 0 && b <= kMaxBatch, "%s: batch %d outside [0, %d]", who, b, kMaxBatch);
-  VIT_REQUIRE(M->dim == 256 || M->dim == 512 || M->dim == 768 || M->dim == 1024, "%s: dim %d is not one the LayerNorm kernel takes (256, 512, 768, 1024)", who,
+  FTX_REQUIRE(M, "%s: null model record", who);
+  FTX_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "%s: block count %d outside [1, %d]", who, n_blocks, kMaxBlocks);
+  FTX_REQUIRE(b >= 0 && b <= kMaxBatch, "%s: batch %d outside [0, %d]", who, b, kMaxBatch);
+  FTX_REQUIRE(M->dim == 256 || M->dim == 512 || M->dim == 768 || M->dim == 1024, "%s: dim %d is not one the LayerNorm kernel takes (256, 512, 768, 1024)", who,
               M->dim);
-  VIT_REQUIRE(M->heads >= 1 && M->heads * 64 == M->dim, "%s: heads * 64 != dim (heads=%d dim=%d)", who, M->heads, M->dim);
-  VIT_REQUIRE(M->hidden >= 64 && M->hidden % 64 == 0 && M->hidden <= 16384, "%s: hidden must be a multiple of 64 (hidden=%d)", who, M->hidden);
-  VIT_REQUIRE(M->t0 == 1 || M->t0 == 2, "%s: t0 must be 1 or 2 (t0=%d)", who, M->t0);
-  VIT_REQUIRE(M->patch >= 4 && M->patch % 4 == 0 && M->patch <= 64 && M->grid >= 1 && M->grid <= 256 && M->in_chans >= 1 && M->in_chans <= 64,
+  FTX_REQUIRE(M->heads >= 1 && M->heads * 64 == M->dim, "%s: heads * 64 != dim (heads=%d dim=%d)", who, M->heads, M->dim);
+  FTX_REQUIRE(M->hidden >= 64 && M->hidden % 64 == 0 && M->hidden <= 16384, "%s: hidden must be a multiple of 64 (hidden=%d)", who, M->hidden);
+  FTX_REQUIRE(M->t0 == 1 || M->t0 == 2, "%s: t0 must be 1 or 2 (t0=%d)", who, M->t0);
+  FTX_REQUIRE(M->patch >= 4 && M->patch % 4 == 0 && M->patch <= 64 && M->grid >= 1 && M->grid <= 256 && M->in_chans >= 1 && M->in_chans <= 64,
               "%s: patch %d (a multiple of 4), grid %d or channels %d out of range", who, M->patch, M->grid, M->in_chans);
   return FTX_OK;
 }

@@ -29,8 +29,6 @@ constexpr int kPvLevel[kNPV] = {0, 4, 2};     // strides 1, 16, 4: the order of 
 constexpr int kScanChunk = 4096;              // elements per block of the validity scan (256 threads x 16)
 constexpr int kLayoutWords = 105;
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 struct Lay {
   int64_t n = 0, c = 0;
   int64_t nl[kNL] = {}, off[kNL + 1] = {}, cap[kNL] = {}, pairs[kNL] = {};

@@ -1,6 +1,8 @@
 // Table records of the SPVCNN entry points (layouts documented in include/ftx.h).  The batch tables (map, pv) are read by ftx_spvcnn_eval
 // (ftx_exec.hip) and ftx_spvcnn_train_fwd / _bwd (ftx_exec_train.hip) and written by ftx_spvcnn_index_pairs (ftx_native_index.hip); the model
 // table (layer), the program (op) and the train-only side tables are the two executors'.  ftx_spvcnn_*_bytes report their sizes.
+// What the two executors do with these records on the host before they place or launch anything -- the view of one call's tables,
+// the two sides of a kernel map, the checker of the program -- is ftx_spvcnn_program.h.
 #pragma once
 #include <stdint.h>
 

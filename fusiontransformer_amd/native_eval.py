@@ -245,19 +245,17 @@ def arena_bytes(layers, ops, rows, maps, pvs, routes) -> int:
     return n
 
 
-class NativeEval:
-    """Per-module state of the executor: the program, the model table (rebuilt when a parameter moved or the bf16 switch changed) and one
-    arena per (device, stream)."""
+class _Host:
+    """What both executors keep per module: the program, its op table and the model table (rebuilt when a parameter moved or the bf16
+    switch changed)."""
 
-    def __init__(self, net):
-        check_record_sizes()
-        self.program = emit_program(net)
-        self.ops = self.program.ops_array()
-        self.refs = [r for l in self.program.layers for r in l["refs"] if r is not None]
-        self.modules = [l["module"] for l in self.program.layers]
+    def __init__(self, program):
+        self.program = program
+        self.ops = program.ops_array()
+        self.refs = [r for l in program.layers for r in l["refs"] if r is not None]
+        self.modules = [l["module"] for l in program.layers]
         self.key = None
         self.layers = None
-        self.arenas = {}
 
     def model_table(self):
         key = tuple([d[n].data_ptr() for d, n in self.refs] + [getattr(m, "ftx_bf16", False) for m in self.modules])
@@ -265,6 +263,15 @@ class NativeEval:
             self.layers = layer_table(self.program)
             self.key = key
         return self.layers
+
+
+class NativeEval(_Host):
+    """Per-module state of the executor: the program, the model table and one arena per (device, stream)."""
+
+    def __init__(self, net):
+        check_record_sizes()
+        super().__init__(emit_program(net))
+        self.arenas = {}
 
     def arena(self, nbytes, device):
         st = _lib.stream()

@@ -153,28 +153,15 @@ def _alias(storage, byte_offset, shape, device):
     return torch.empty(0, dtype=torch.float32, device=device).set_(storage, byte_offset // 4, shape)
 
 
-class NativeTrain:
-    """Per-module state of the training executor: the program and the model table (rebuilt when a parameter moved or the bf16 switch
-    changed).  Runs are per forward."""
+class NativeTrain(ne._Host):
+    """Per-module state of the training executor: the program and the model table.  Runs are per forward."""
 
     def __init__(self, net):
         check_record_sizes()
         self.tp = TrainProgram(net)
-        self.program = self.tp.program
-        self.ops = self.program.ops_array()
-        self.refs = [r for l in self.program.layers for r in l["refs"] if r is not None]
-        self.modules = [l["module"] for l in self.program.layers]
-        self.key = None
-        self.layers = None
+        super().__init__(self.tp.program)
         self.runs = 0              # forwards this executor ran (the tests' witness)
         self.last_arena_bytes = 0
-
-    def model_table(self):
-        key = tuple([d[n].data_ptr() for d, n in self.refs] + [getattr(m, "ftx_bf16", False) for m in self.modules])
-        if key != self.key:
-            self.layers = ne.layer_table(self.program)
-            self.key = key
-        return self.layers
 
     def trainable(self):
         return all(p.requires_grad for p in self.tp.parameters())
