@@ -22,9 +22,8 @@
 // of four MFMAs is ONE ds_read_b128 (row stride 36 floats -> conflict-free).
 #include <cstring>
 #include <cstdlib>
-#include "ftx_common.h"
 #include "ftx_bn_eval_op.h"
-#include "ftx_mfma.h"
+#include "ftx_spconv_common.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -123,14 +122,13 @@ extern "C" int ftx_kernel_map_pairs(const int32_t *nbr, int64_t n_out, int64_t n
 // ---------------------------------------------------------------------------------------
 // phase 1: tmp[p,:] = A[gather[p],:] @ Wk(p)        (tiles of 128 pairs of one offset)
 // ---------------------------------------------------------------------------------------
-constexpr int BK = 32;         // reduction chunk staged per step
 constexpr int AS_STRIDE = 36;  // floats
-constexpr int TILE_P = 128;    // pairs per tile and row-tile count RT: tile = RT x (4 waves x 32 pairs)
 
-// NT = 32-column tiles per wave, RT = 32-pair row tiles per wave.  RT = 2 (256-pair tiles) halves the
-// W[k] traffic, the B-operand LDS reads and the barriers per MFMA; used when every offset has
-// enough pairs that the padding of its last tile does not matter.
-template <int NT, int RT>
+// NT = 32-column tiles per wave; a wave owns one 32-pair row tile of the block's kPairTile pairs.
+// Measured on MI355X (profiles/r01_spconv_layer_micro.txt workload): 256-pair tiles (RT = 2 row tiles per wave) are 5-30 % SLOWER than
+// 128-pair tiles on every layer -- the extra accumulators cut occupancy to 1-2 waves per SIMD and the kernel is latency-, not
+// W-traffic-bound: RT = 1 everywhere, so the kernel has no such parameter.
+template <int NT>
 __global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict__ A, int64_t rows_a, const int32_t *__restrict__ gather,
                                                          const float *__restrict__ W, int w_transposed, const int32_t *__restrict__ koff,
                                                          int ca, int co, int kvol, float *__restrict__ tmp, const float *__restrict__ bias,
@@ -138,48 +136,17 @@ __global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict
   // gather == nullptr: dense mode, tmp[r,:] = A[r,:] @ W (+ bias) for r < n_dense (kvol = 1)
   // scatter != nullptr: the result row of pair p goes to row scatter[p] of `tmp` (rows_out rows) instead of row p: for maps in
   // which every destination row receives exactly ONE pair the convolution is this one launch, with no tmp and no reduce pass
-  constexpr int TILE = TILE_P * RT;
   constexpr int BN = 32 * NT;
   constexpr int BS_STRIDE = AS_STRIDE;         // W chunk kept as Bs[n][k]: the reduction index is contiguous for BOTH operands
-  constexpr int B_PASSES = NT;                 // BK * BN / 4 float4 per W chunk = NT * 256
-  constexpr int A_PASSES = 4 * RT;
+  constexpr int A_PASSES = kPairAPasses;
+  constexpr int B_PASSES = NT;                 // kPairBK * BN / 4 float4 per W chunk = NT * 256
 
-  __shared__ __attribute__((aligned(16))) float As[TILE * AS_STRIDE];
+  __shared__ __attribute__((aligned(16))) float As[kPairTile * AS_STRIDE];
   __shared__ __attribute__((aligned(16))) float Bs[BN * BS_STRIDE];
   __shared__ int s_tile[3];
 
   const int tid = threadIdx.x;
-  if (gather == nullptr) {
-    if (tid == 0) {
-      int64_t left = n_dense - (int64_t)blockIdx.x * TILE;
-      s_tile[0] = left > 0 ? 0 : -1;
-      s_tile[1] = blockIdx.x * TILE;
-      s_tile[2] = left > TILE ? TILE : (int)left;
-    }
-  } else if (tid < 64) {
-    // tile -> (offset, first pair, pair count): wave 0 scans the per-offset tile counts
-    const int lane0 = tid;
-    const int b = blockIdx.x;
-    int c = (lane0 < kvol) ? koff[lane0 + 1] - koff[lane0] : 0;
-    int nt = (c + TILE - 1) / TILE;
-    int incl = nt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      int v = __shfl_up(incl, off, 64);
-      if (lane0 >= off) incl += v;
-    }
-    int excl = incl - nt;
-    bool mine = (lane0 < kvol) && b >= excl && b < incl;
-    unsigned long long m = __ballot(mine);
-    if (mine) {
-      int t = b - excl;
-      int left = c - t * TILE;
-      s_tile[0] = lane0;
-      s_tile[1] = koff[lane0] + t * TILE;
-      s_tile[2] = left > TILE ? TILE : left;
-    }
-    if (m == 0ull && lane0 == 0) s_tile[0] = -1;
-  }
+  gemm_tile_scan(koff, kvol, n_dense, gather == nullptr, s_tile);
   __syncthreads();
   const int k = s_tile[0];
   if (k < 0) return;  // surplus block of the upper-bound grid
@@ -190,31 +157,20 @@ __global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict
   const int n0 = blockIdx.y * BN;
   const int arow = tid >> 3, acol = (tid & 7) * 4;
 
-  // Gathers are unconditional loads from addresses that are always valid: rows past the end of the tile (and malformed
-  // indices) read row 0 -- what they produce lands in accumulator rows the epilogue never stores (or zeroes) -- and a column
-  // tile that sticks out of W re-reads W's last float4.  Only a reduction dimension that is not a multiple of BK (the 4-channel
-  // stem) needs zero fill, on a uniform slow path.  (A branch per load kept every load behind its own compare.)
-  const bool kfull = (ca % BK) == 0;
+  const bool kfull = (ca % kPairBK) == 0;
   int32_t src[A_PASSES];
-#pragma unroll
-  for (int p = 0; p < A_PASSES; ++p) {
-    int r = p * 32 + arow;
-    int32_t s = 0;
-    if (r < cnt) s = gather ? gather[p0 + r] : p0 + r;
-    if (s < 0 || s >= rows_a) s = 0;
-    src[p] = s;
-  }
+  pair_gather_rows(gather, p0, cnt, rows_a, src);
   const float *Wk = W + (int64_t)k * ca * co;
 
-  f32x16 acc[RT][NT];
+  f32x16 acc[NT];
 #pragma unroll
-  for (int r = 0; r < RT; ++r)
+  for (int j = 0; j < NT; ++j)
 #pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) acc[r][j][g] = 0.f;
+    for (int g = 0; g < 16; ++g) acc[j][g] = 0.f;
 
   float4 ra[A_PASSES], rb[B_PASSES];
+  // The chunk loader stays a lambda of each kernel, the same text in both families: as a function of ftx_spconv_common.h the compiler
+  // ordered its instructions differently and the 32 -> 32 layers ran 4-5 % slower (profiles/spconv_shared_host.txt, section 1).
   auto load_chunk = [&](int c0) {
     if (kfull) {
 #pragma unroll
@@ -274,21 +230,18 @@ __global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict
   };
 
   load_chunk(0);
-  for (int c0 = 0; c0 < ca; c0 += BK) {
+  for (int c0 = 0; c0 < ca; c0 += kPairBK) {
     store_chunk();
     __syncthreads();
-    if (c0 + BK < ca) load_chunk(c0 + BK);  // next chunk's global loads fly under the MFMAs
+    if (c0 + kPairBK < ca) load_chunk(c0 + kPairBK);  // next chunk's global loads fly under the MFMAs
     // lane (l31, half) owns k = 8t + 4*half + s of both operands: one ds_read_b128 per operand row feeds 4 MFMAs.
     // The fragments of step t+1 are in flight while the MFMAs of step t issue.
-    const float *arow_p = &As[(wave * 32 * RT + l31) * AS_STRIDE + 4 * half];
+    const float *arow_p = &As[(wave * 32 + l31) * AS_STRIDE + 4 * half];
     const float *brow_p = &Bs[l31 * BS_STRIDE + 4 * half];
-    float af[2][RT][4], bf[2][NT][4];
+    float af[2][4], bf[2][NT][4];
     auto load_frag = [&](int buf, int t) {
-#pragma unroll
-      for (int r = 0; r < RT; ++r) {
-        float4 a = *(const float4 *)(arow_p + r * 32 * AS_STRIDE + 8 * t);
-        af[buf][r][0] = a.x; af[buf][r][1] = a.y; af[buf][r][2] = a.z; af[buf][r][3] = a.w;
-      }
+      float4 a = *(const float4 *)(arow_p + 8 * t);
+      af[buf][0] = a.x; af[buf][1] = a.y; af[buf][2] = a.z; af[buf][3] = a.w;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         float4 b = *(const float4 *)(brow_p + j * 32 * BS_STRIDE + 8 * t);
@@ -297,147 +250,55 @@ __global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict
     };
     load_frag(0, 0);
 #pragma unroll
-    for (int t = 0; t < BK / 8; ++t) {
-      if (t + 1 < BK / 8) load_frag((t + 1) & 1, t + 1);
+    for (int t = 0; t < kPairBK / 8; ++t) {
+      if (t + 1 < kPairBK / 8) load_frag((t + 1) & 1, t + 1);
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int r = 0; r < RT; ++r)
-            acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[t & 1][j][s], af[t & 1][r][s], acc[r][j], 0, 0, 0);
+        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[t & 1][j][s], af[t & 1][s], acc[j], 0, 0, 0);
     }
     __syncthreads();
   }
-
-  // ---- W is the MFMA's row operand, so lane (pair l31, half) holds 4 consecutive output channels in every 4
-  // consecutive accumulator registers: 16-byte stores, each pair row receives 32 contiguous bytes per instruction
-  // (dword stores of the (pair, channel) orientation took 17k cycles per tile here, these take 6k)
-  const bool nfull = n0 + BN <= co;
-#pragma unroll
-  for (int r = 0; r < RT; ++r) {
-    const int row = wave * 32 * RT + r * 32 + l31;
-    int64_t drow = row < cnt ? p0 + row : -1;
-    bool zero = false;   // a pair whose source index is out of range contributes a zero row, as if it gathered zeros
-    if (gather != nullptr && drow >= 0) {
-      const int32_t sidx = gather[drow];
-      zero = sidx < 0 || sidx >= rows_a;
-    }
-    if (scatter != nullptr && drow >= 0) {
-      drow = scatter[drow];
-      if (drow >= rows_out) drow = -1;
-    }
-    if (drow >= 0) {
-      float *dst = tmp + drow * co;
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int col = n0 + j * 32 + 8 * q + 4 * half;
-          if (nfull || col < co) {
-            float4 v = make_float4(acc[r][j][4 * q], acc[r][j][4 * q + 1], acc[r][j][4 * q + 2], acc[r][j][4 * q + 3]);
-            if (zero) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (bias) {
-              const float4 bv = *(const float4 *)&bias[col];
-              v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-            }
-            *(float4 *)&dst[col] = v;
-          }
-        }
-    }
-  }
-}
-
-template <int RT>
-static void launch_pairs_gemm(int nt, dim3 grid, hipStream_t st, const float *A, int64_t rows_a, const int32_t *gather, const float *W, int wT,
-                              const int32_t *koff, int ca, int co, int kvol, float *tmp, const float *bias, int64_t n_dense,
-                              const int32_t *scatter = nullptr, int64_t rows_out = 0) {
-  switch (nt) {
-    case 1: pairs_gemm_kernel<1, RT><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-    case 2: pairs_gemm_kernel<2, RT><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-    case 3: pairs_gemm_kernel<3, RT><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-    default: pairs_gemm_kernel<4, RT><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-  }
+  pair_gemm_epilogue<NT>(acc, p0, cnt, n0, gather, rows_a, scatter, rows_out, bias, co, tmp);
 }
 
 #include "ftx_lastblock.h"
 
 // One pair-GEMM kernel ships.  The LDS-DMA, producer / consumer and bf16x3 variants of rounds 1-2 each tied or lost against it
-// (DESIGN.md section 8); their sources live under tools/probes/spconv_variants/ and are not part of libftx.so.  Nothing in this file
-// is selected by process-wide mutable state or by a device query: tile shapes and workspace sizes are functions of the arguments.
-// 32-column tiles per block as a function of the arguments: 128 columns per block where there are enough pair tiles to fill the chip,
-// 64 where there are not (the two deepest levels: 159-445 tiles -- 372 blocks of 128 columns took 42.0 us on the 256 -> 256 layer of
-// level 16, 744 blocks of 64 take 34.5; with 472 blocks and more the wider tile wins by 2-5 %, it reads every gathered row once).
-// A column split changes no sum: the results are the same bits either way.
-static int gemm_nt(int co, int64_t row_tiles) {
-  int nt = co >= 128 ? 4 : (co + 31) / 32;
-  if (co > 128 && co % 96 == 0 && co % 128 != 0) nt = 3;
-  if (nt == 4 && row_tiles * ceil_div(co, 128) <= 400) nt = 2;
-  return nt;
-}
-
-// Column-block width (32 * nt) that the launches below pick, for tests that must know which tile shape they reach:
-// kvol >= 1 is a pair list of n_pairs pairs (ftx_spconv_pairs_gemm / _scatter), kvol == 0 dense rows (ftx_rows_gemm, n_pairs rows).
-extern "C" int32_t ftx_spconv_gemm_block_cols(int32_t co, int64_t n_pairs, int32_t kvol) {
-  if (co < 4 || co % 4 != 0 || n_pairs < 0 || kvol < 0) return -1;
-  const int64_t row_tiles = ceil_div(n_pairs, TILE_P) + kvol;
-  return 32 * gemm_nt(co, row_tiles);
-}
-
-// Measured on MI355X (profiles/r01_spconv_layer_micro.txt workload): 256-pair tiles (RT = 2) are 5-30 % SLOWER than 128-pair tiles on every
-// layer -- the extra accumulators cut occupancy to 1-2 waves per SIMD and the kernel is latency-, not W-traffic-bound: RT = 1 everywhere.
-
-extern "C" int ftx_spconv_pairs_gemm(const float *A, int64_t rows_a, const int32_t *gather, const float *W, int32_t w_transposed,
-                                     const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *tmp, void *stream) {
-  FTX_REQUIRE(n_pairs >= 0 && rows_a >= 0 && kvol >= 1 && kvol <= 64, "ftx_spconv_pairs_gemm: bad size");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && co >= 4 && co % 4 == 0, "ftx_spconv_pairs_gemm: channels must be multiples of 4 (ca=%d co=%d)", ca, co);
-  if (n_pairs == 0) return FTX_OK;
-  FTX_REQUIRE(A && gather && W && koff && tmp && rows_a >= 1, "ftx_spconv_pairs_gemm: null pointer or empty operand");
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned tiles_ub = (unsigned)(ceil_div(n_pairs, TILE_P) + kvol);  // sum_k ceil(cnt_k/tile) <= P/tile + kvol
-  const int nt = gemm_nt(co, tiles_ub);
-  dim3 grid(tiles_ub, (unsigned)ceil_div(co, 32 * nt));
-  launch_pairs_gemm<1>(nt, grid, st, A, rows_a, gather, W, w_transposed, koff, ca, co, kvol, tmp, nullptr, 0);
-  return check_launch("ftx_spconv_pairs_gemm");
-}
-
-// One-launch convolution for maps whose destination side is a bijection of the pair list: out[scatter[p],:] = A[gather[p],:] @ Wk(p).
-// The strided 2^3 convolution joins every fine voxel to exactly one (coarse voxel, offset), so its data gradient and the
-// transposed convolution built on the same map (models/spvcnn.py:38-50) write every fine row exactly once: no tmp, no reduce.
-// The caller guarantees that `scatter` is injective (rows it does not name are left untouched).
-extern "C" int ftx_spconv_pairs_gemm_scatter(const float *A, int64_t rows_a, const int32_t *gather, const int32_t *scatter, const float *W,
-                                             int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol,
-                                             float *out, int64_t rows_out, void *stream) {
-  FTX_REQUIRE(n_pairs >= 0 && rows_a >= 0 && rows_out >= 0 && kvol >= 1 && kvol <= 64, "ftx_spconv_pairs_gemm_scatter: bad size");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && co >= 4 && co % 4 == 0, "ftx_spconv_pairs_gemm_scatter: channels must be multiples of 4 (ca=%d co=%d)", ca, co);
-  if (n_pairs == 0) return FTX_OK;
-  FTX_REQUIRE(A && gather && scatter && W && koff && out && rows_a >= 1, "ftx_spconv_pairs_gemm_scatter: null pointer or empty operand");
-  hipStream_t st = (hipStream_t)stream;
-  const int nt = gemm_nt(co, ceil_div(n_pairs, TILE_P) + kvol);
-  dim3 grid((unsigned)(ceil_div(n_pairs, TILE_P) + kvol), (unsigned)ceil_div(co, 32 * nt));
-  launch_pairs_gemm<1>(nt, grid, st, A, rows_a, gather, W, w_transposed, koff, ca, co, kvol, out, nullptr, 0, scatter, rows_out);
-  return check_launch("ftx_spconv_pairs_gemm_scatter");
-}
-
-// Dense rows: out[r,:] = A[r,:] @ W (+ bias) on the same tile code (identity gather, one "offset").
-// The point-branch Linear layers, the 1x1x1 convolutions and the heads are skinny GEMMs
-// (81k rows x 20..256 columns, K = 32..256) that are HBM-bound: rows in, rows out, W from L2.
-extern "C" int ftx_rows_gemm(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co,
-                             float *out, void *stream) {
-  FTX_REQUIRE(n >= 0, "ftx_rows_gemm: n < 0");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && co >= 4 && co % 4 == 0, "ftx_rows_gemm: channels must be multiples of 4 (ca=%d co=%d)", ca, co);
-  if (n == 0) return FTX_OK;
-  FTX_REQUIRE(A && W && out, "ftx_rows_gemm: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int nt = gemm_nt(co, ceil_div(n, TILE_P));
-  dim3 grid((unsigned)ceil_div(n, TILE_P), (unsigned)ceil_div(co, 32 * nt));
-  launch_pairs_gemm<1>(nt, grid, st, A, n, nullptr, W, w_transposed, nullptr, ca, co, 1, out, bias, n);
-  return check_launch("ftx_rows_gemm");
-}
+// (DESIGN.md section 8); their sources live under tools/probes/spconv_variants/ and are not part of libftx.so.
 
 // ---------------------------------------------------------------------------------------
 // phase 2: out[r,:] = sum_k tmp[pos[k,r],:]   (fixed k order; rows without pairs become 0)
 // ---------------------------------------------------------------------------------------
+// Channels j .. j+3 of output row r: the rows tmp[pos[k, r]] of its pairs, added in ascending k.  KVOL > 0 is the offset count at
+// compile time (all positions are read first, then the valid rows), KVOL == 0 takes it from `kvol`.
+template <int KVOL>
+__device__ __forceinline__ float4 reduce_row(const float *__restrict__ tmp, const int32_t *__restrict__ pos, int64_t n, int co, int kvol,
+                                             int64_t r, int j) {
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (KVOL > 0) {
+    int32_t p[KVOL > 0 ? KVOL : 1];
+#pragma unroll
+    for (int k = 0; k < KVOL; ++k) p[k] = pos[(int64_t)k * n + r];
+#pragma unroll
+    for (int k = 0; k < KVOL; ++k) {
+      if (p[k] >= 0) {
+        float4 v = *(const float4 *)&tmp[(int64_t)p[k] * co + j];
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+      }
+    }
+  } else {
+    for (int k = 0; k < kvol; ++k) {
+      int32_t q = pos[(int64_t)k * n + r];
+      if (q >= 0) {
+        float4 v = *(const float4 *)&tmp[(int64_t)q * co + j];
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+      }
+    }
+  }
+  return acc;
+}
+
 template <int KVOL>
 __global__ void spconv_reduce_kernel(const float *__restrict__ tmp, const int32_t *__restrict__ pos, int64_t n, int co, int kvol,
                                      float *__restrict__ out) {
@@ -446,27 +307,7 @@ __global__ void spconv_reduce_kernel(const float *__restrict__ tmp, const int32_
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     int64_t r = e / cv;
     int j = (int)(e - r * cv) * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (KVOL > 0) {
-      int32_t p[KVOL > 0 ? KVOL : 1];
-#pragma unroll
-      for (int k = 0; k < KVOL; ++k) p[k] = pos[(int64_t)k * n + r];
-#pragma unroll
-      for (int k = 0; k < KVOL; ++k) {
-        if (p[k] >= 0) {
-          float4 v = *(const float4 *)&tmp[(int64_t)p[k] * co + j];
-          acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-      }
-    } else {
-      for (int k = 0; k < kvol; ++k) {
-        int32_t q = pos[(int64_t)k * n + r];
-        if (q >= 0) {
-          float4 v = *(const float4 *)&tmp[(int64_t)q * co + j];
-          acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-      }
-    }
+    const float4 acc = reduce_row<KVOL>(tmp, pos, n, co, kvol, r, j);
     *(float4 *)&out[r * co + j] = acc;
   }
 }
@@ -501,17 +342,7 @@ __global__ void spconv_reduce_bn_eval_kernel(const float *__restrict__ tmp, cons
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     int64_t r = e / cv;
     int j = (int)(e - r * cv) * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    int32_t p[KVOL];
-#pragma unroll
-    for (int k = 0; k < KVOL; ++k) p[k] = pos[(int64_t)k * n + r];
-#pragma unroll
-    for (int k = 0; k < KVOL; ++k) {
-      if (p[k] >= 0) {
-        float4 v = *(const float4 *)&tmp[(int64_t)p[k] * co + j];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-      }
-    }
+    const float4 acc = reduce_row<KVOL>(tmp, pos, n, co, KVOL, r, j);
     float o[4] = {acc.x, acc.y, acc.z, acc.w};
     float rr[4] = {0, 0, 0, 0};
     if (res) {
@@ -561,27 +392,7 @@ __global__ __launch_bounds__(256) void spconv_reduce_stats_kernel(const float *_
   if (rl < RL) {
     const int j = cg * 4;
     for (int64_t r = r0 + rl; r < r1; r += RL) {
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (KVOL > 0) {
-        int32_t p[KVOL > 0 ? KVOL : 1];
-#pragma unroll
-        for (int k = 0; k < KVOL; ++k) p[k] = pos[(int64_t)k * n + r];
-#pragma unroll
-        for (int k = 0; k < KVOL; ++k) {
-          if (p[k] >= 0) {
-            float4 v = *(const float4 *)&tmp[(int64_t)p[k] * co + j];
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-          }
-        }
-      } else {
-        for (int k = 0; k < kvol; ++k) {
-          int32_t q = pos[(int64_t)k * n + r];
-          if (q >= 0) {
-            float4 v = *(const float4 *)&tmp[(int64_t)q * co + j];
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-          }
-        }
-      }
+      const float4 acc = reduce_row<KVOL>(tmp, pos, n, co, kvol, r, j);
       *(float4 *)&out[r * co + j] = acc;
       s0[0] += (double)acc.x; s1[0] += (double)acc.x * (double)acc.x;
       s0[1] += (double)acc.y; s1[1] += (double)acc.y * (double)acc.y;
@@ -647,7 +458,6 @@ extern "C" int ftx_spconv_reduce_stats(const float *tmp, const int32_t *pos, int
 // Waves: WMG x WNG x KS = 4; KS > 1 splits the pairs of each step and sums the KS groups through LDS in a fixed order.
 // ---------------------------------------------------------------------------------------
 constexpr int WG_BR = 32;       // pairs staged per step
-constexpr int WG_ROUND = 1024;  // pair indices kept in LDS at a time
 
 template <int N> struct FragLoad;
 template <> struct FragLoad<1> { static __device__ __forceinline__ void ld(const float *p, float (&f)[1]) { f[0] = *p; } };
@@ -666,8 +476,8 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
   constexpr int RED = KS > 1 ? MI * NI * 1024 * WMG * WNG : 0;  // floats: one KS group's accumulators
   constexpr int LDSF = STAGE > RED ? STAGE : RED;
   __shared__ __attribute__((aligned(16))) float lds[LDSF];
-  __shared__ int32_t s_ia[WG_ROUND], s_ig[WG_ROUND];
-  __shared__ uint8_t s_ok[WG_ROUND];
+  __shared__ int32_t s_ia[kWgradRound], s_ig[kWgradRound];
+  __shared__ uint8_t s_ok[kWgradRound];
   __shared__ int s_tile[4];
   __shared__ int s_bad;
   float *As = lds, *Gs = lds + WG_BR * TM;
@@ -676,34 +486,7 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
   const int half = lane >> 5, l31 = lane & 31;
   const int wq = wave % (WMG * WNG), ks = wave / (WMG * WNG);
   const int wm = wq % WMG, wn = wq / WMG;
-  // Tile = `tile_len` consecutive pairs of ONE offset.  Offsets differ a lot in pair count (the centre offset of a submanifold
-  // map has one pair per voxel, ~7x the others), so tiles are cut from the pair list, not per offset: a wave-level scan of
-  // koff maps block -> (offset, range).
-  if (tid < 64) {
-    const int b = blockIdx.x;
-    int c = 0;
-    if (tid < kvol) c = koff ? koff[tid + 1] - koff[tid] : n_dense;
-    int nt = (c + tile_len - 1) / tile_len;
-    int incl = nt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      int v = __shfl_up(incl, off, 64);
-      if (tid >= off) incl += v;
-    }
-    int excl = incl - nt;
-    bool mine = (tid < kvol) && b >= excl && b < incl;
-    unsigned long long msk = __ballot(mine);
-    if (mine) {
-      int t = b - excl;
-      int first = (koff ? koff[tid] : 0) + t * tile_len;
-      int left = c - t * tile_len;
-      s_tile[0] = tid;
-      s_tile[1] = first;
-      s_tile[2] = first + (left > tile_len ? tile_len : left);
-      s_tile[3] = nt;
-    }
-    if (msk == 0ull && tid == 0) s_tile[0] = -1;
-  }
+  pair_tile_scan<true>(koff, kvol, tile_len, n_dense, s_tile);   // tile -> (offset, pair range)
   __syncthreads();
   const int k = s_tile[0];
   if (k < 0) return;  // surplus block of the upper-bound grid
@@ -748,12 +531,12 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
   }
   auto load_step = [&](int p0, float4 (&ra)[QA], float4 (&rg)[QG]) {
     const int o = p0 - rbase;
-    if (o >= WG_ROUND) return;   // past this round's indices: the step is never consumed
+    if (o >= kWgradRound) return;   // past this round's indices: the step is never consumed
     int32_t ia[QA], ig[QG];
 #pragma unroll
-    for (int q = 0; q < QA; ++q) ia[q] = s_ia[(o + pra[q]) & (WG_ROUND - 1)];
+    for (int q = 0; q < QA; ++q) ia[q] = s_ia[(o + pra[q]) & (kWgradRound - 1)];
 #pragma unroll
-    for (int q = 0; q < QG; ++q) ig[q] = s_ig[(o + prg[q]) & (WG_ROUND - 1)];
+    for (int q = 0; q < QG; ++q) ig[q] = s_ig[(o + prg[q]) & (kWgradRound - 1)];
 #pragma unroll
     for (int q = 0; q < QA; ++q) ra[q] = *(const float4 *)(A + ((int64_t)ia[q] * ca + ca_off[q]));
 #pragma unroll
@@ -764,12 +547,12 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
 #pragma unroll
       for (int q = 0; q < QA; ++q) {
         const int p = p0 + pra[q];
-        if (p >= rend || s_ok[(p - rbase) & (WG_ROUND - 1)] == 0) ra[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p >= rend || s_ok[(p - rbase) & (kWgradRound - 1)] == 0) ra[q] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
       for (int q = 0; q < QG; ++q) {
         const int p = p0 + prg[q];
-        if (p >= rend || s_ok[(p - rbase) & (WG_ROUND - 1)] == 0) rg[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p >= rend || s_ok[(p - rbase) & (kWgradRound - 1)] == 0) rg[q] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
 #pragma unroll
@@ -798,30 +581,9 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
     }
   };
 
-  for (rbase = lo; rbase < hi; rbase += WG_ROUND) {
-    rend = (rbase + WG_ROUND < hi) ? rbase + WG_ROUND : hi;
-    __syncthreads();  // previous round's gathers are done with s_ia / s_ig
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    for (int t = tid; t < WG_ROUND; t += 256) {
-      // every slot gets a loadable row: slots past the end repeat row 0, malformed pairs are flagged and zeroed at store time
-      int32_t ia = 0, ig = 0;
-      uint8_t ok = 0;
-      if (t < rend - rbase) {
-        ia = idx_a ? idx_a[rbase + t] : rbase + t;
-        ig = idx_g ? idx_g[rbase + t] : rbase + t;
-        ok = 1;
-        if (ia < 0 || ia >= rows_a || ig < 0 || ig >= rows_g) {
-          ia = ig = 0;
-          ok = 0;
-          s_bad = 1;
-        }
-      }
-      s_ia[t] = ia;
-      s_ig[t] = ig;
-      s_ok[t] = ok;
-    }
-    __syncthreads();
+  for (rbase = lo; rbase < hi; rbase += kWgradRound) {
+    rend = (rbase + kWgradRound < hi) ? rbase + kWgradRound : hi;
+    wgrad_stage_indices(idx_a, rows_a, idx_g, rows_g, rbase, rend, s_ia, s_ig, s_ok, &s_bad);
     load_step(rbase, ra0, rg0);
     load_step(rbase + WG_BR, ra1, rg1);
     for (int p0 = rbase; p0 < rend; p0 += 2 * WG_BR) {
@@ -839,29 +601,7 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
     }
   }
 
-  if (KS > 1) {  // sum the pair-subsets of the KS wave groups, fixed order (the staging buffers are free now)
-    float *red = lds;
-    for (int r = 1; r < KS; ++r) {
-      if (ks == r) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) red[(((wq * MI + i) * NI + j) * 16 + g) * 64 + lane] = acc[i][j][g];
-      }
-      __syncthreads();
-      if (ks == 0) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[i][j][g] += red[(((wq * MI + i) * NI + j) * 16 + g) * 64 + lane];
-      }
-      __syncthreads();
-    }
-  }
+  wgrad_ks_reduce<MI, NI, KS>(acc, lds, wq, ks, lane);   // the pair-subsets of the KS wave groups (the staging buffers are free now)
 
   if (ks == 0) {
     const int64_t mat = (int64_t)ca * cg;
@@ -890,122 +630,57 @@ __global__ __launch_bounds__(256) void pairs_wgrad_kernel(const float *__restric
   }
 }
 
-#include "ftx_spconv_wgrad_reduce.h"
-
-// Tile shape per channel count.  M side: 32 / 64 / 96 (multiples of 96 that are not multiples of 128: 96, 192) / 128;
-// N side: 32 / 64 / 96 / 128.
-struct WgradCfg { int mi, wmg, ni, wng; };
-static WgradCfg wgrad_config(int ca, int cg) {
-  WgradCfg c;
-  if (ca <= 32) { c.mi = 1; c.wmg = 1; }
-  else if (ca <= 64) { c.mi = 2; c.wmg = 1; }
-  else if (ca % 96 == 0 && ca % 128 != 0) { c.mi = 3; c.wmg = 1; }
-  else { c.mi = 2; c.wmg = 2; }
-  if (cg <= 32) { c.ni = 1; c.wng = 1; }
-  else if (cg <= 64) { c.ni = 2; c.wng = 1; }
-  else if (cg % 96 == 0 && cg % 128 != 0) { c.ni = 3; c.wng = 1; }
-  else { c.ni = 2; c.wng = 2; }
-  // a 96 x 96 tile per wave is 9 accumulators (144 registers): one wave per SIMD.  96 -> 96 layers take a 128 x 96 tile instead
-  // (2 x 3 accumulators per wave, the last 32 M rows are padding).
-  if (c.mi == 3 && c.ni == 3) { c.mi = 2; c.wmg = 2; }
-  return c;
-}
-
-// Resident blocks per CU of the instantiation a layer uses, as a TABLE: registers decide (a block is one wave per SIMD, a SIMD has 512
-// vector registers; LDS never binds first).  Values = min(8, 512 / allocated VGPRs) read from the gfx950 code object (llvm-readelf --notes:
-// .vgpr_count 60 / 96-104 / 128-136 / 156 / 184-236 / 316) -- tests/test_cabi.py recomputes them from the built object and fails when the
-// table is stale.  A table and not hipOccupancyMaxActiveBlocksPerMultiprocessor: the tile length, the workspace size and the summation tree
-// of the weight gradient (hence its bits) must be functions of the arguments alone, the same on every host and device (round 2 asked the
-// runtime, with a fallback of 2 where there was no device to ask).
-static int wgrad_occ(const WgradCfg &c) {
-  // rows: M side (mi, wmg) = (1,1) (2,1) (3,1) (2,2); columns: N side (ni, wng) in the same order
-  static const int occ[4][4] = {{8, 4, 3, 3}, {5, 3, 2, 2}, {4, 2, 1, 2}, {3, 2, 2, 2}};
-  auto side = [](int i, int w) { return w == 2 ? 3 : i - 1; };
-  return occ[side(c.mi, c.wmg)][side(c.ni, c.wng)];
-}
-// (mi, wmg, ni, wng) -> table value, for the build-time check of the table against the code object
-extern "C" int32_t ftx_spconv_wgrad_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng) {
-  if (!((mi >= 1 && mi <= 3 && wmg == 1) || (mi == 2 && wmg == 2)) || !((ni >= 1 && ni <= 3 && wng == 1) || (ni == 2 && wng == 2))) return -1;
-  WgradCfg c{mi, wmg, ni, wng};
-  return wgrad_occ(c);
-}
-extern "C" int32_t ftx_spconv_wgrad_resident_blocks(int32_t ca, int32_t cg) { return wgrad_occ(wgrad_config(ca, cg)); }
-constexpr int WGRAD_CUS = 256;   // MI355X; a constant of the tiling, not a device query (see above)
-
-// Pairs per tile.  All blocks of a launch should be resident together: a launch of 1.2x the resident slots takes as long as one of 2x
-// (measured: 620 blocks on 512 slots ran 1.7x longer than 820).  So the tile length is chosen for R full rounds of
-// slots = CUs x resident blocks per CU, R as small as keeps a tile <= 4096 pairs; every offset adds about half a tile of rounding.
-static int wgrad_tile_len(int64_t n_pairs, int ca, int cg, int kvol) {
-  const WgradCfg c = wgrad_config(ca, cg);
-  const int64_t mn_tiles = ceil_div(ca, 32 * c.mi * c.wmg) * ceil_div(cg, 32 * c.ni * c.wng);
-  const int64_t slots = (int64_t)WGRAD_CUS * wgrad_occ(c);
-  int64_t len = 256;
-  for (int rounds = 1; rounds <= 64; ++rounds) {
-    int64_t tiles = (slots * rounds * 15 / 16) / mn_tiles - (kvol + 1) / 2;   // 1/16 of head room: an overshoot costs a whole round
-    if (tiles < 1) tiles = 1;
-    len = ceil_div(ceil_div(n_pairs, tiles), 2 * WG_BR) * 2 * WG_BR;
-    if (len <= 4096) break;
+// ---------------------------------------------------------------------------------------
+// the family's description and entries (ftx_spconv_common.h)
+// ---------------------------------------------------------------------------------------
+struct SpconvF32 {
+  static constexpr const char *pairs_name = "ftx_spconv_pairs_gemm", *scatter_name = "ftx_spconv_pairs_gemm_scatter", *rows_name = "ftx_rows_gemm",
+                              *wgrad_name = "ftx_spconv_pairs_wgrad";
+  // registers decide (a block is one wave per SIMD, a SIMD has 512 vector registers; LDS never binds first):
+  // .vgpr_count 60 / 96-104 / 128-136 / 156 / 184-236 / 316
+  static constexpr int wgrad_blocks[4][4] = {{8, 4, 3, 3}, {5, 3, 2, 2}, {4, 2, 1, 2}, {3, 2, 2, 2}};
+  static constexpr int wgrad_step = 2 * WG_BR;
+  template <int NT>
+  static void gemm(dim3 grid, hipStream_t st, const PairsGemmArgs &a) {
+    pairs_gemm_kernel<NT><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.gather, a.W, a.w_transposed, a.koff, a.ca, a.co, a.kvol, a.out, a.bias, a.n_dense,
+                                                a.scatter, a.rows_out);
   }
-  if (len < 256) len = 256;
-  return (int)len;
+  template <int MI, int NI, int WMG, int WNG>
+  static void wgrad(dim3 grid, hipStream_t st, const PairsWgradArgs &a) {
+    pairs_wgrad_kernel<MI, NI, WMG, WNG><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.idx_a, a.G, a.rows_g, a.idx_g, a.koff, a.ca, a.cg, a.kvol, a.tile_len,
+                                                               a.part, a.dW, a.n_dense);
+  }
+};
+
+extern "C" int32_t ftx_spconv_gemm_block_cols(int32_t co, int64_t n_pairs, int32_t kvol) { return spconv_gemm_block_cols(co, n_pairs, kvol); }
+
+extern "C" int ftx_spconv_pairs_gemm(const float *A, int64_t rows_a, const int32_t *gather, const float *W, int32_t w_transposed,
+                                     const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *tmp, void *stream) {
+  return spconv_pairs_entry<SpconvF32>(false, A, rows_a, gather, nullptr, W, w_transposed, koff, n_pairs, ca, co, kvol, tmp, 0, stream);
 }
 
-static int64_t wgrad_tiles_ub(int64_t n_pairs, int tile_len, int kvol) { return ceil_div(n_pairs, tile_len) + kvol; }
+extern "C" int ftx_spconv_pairs_gemm_scatter(const float *A, int64_t rows_a, const int32_t *gather, const int32_t *scatter, const float *W,
+                                             int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol,
+                                             float *out, int64_t rows_out, void *stream) {
+  return spconv_pairs_entry<SpconvF32>(true, A, rows_a, gather, scatter, W, w_transposed, koff, n_pairs, ca, co, kvol, out, rows_out, stream);
+}
+
+extern "C" int ftx_rows_gemm(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co,
+                             float *out, void *stream) {
+  return spconv_rows_entry<SpconvF32>(A, n, W, w_transposed, bias, ca, co, out, stream);
+}
+
+extern "C" int32_t ftx_spconv_wgrad_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng) {
+  return spconv_wgrad_table_blocks<SpconvF32>(mi, wmg, ni, wng);
+}
+extern "C" int32_t ftx_spconv_wgrad_resident_blocks(int32_t ca, int32_t cg) { return spconv_wgrad_occ<SpconvF32>(spconv_wgrad_config(ca, cg)); }
 
 extern "C" size_t ftx_spconv_pairs_wgrad_workspace_bytes(int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol) {
-  if (n_pairs <= 0 || ca <= 0 || cg <= 0 || kvol <= 0) return 256;
-  int len = wgrad_tile_len(n_pairs, ca, cg, kvol);
-  return sizeof(float) * (size_t)wgrad_tiles_ub(n_pairs, len, kvol) * ca * cg;
-}
-
-template <int MI, int WMG>
-static void launch_wgrad_n(const WgradCfg &c, dim3 grid, hipStream_t st, const float *A, int64_t rows_a, const int32_t *idx_a, const float *G, int64_t rows_g,
-                           const int32_t *idx_g, const int32_t *koff, int ca, int cg, int kvol, int tl, float *part, float *dW, int n_dense) {
-  if (c.ni == 1)
-    pairs_wgrad_kernel<MI, 1, WMG, 1><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
-  else if (c.ni == 3)
-    pairs_wgrad_kernel<MI, 3, WMG, 1><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
-  else if (c.wng == 1)
-    pairs_wgrad_kernel<MI, 2, WMG, 1><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
-  else
-    pairs_wgrad_kernel<MI, 2, WMG, 2><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
+  return spconv_wgrad_workspace_bytes<SpconvF32>(n_pairs, ca, cg, kvol);
 }
 
 extern "C" int ftx_spconv_pairs_wgrad(const float *A, int64_t rows_a, const int32_t *idx_a, const float *G, int64_t rows_g, const int32_t *idx_g,
                                       const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol, float *dW, void *workspace,
                                       size_t workspace_bytes, void *stream) {
-  FTX_REQUIRE(n_pairs >= 0 && rows_a >= 0 && rows_g >= 0 && kvol >= 1 && kvol <= 64, "ftx_spconv_pairs_wgrad: bad size");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && cg >= 4 && cg % 4 == 0, "ftx_spconv_pairs_wgrad: channels must be multiples of 4 (ca=%d cg=%d)", ca, cg);
-  FTX_REQUIRE(dW, "ftx_spconv_pairs_wgrad: null dW");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t mat = (int64_t)ca * cg;
-  if (n_pairs == 0) {
-    if (hipMemsetAsync(dW, 0, sizeof(float) * kvol * mat, st) != hipSuccess) return check_launch("ftx_spconv_pairs_wgrad memset");
-    return FTX_OK;
-  }
-  FTX_REQUIRE(A && G && rows_a >= 1 && rows_g >= 1, "ftx_spconv_pairs_wgrad: null pointer or empty operand");
-  const bool dense = (idx_a == nullptr && idx_g == nullptr && koff == nullptr);
-  FTX_REQUIRE(dense || (idx_a && idx_g && koff), "ftx_spconv_pairs_wgrad: idx_a, idx_g and koff must be all set or all null (dense rows)");
-  FTX_REQUIRE(!dense || (kvol == 1 && n_pairs <= rows_a && n_pairs <= rows_g), "ftx_spconv_pairs_wgrad: dense mode needs kvol == 1 and n_pairs rows in A and G");
-  FTX_REQUIRE(n_pairs < 0x7fffffff, "ftx_spconv_pairs_wgrad: too many pairs");
-  const int tile_len = wgrad_tile_len(n_pairs, ca, cg, kvol);
-  const int64_t tiles = wgrad_tiles_ub(n_pairs, tile_len, kvol);
-  size_t need = sizeof(float) * (size_t)tiles * mat;
-  if (!workspace || workspace_bytes < need) {
-    set_error("ftx_spconv_pairs_wgrad: workspace %zu < required %zu", workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
-  float *part = (float *)workspace;
-  const WgradCfg c = wgrad_config(ca, cg);
-  dim3 grid((unsigned)tiles, (unsigned)ceil_div(ca, 32 * c.mi * c.wmg), (unsigned)ceil_div(cg, 32 * c.ni * c.wng));
-  if (c.mi == 1)
-    launch_wgrad_n<1, 1>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  else if (c.mi == 3)
-    launch_wgrad_n<3, 1>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  else if (c.wmg == 1)
-    launch_wgrad_n<2, 1>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  else
-    launch_wgrad_n<2, 2>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  launch_wgrad_reduce(part, koff, kvol, tile_len, (int)n_pairs, mat, tiles, dW, st);
-  return check_launch("ftx_spconv_pairs_wgrad");
+  return spconv_wgrad_entry<SpconvF32>(A, rows_a, idx_a, G, rows_g, idx_g, koff, n_pairs, ca, cg, kvol, dW, workspace, workspace_bytes, stream);
 }

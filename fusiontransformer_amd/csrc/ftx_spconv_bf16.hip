@@ -11,62 +11,19 @@
 //
 // Operand maps of v_mfma_f32_32x32x16_bf16 (cdna_hip_programming.md section 3): lane (r = lane & 31, h = lane >> 5) holds A[row r][k]
 // and B[k][col r] for k = 8h + j, j = 0..7, of each 16-wide k-step; accumulator register g of the lane is C[(g&3) + 8(g>>2) + 4h][r],
-// the same layout as the f32 MFMA, so both kernels keep the epilogues of their fp32 twins.  Both operands are staged as bf16 LDS images
-// in which the reduction index is contiguous: one ds_read_b128 per operand and k-step.
-#include "ftx_common.h"
-#include "ftx_mfma.h"
-#include "ftx_spconv_wgrad_reduce.h"
+// the same layout as the f32 MFMA, so the pair GEMM shares its epilogue with the fp32 kernel (ftx_spconv_common.h, with everything
+// else the two families have in common).  Both operands are staged as bf16 LDS images in which the reduction index is contiguous: one
+// ds_read_b128 per operand and k-step.
+#include "ftx_spconv_common.h"
 
 using namespace ftx;
 
-namespace {
-
 __device__ inline bf16x4 round4(float4 v) { return (bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
-
-// Tile -> (offset, first pair, pair count) of an upper-bound grid of `tile`-pair tiles: wave 0 scans the per-offset tile counts
-// (the scan of pairs_gemm_kernel).  s_tile[0] = -1 for a surplus block.
-__device__ inline void gemm_tile_scan(const int32_t *__restrict__ koff, int kvol, int tile, int64_t n_dense, bool dense, int *s_tile) {
-  const int tid = threadIdx.x;
-  const int b = blockIdx.x;
-  if (dense) {
-    if (tid == 0) {
-      int64_t left = n_dense - (int64_t)b * tile;
-      s_tile[0] = left > 0 ? 0 : -1;
-      s_tile[1] = b * tile;
-      s_tile[2] = left > tile ? tile : (int)left;
-    }
-    return;
-  }
-  if (tid >= 64) return;
-  int c = (tid < kvol) ? koff[tid + 1] - koff[tid] : 0;
-  int nt = (c + tile - 1) / tile;
-  int incl = nt;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    int v = __shfl_up(incl, off, 64);
-    if (tid >= off) incl += v;
-  }
-  int excl = incl - nt;
-  bool mine = (tid < kvol) && b >= excl && b < incl;
-  unsigned long long m = __ballot(mine);
-  if (mine) {
-    int t = b - excl;
-    int left = c - t * tile;
-    s_tile[0] = tid;
-    s_tile[1] = koff[tid] + t * tile;
-    s_tile[2] = left > tile ? tile : left;
-  }
-  if (m == 0ull && tid == 0) s_tile[0] = -1;
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------------------
 // tmp[p,:] = bf16(A[gather[p],:]) @ bf16(Wk(p))      (tiles of 128 pairs of one offset; the forms of pairs_gemm_kernel)
 // ---------------------------------------------------------------------------------------
-constexpr int GB_BK = 32;       // channels of the reduction staged per step: two k-steps of 16
 constexpr int GB_STRIDE = 40;   // bf16 per LDS row (80 B): the 16 lanes of one ds_read_b128 phase cover 16 disjoint bank quads
-constexpr int GB_TILE = 128;    // pairs per tile: 4 waves x 32 pairs
 
 // NT = 32-column tiles per block.  W is the MFMA's row operand (rows = output channels, columns = pairs), as in the fp32 kernel.
 template <int NT>
@@ -75,14 +32,14 @@ __global__ __launch_bounds__(256) void pairs_gemm_bf16_kernel(const float *__res
                                                               int ca, int co, int kvol, float *__restrict__ tmp, const float *__restrict__ bias,
                                                               int64_t n_dense, const int32_t *__restrict__ scatter, int64_t rows_out) {
   constexpr int BN = 32 * NT;
-  constexpr int A_PASSES = 4;      // GB_TILE * GB_BK / 4 float4 = 4 per thread
-  constexpr int B_PASSES = NT;     // GB_BK * BN / 4 float4 = NT * 256
-  __shared__ __attribute__((aligned(16))) __bf16 As[GB_TILE * GB_STRIDE];   // [pair][k]
+  constexpr int A_PASSES = kPairAPasses;
+  constexpr int B_PASSES = NT;     // kPairBK * BN / 4 float4 = NT * 256; a step of kPairBK channels is two k-steps of 16
+  __shared__ __attribute__((aligned(16))) __bf16 As[kPairTile * GB_STRIDE];   // [pair][k]
   __shared__ __attribute__((aligned(16))) __bf16 Bs[BN * GB_STRIDE];        // [n][k]
   __shared__ int s_tile[3];
 
   const int tid = threadIdx.x;
-  gemm_tile_scan(koff, kvol, GB_TILE, n_dense, gather == nullptr, s_tile);
+  gemm_tile_scan(koff, kvol, n_dense, gather == nullptr, s_tile);
   __syncthreads();
   const int k = s_tile[0];
   if (k < 0) return;  // surplus block of the upper-bound grid
@@ -93,19 +50,9 @@ __global__ __launch_bounds__(256) void pairs_gemm_bf16_kernel(const float *__res
   const int n0 = blockIdx.y * BN;
   const int arow = tid >> 3, acol = (tid & 7) * 4;
 
-  // Gather rules of pairs_gemm_kernel: unconditional loads from always-valid addresses (rows past the tile and malformed indices read
-  // row 0 and land in accumulator columns the epilogue never stores, or zeroes); a reduction dimension that is not a multiple of
-  // GB_BK (the 4-channel stem) is zero-filled on a uniform slow path.
-  const bool kfull = (ca % GB_BK) == 0;
+  const bool kfull = (ca % kPairBK) == 0;
   int32_t src[A_PASSES];
-#pragma unroll
-  for (int p = 0; p < A_PASSES; ++p) {
-    int r = p * 32 + arow;
-    int32_t s = 0;
-    if (r < cnt) s = gather ? gather[p0 + r] : p0 + r;
-    if (s < 0 || s >= rows_a) s = 0;
-    src[p] = s;
-  }
+  pair_gather_rows(gather, p0, cnt, rows_a, src);
   const float *Wk = W + (int64_t)k * ca * co;
 
   f32x16 acc[NT];
@@ -115,6 +62,8 @@ __global__ __launch_bounds__(256) void pairs_gemm_bf16_kernel(const float *__res
     for (int g = 0; g < 16; ++g) acc[j][g] = 0.f;
 
   float4 ra[A_PASSES], rb[B_PASSES];
+  // The chunk loader stays a lambda of each kernel, the same text in both families: as a function of ftx_spconv_common.h the compiler
+  // ordered its instructions differently and the 32 -> 32 layers ran 4-5 % slower (profiles/spconv_shared_host.txt, section 1).
   auto load_chunk = [&](int c0) {
     if (kfull) {
 #pragma unroll
@@ -178,12 +127,12 @@ __global__ __launch_bounds__(256) void pairs_gemm_bf16_kernel(const float *__res
   const __bf16 *ap = &As[(wave * 32 + l31) * GB_STRIDE + 8 * half];
   const __bf16 *bp = &Bs[l31 * GB_STRIDE + 8 * half];
   load_chunk(0);
-  for (int c0 = 0; c0 < ca; c0 += GB_BK) {
+  for (int c0 = 0; c0 < ca; c0 += kPairBK) {
     store_chunk();
     __syncthreads();
-    if (c0 + GB_BK < ca) load_chunk(c0 + GB_BK);  // next chunk's global loads fly under the MFMAs
+    if (c0 + kPairBK < ca) load_chunk(c0 + kPairBK);  // next chunk's global loads fly under the MFMAs
 #pragma unroll
-    for (int s = 0; s < GB_BK / 16; ++s) {
+    for (int s = 0; s < kPairBK / 16; ++s) {
       const bf16x8 a = *(const bf16x8 *)(ap + 16 * s);
 #pragma unroll
       for (int j = 0; j < NT; ++j) acc[j] = mfma_bf16(*(const bf16x8 *)(bp + j * 32 * GB_STRIDE + 16 * s), a, acc[j]);
@@ -191,104 +140,7 @@ __global__ __launch_bounds__(256) void pairs_gemm_bf16_kernel(const float *__res
     __syncthreads();
   }
 
-  // epilogue of pairs_gemm_kernel: lane (pair l31, half) holds 4 consecutive output channels in every 4 accumulator registers
-  const bool nfull = n0 + BN <= co;
-  const int row = wave * 32 + l31;
-  int64_t drow = row < cnt ? p0 + row : -1;
-  bool zero = false;   // a pair whose source index is out of range contributes a zero row
-  if (gather != nullptr && drow >= 0) {
-    const int32_t sidx = gather[drow];
-    zero = sidx < 0 || sidx >= rows_a;
-  }
-  if (scatter != nullptr && drow >= 0) {
-    drow = scatter[drow];
-    if (drow >= rows_out) drow = -1;
-  }
-  if (drow >= 0) {
-    float *dst = tmp + drow * co;
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int col = n0 + j * 32 + 8 * q + 4 * half;
-        if (nfull || col < co) {
-          float4 v = make_float4(acc[j][4 * q], acc[j][4 * q + 1], acc[j][4 * q + 2], acc[j][4 * q + 3]);
-          if (zero) v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (bias) {
-            const float4 bv = *(const float4 *)&bias[col];
-            v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-          }
-          *(float4 *)&dst[col] = v;
-        }
-      }
-  }
-}
-
-static void launch_pairs_gemm_bf16(int nt, dim3 grid, hipStream_t st, const float *A, int64_t rows_a, const int32_t *gather, const float *W, int wT,
-                                   const int32_t *koff, int ca, int co, int kvol, float *tmp, const float *bias, int64_t n_dense,
-                                   const int32_t *scatter = nullptr, int64_t rows_out = 0) {
-  switch (nt) {
-    case 1: pairs_gemm_bf16_kernel<1><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-    case 2: pairs_gemm_bf16_kernel<2><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-    case 3: pairs_gemm_bf16_kernel<3><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-    default: pairs_gemm_bf16_kernel<4><<<grid, 256, 0, st>>>(A, rows_a, gather, W, wT, koff, ca, co, kvol, tmp, bias, n_dense, scatter, rows_out); break;
-  }
-}
-
-// Column tiles per block as a function of the arguments only: the fp32 rule (gemm_nt in ftx_spconv.hip) -- 128 columns where there
-// are enough pair tiles to fill the chip, 64 on the two deepest levels, 96 for multiples of 96.
-static int gemm_bf16_nt(int co, int64_t row_tiles) {
-  int nt = co >= 128 ? 4 : (co + 31) / 32;
-  if (co > 128 && co % 96 == 0 && co % 128 != 0) nt = 3;
-  if (nt == 4 && row_tiles * ceil_div(co, 128) <= 400) nt = 2;
-  return nt;
-}
-
-extern "C" int32_t ftx_spconv_gemm_bf16_block_cols(int32_t co, int64_t n_pairs, int32_t kvol) {
-  if (co < 4 || co % 4 != 0 || n_pairs < 0 || kvol < 0) return -1;
-  return 32 * gemm_bf16_nt(co, ceil_div(n_pairs, GB_TILE) + kvol);
-}
-
-extern "C" int ftx_spconv_pairs_gemm_bf16(const float *A, int64_t rows_a, const int32_t *gather, const float *W, int32_t w_transposed,
-                                          const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *tmp, void *stream) {
-  FTX_REQUIRE(n_pairs >= 0 && rows_a >= 0 && kvol >= 1 && kvol <= 64, "ftx_spconv_pairs_gemm_bf16: bad size");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && co >= 4 && co % 4 == 0, "ftx_spconv_pairs_gemm_bf16: channels must be multiples of 4 (ca=%d co=%d)", ca, co);
-  if (n_pairs == 0) return FTX_OK;
-  FTX_REQUIRE(A && gather && W && koff && tmp && rows_a >= 1, "ftx_spconv_pairs_gemm_bf16: null pointer or empty operand");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t tiles_ub = ceil_div(n_pairs, GB_TILE) + kvol;   // sum_k ceil(cnt_k/tile) <= P/tile + kvol
-  const int nt = gemm_bf16_nt(co, tiles_ub);
-  dim3 grid((unsigned)tiles_ub, (unsigned)ceil_div(co, 32 * nt));
-  launch_pairs_gemm_bf16(nt, grid, st, A, rows_a, gather, W, w_transposed, koff, ca, co, kvol, tmp, nullptr, 0);
-  return check_launch("ftx_spconv_pairs_gemm_bf16");
-}
-
-extern "C" int ftx_spconv_pairs_gemm_scatter_bf16(const float *A, int64_t rows_a, const int32_t *gather, const int32_t *scatter, const float *W,
-                                                  int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol,
-                                                  float *out, int64_t rows_out, void *stream) {
-  FTX_REQUIRE(n_pairs >= 0 && rows_a >= 0 && rows_out >= 0 && kvol >= 1 && kvol <= 64, "ftx_spconv_pairs_gemm_scatter_bf16: bad size");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && co >= 4 && co % 4 == 0, "ftx_spconv_pairs_gemm_scatter_bf16: channels must be multiples of 4 (ca=%d co=%d)", ca, co);
-  if (n_pairs == 0) return FTX_OK;
-  FTX_REQUIRE(A && gather && scatter && W && koff && out && rows_a >= 1, "ftx_spconv_pairs_gemm_scatter_bf16: null pointer or empty operand");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t tiles_ub = ceil_div(n_pairs, GB_TILE) + kvol;
-  const int nt = gemm_bf16_nt(co, tiles_ub);
-  dim3 grid((unsigned)tiles_ub, (unsigned)ceil_div(co, 32 * nt));
-  launch_pairs_gemm_bf16(nt, grid, st, A, rows_a, gather, W, w_transposed, koff, ca, co, kvol, out, nullptr, 0, scatter, rows_out);
-  return check_launch("ftx_spconv_pairs_gemm_scatter_bf16");
-}
-
-extern "C" int ftx_rows_gemm_bf16(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co,
-                                  float *out, void *stream) {
-  FTX_REQUIRE(n >= 0, "ftx_rows_gemm_bf16: n < 0");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && co >= 4 && co % 4 == 0, "ftx_rows_gemm_bf16: channels must be multiples of 4 (ca=%d co=%d)", ca, co);
-  if (n == 0) return FTX_OK;
-  FTX_REQUIRE(A && W && out, "ftx_rows_gemm_bf16: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int nt = gemm_bf16_nt(co, ceil_div(n, GB_TILE));
-  dim3 grid((unsigned)ceil_div(n, GB_TILE), (unsigned)ceil_div(co, 32 * nt));
-  launch_pairs_gemm_bf16(nt, grid, st, A, n, nullptr, W, w_transposed, nullptr, ca, co, 1, out, bias, n);
-  return check_launch("ftx_rows_gemm_bf16");
+  pair_gemm_epilogue<NT>(acc, p0, cnt, n0, gather, rows_a, scatter, rows_out, bias, co, tmp);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -303,7 +155,6 @@ extern "C" int ftx_rows_gemm_bf16(const float *A, int64_t n, const float *W, int
 // ---------------------------------------------------------------------------------------
 constexpr int WB_BR = 64;       // pairs staged per step: four k-steps of 16
 constexpr int WB_STRIDE = 72;   // bf16 per image row (144 B): conflict-free ds_read_b128
-constexpr int WB_ROUND = 1024;  // pair indices kept in LDS at a time
 
 template <int MI, int NI, int WMG, int WNG>
 __global__ __launch_bounds__(256) void pairs_wgrad_bf16_kernel(const float *__restrict__ A, int64_t rows_a, const int32_t *__restrict__ idx_a,
@@ -316,8 +167,8 @@ __global__ __launch_bounds__(256) void pairs_wgrad_bf16_kernel(const float *__re
   constexpr int RED_B = KS > 1 ? MI * NI * 1024 * WMG * WNG * 4 : 0;          // bytes: one KS group's accumulators
   constexpr int LDS_B = STAGE_B > RED_B ? STAGE_B : RED_B;
   __shared__ __attribute__((aligned(16))) char lds[LDS_B];
-  __shared__ int32_t s_ia[WB_ROUND], s_ig[WB_ROUND];
-  __shared__ uint8_t s_ok[WB_ROUND];
+  __shared__ int32_t s_ia[kWgradRound], s_ig[kWgradRound];
+  __shared__ uint8_t s_ok[kWgradRound];
   __shared__ int s_tile[4];
   __shared__ int s_bad;
   __bf16 *At = (__bf16 *)lds, *Gt = At + TM * WB_STRIDE;
@@ -326,31 +177,7 @@ __global__ __launch_bounds__(256) void pairs_wgrad_bf16_kernel(const float *__re
   const int half = lane >> 5, l31 = lane & 31;
   const int wq = wave % (WMG * WNG), ks = wave / (WMG * WNG);
   const int wm = wq % WMG, wn = wq / WMG;
-  if (tid < 64) {   // tile -> (offset, pair range), as pairs_wgrad_kernel
-    const int b = blockIdx.x;
-    int c = 0;
-    if (tid < kvol) c = koff ? koff[tid + 1] - koff[tid] : n_dense;
-    int nt = (c + tile_len - 1) / tile_len;
-    int incl = nt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      int v = __shfl_up(incl, off, 64);
-      if (tid >= off) incl += v;
-    }
-    int excl = incl - nt;
-    bool mine = (tid < kvol) && b >= excl && b < incl;
-    unsigned long long msk = __ballot(mine);
-    if (mine) {
-      int t = b - excl;
-      int first = (koff ? koff[tid] : 0) + t * tile_len;
-      int left = c - t * tile_len;
-      s_tile[0] = tid;
-      s_tile[1] = first;
-      s_tile[2] = first + (left > tile_len ? tile_len : left);
-      s_tile[3] = nt;
-    }
-    if (msk == 0ull && tid == 0) s_tile[0] = -1;
-  }
+  pair_tile_scan<true>(koff, kvol, tile_len, n_dense, s_tile);   // tile -> (offset, pair range)
   __syncthreads();
   const int k = s_tile[0];
   if (k < 0) return;  // surplus block of the upper-bound grid
@@ -450,30 +277,9 @@ __global__ __launch_bounds__(256) void pairs_wgrad_bf16_kernel(const float *__re
     }
   };
 
-  for (rbase = lo; rbase < hi; rbase += WB_ROUND) {
-    rend = (rbase + WB_ROUND < hi) ? rbase + WB_ROUND : hi;
-    __syncthreads();  // previous round's gathers are done with s_ia / s_ig
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    for (int t = tid; t < WB_ROUND; t += 256) {
-      // every slot gets a loadable row: slots past the end repeat row 0, malformed pairs are flagged and zeroed at store time
-      int32_t ia = 0, ig = 0;
-      uint8_t ok = 0;
-      if (t < rend - rbase) {
-        ia = idx_a ? idx_a[rbase + t] : rbase + t;
-        ig = idx_g ? idx_g[rbase + t] : rbase + t;
-        ok = 1;
-        if (ia < 0 || ia >= rows_a || ig < 0 || ig >= rows_g) {
-          ia = ig = 0;
-          ok = 0;
-          s_bad = 1;
-        }
-      }
-      s_ia[t] = ia;
-      s_ig[t] = ig;
-      s_ok[t] = ok;
-    }
-    __syncthreads();
+  for (rbase = lo; rbase < hi; rbase += kWgradRound) {
+    rend = (rbase + kWgradRound < hi) ? rbase + kWgradRound : hi;
+    wgrad_stage_indices(idx_a, rows_a, idx_g, rows_g, rbase, rend, s_ia, s_ig, s_ok, &s_bad);
     load_step(rbase);
     for (int p0 = rbase; p0 < rend; p0 += WB_BR) {
       store_step(p0);
@@ -484,29 +290,7 @@ __global__ __launch_bounds__(256) void pairs_wgrad_bf16_kernel(const float *__re
     }
   }
 
-  if (KS > 1) {  // sum the k-step subsets of the KS wave groups, fixed order (the staging images are free now)
-    float *red = (float *)lds;
-    for (int r = 1; r < KS; ++r) {
-      if (ks == r) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) red[(((wq * MI + i) * NI + j) * 16 + g) * 64 + lane] = acc[i][j][g];
-      }
-      __syncthreads();
-      if (ks == 0) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[i][j][g] += red[(((wq * MI + i) * NI + j) * 16 + g) * 64 + lane];
-      }
-      __syncthreads();
-    }
-  }
+  wgrad_ks_reduce<MI, NI, KS>(acc, (float *)lds, wq, ks, lane);   // the k-step subsets of the KS wave groups (the staging images are free now)
 
   if (ks == 0) {
     const int64_t mat = (int64_t)ca * cg;
@@ -529,110 +313,55 @@ __global__ __launch_bounds__(256) void pairs_wgrad_bf16_kernel(const float *__re
   }
 }
 
-// Tile shape per channel count: the sides of wgrad_config (ftx_spconv.hip) -- M side 32 / 64 / 96 (multiples of 96 that are not
-// multiples of 128) / 128, N side the same; 96 x 96 becomes 128 x 96.
-struct WgradBf16Cfg { int mi, wmg, ni, wng; };
-static WgradBf16Cfg wgrad_bf16_config(int ca, int cg) {
-  WgradBf16Cfg c;
-  if (ca <= 32) { c.mi = 1; c.wmg = 1; }
-  else if (ca <= 64) { c.mi = 2; c.wmg = 1; }
-  else if (ca % 96 == 0 && ca % 128 != 0) { c.mi = 3; c.wmg = 1; }
-  else { c.mi = 2; c.wmg = 2; }
-  if (cg <= 32) { c.ni = 1; c.wng = 1; }
-  else if (cg <= 64) { c.ni = 2; c.wng = 1; }
-  else if (cg % 96 == 0 && cg % 128 != 0) { c.ni = 3; c.wng = 1; }
-  else { c.ni = 2; c.wng = 2; }
-  if (c.mi == 3 && c.ni == 3) { c.mi = 2; c.wmg = 2; }
-  return c;
-}
-
-// Resident blocks per CU of each instantiation, as a TABLE (the tile length, the workspace and the summation tree must be functions of
-// the arguments alone): min(8, 512 / VGPRs rounded up to 8, 160 KiB / LDS) from the gfx950 code object (llvm-readelf --notes: .vgpr_count
-// 64 / 100-104 / 136-152 / 188-244 / 312).  tests/test_spconv_bf16_host.py recomputes them from the built object.
-static int wgrad_bf16_occ(const WgradBf16Cfg &c) {
-  // rows: M side (mi, wmg) = (1,1) (2,1) (3,1) (2,2); columns: N side (ni, wng) in the same order
-  static const int occ[4][4] = {{8, 4, 3, 3}, {4, 3, 2, 2}, {3, 2, 1, 2}, {3, 2, 2, 2}};
-  auto side = [](int i, int w) { return w == 2 ? 3 : i - 1; };
-  return occ[side(c.mi, c.wmg)][side(c.ni, c.wng)];
-}
-// (mi, wmg, ni, wng) -> table value, for the build-time check of the table against the code object
-extern "C" int32_t ftx_spconv_wgrad_bf16_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng) {
-  if (!((mi >= 1 && mi <= 3 && wmg == 1) || (mi == 2 && wmg == 2)) || !((ni >= 1 && ni <= 3 && wng == 1) || (ni == 2 && wng == 2))) return -1;
-  WgradBf16Cfg c{mi, wmg, ni, wng};
-  return wgrad_bf16_occ(c);
-}
-constexpr int WGRAD_BF16_CUS = 256;   // MI355X; a constant of the tiling, not a device query
-
-// Pairs per tile: R full rounds of CUs x resident blocks, R as small as keeps a tile <= 4096 pairs (the rule of wgrad_tile_len).
-static int wgrad_bf16_tile_len(int64_t n_pairs, int ca, int cg, int kvol) {
-  const WgradBf16Cfg c = wgrad_bf16_config(ca, cg);
-  const int64_t mn_tiles = ceil_div(ca, 32 * c.mi * c.wmg) * ceil_div(cg, 32 * c.ni * c.wng);
-  const int64_t slots = (int64_t)WGRAD_BF16_CUS * wgrad_bf16_occ(c);
-  int64_t len = 256;
-  for (int rounds = 1; rounds <= 64; ++rounds) {
-    int64_t tiles = (slots * rounds * 15 / 16) / mn_tiles - (kvol + 1) / 2;
-    if (tiles < 1) tiles = 1;
-    len = ceil_div(ceil_div(n_pairs, tiles), 2 * WB_BR) * 2 * WB_BR;
-    if (len <= 4096) break;
+// ---------------------------------------------------------------------------------------
+// the family's description and entries (ftx_spconv_common.h): the tile rules of the fp32 family with this family's table and step
+// ---------------------------------------------------------------------------------------
+struct SpconvBf16 {
+  static constexpr const char *pairs_name = "ftx_spconv_pairs_gemm_bf16", *scatter_name = "ftx_spconv_pairs_gemm_scatter_bf16",
+                              *rows_name = "ftx_rows_gemm_bf16", *wgrad_name = "ftx_spconv_pairs_wgrad_bf16";
+  // .vgpr_count 64 / 100-104 / 136-152 / 188-244 / 312
+  static constexpr int wgrad_blocks[4][4] = {{8, 4, 3, 3}, {4, 3, 2, 2}, {3, 2, 1, 2}, {3, 2, 2, 2}};
+  static constexpr int wgrad_step = 2 * WB_BR;
+  template <int NT>
+  static void gemm(dim3 grid, hipStream_t st, const PairsGemmArgs &a) {
+    pairs_gemm_bf16_kernel<NT><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.gather, a.W, a.w_transposed, a.koff, a.ca, a.co, a.kvol, a.out, a.bias, a.n_dense,
+                                                     a.scatter, a.rows_out);
   }
-  if (len < 256) len = 256;
-  return (int)len;
+  template <int MI, int NI, int WMG, int WNG>
+  static void wgrad(dim3 grid, hipStream_t st, const PairsWgradArgs &a) {
+    pairs_wgrad_bf16_kernel<MI, NI, WMG, WNG><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.idx_a, a.G, a.rows_g, a.idx_g, a.koff, a.ca, a.cg, a.kvol,
+                                                                    a.tile_len, a.part, a.dW, a.n_dense);
+  }
+};
+
+extern "C" int32_t ftx_spconv_gemm_bf16_block_cols(int32_t co, int64_t n_pairs, int32_t kvol) { return spconv_gemm_block_cols(co, n_pairs, kvol); }
+
+extern "C" int ftx_spconv_pairs_gemm_bf16(const float *A, int64_t rows_a, const int32_t *gather, const float *W, int32_t w_transposed,
+                                          const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *tmp, void *stream) {
+  return spconv_pairs_entry<SpconvBf16>(false, A, rows_a, gather, nullptr, W, w_transposed, koff, n_pairs, ca, co, kvol, tmp, 0, stream);
+}
+
+extern "C" int ftx_spconv_pairs_gemm_scatter_bf16(const float *A, int64_t rows_a, const int32_t *gather, const int32_t *scatter, const float *W,
+                                                  int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol,
+                                                  float *out, int64_t rows_out, void *stream) {
+  return spconv_pairs_entry<SpconvBf16>(true, A, rows_a, gather, scatter, W, w_transposed, koff, n_pairs, ca, co, kvol, out, rows_out, stream);
+}
+
+extern "C" int ftx_rows_gemm_bf16(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co,
+                                  float *out, void *stream) {
+  return spconv_rows_entry<SpconvBf16>(A, n, W, w_transposed, bias, ca, co, out, stream);
+}
+
+extern "C" int32_t ftx_spconv_wgrad_bf16_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng) {
+  return spconv_wgrad_table_blocks<SpconvBf16>(mi, wmg, ni, wng);
 }
 
 extern "C" size_t ftx_spconv_pairs_wgrad_bf16_workspace_bytes(int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol) {
-  if (n_pairs <= 0 || ca <= 0 || cg <= 0 || kvol <= 0) return 256;
-  const int len = wgrad_bf16_tile_len(n_pairs, ca, cg, kvol);
-  return sizeof(float) * (size_t)(ceil_div(n_pairs, len) + kvol) * ca * cg;
-}
-
-template <int MI, int WMG>
-static void launch_wgrad_bf16_n(const WgradBf16Cfg &c, dim3 grid, hipStream_t st, const float *A, int64_t rows_a, const int32_t *idx_a, const float *G,
-                                int64_t rows_g, const int32_t *idx_g, const int32_t *koff, int ca, int cg, int kvol, int tl, float *part, float *dW, int n_dense) {
-  if (c.ni == 1)
-    pairs_wgrad_bf16_kernel<MI, 1, WMG, 1><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
-  else if (c.ni == 3)
-    pairs_wgrad_bf16_kernel<MI, 3, WMG, 1><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
-  else if (c.wng == 1)
-    pairs_wgrad_bf16_kernel<MI, 2, WMG, 1><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
-  else
-    pairs_wgrad_bf16_kernel<MI, 2, WMG, 2><<<grid, 256, 0, st>>>(A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tl, part, dW, n_dense);
+  return spconv_wgrad_workspace_bytes<SpconvBf16>(n_pairs, ca, cg, kvol);
 }
 
 extern "C" int ftx_spconv_pairs_wgrad_bf16(const float *A, int64_t rows_a, const int32_t *idx_a, const float *G, int64_t rows_g, const int32_t *idx_g,
                                            const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol, float *dW, void *workspace,
                                            size_t workspace_bytes, void *stream) {
-  FTX_REQUIRE(n_pairs >= 0 && rows_a >= 0 && rows_g >= 0 && kvol >= 1 && kvol <= 64, "ftx_spconv_pairs_wgrad_bf16: bad size");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && cg >= 4 && cg % 4 == 0, "ftx_spconv_pairs_wgrad_bf16: channels must be multiples of 4 (ca=%d cg=%d)", ca, cg);
-  FTX_REQUIRE(dW, "ftx_spconv_pairs_wgrad_bf16: null dW");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t mat = (int64_t)ca * cg;
-  if (n_pairs == 0) {
-    if (hipMemsetAsync(dW, 0, sizeof(float) * kvol * mat, st) != hipSuccess) return check_launch("ftx_spconv_pairs_wgrad_bf16 memset");
-    return FTX_OK;
-  }
-  FTX_REQUIRE(A && G && rows_a >= 1 && rows_g >= 1, "ftx_spconv_pairs_wgrad_bf16: null pointer or empty operand");
-  const bool dense = (idx_a == nullptr && idx_g == nullptr && koff == nullptr);
-  FTX_REQUIRE(dense || (idx_a && idx_g && koff), "ftx_spconv_pairs_wgrad_bf16: idx_a, idx_g and koff must be all set or all null (dense rows)");
-  FTX_REQUIRE(!dense || (kvol == 1 && n_pairs <= rows_a && n_pairs <= rows_g), "ftx_spconv_pairs_wgrad_bf16: dense mode needs kvol == 1 and n_pairs rows in A and G");
-  FTX_REQUIRE(n_pairs < 0x7fffffff, "ftx_spconv_pairs_wgrad_bf16: too many pairs");
-  const int tile_len = wgrad_bf16_tile_len(n_pairs, ca, cg, kvol);
-  const int64_t tiles = ceil_div(n_pairs, tile_len) + kvol;
-  const size_t need = sizeof(float) * (size_t)tiles * mat;
-  if (!workspace || workspace_bytes < need) {
-    set_error("ftx_spconv_pairs_wgrad_bf16: workspace %zu < required %zu", workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
-  float *part = (float *)workspace;
-  const WgradBf16Cfg c = wgrad_bf16_config(ca, cg);
-  dim3 grid((unsigned)tiles, (unsigned)ceil_div(ca, 32 * c.mi * c.wmg), (unsigned)ceil_div(cg, 32 * c.ni * c.wng));
-  if (c.mi == 1)
-    launch_wgrad_bf16_n<1, 1>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  else if (c.mi == 3)
-    launch_wgrad_bf16_n<3, 1>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  else if (c.wmg == 1)
-    launch_wgrad_bf16_n<2, 1>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  else
-    launch_wgrad_bf16_n<2, 2>(c, grid, st, A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, part, dW, (int)n_pairs);
-  launch_wgrad_reduce(part, koff, kvol, tile_len, (int)n_pairs, mat, tiles, dW, st);
-  return check_launch("ftx_spconv_pairs_wgrad_bf16");
+  return spconv_wgrad_entry<SpconvBf16>(A, rows_a, idx_a, G, rows_g, idx_g, koff, n_pairs, ca, cg, kvol, dW, workspace, workspace_bytes, stream);
 }

@@ -107,7 +107,8 @@ def conv_check(kernel, what, got, A, W, src, dst, koff, n_dst):
 
 
 def wgrad_bound_m(lib, koff, ca, cg):
-    """Longest addition chain into dW[k] per offset for the weight gradient's tiling: tile_len + tiles of the offset + 16."""
+    """Longest addition chain into dW[k] per offset for the weight gradient's tiling (csrc/ftx_spconv_common.h, spconv_wgrad_tile_len
+    and wgrad_reduce_kernel): tile_len + tiles of the offset + 16."""
     kvol = koff.shape[0] - 1
     n = int(koff[-1])
     length = S.wgrad_tile_len(lib, n, ca, cg, kvol)

@@ -1,7 +1,7 @@
 """Which tile shape each sparse-convolution launch reaches (tests/test_spconv_regimes.py, tests/test_spconv_regimes_gpu.py).
 
 The pair GEMM (ftx_spconv_pairs_gemm, _scatter, ftx_rows_gemm), the reduce and the weight gradient (ftx_spconv_pairs_wgrad) of
-csrc/ftx_spconv.hip pick their tiles from the sizes of their arguments.  This module restates those choices in Python, checked
+csrc/ftx_spconv.hip pick their tiles from the sizes of their arguments (the rules: csrc/ftx_spconv_common.h).  This module restates those choices in Python, checked
 against the library's own host queries (ftx_spconv_gemm_block_cols, ftx_spconv_pairs_wgrad_workspace_bytes,
 ftx_spconv_wgrad_resident_blocks), and holds the table of production layers that the GPU tests run at full size."""
 from __future__ import annotations
@@ -55,7 +55,7 @@ def cdiv(a, b):
 
 
 def gemm_nt(co, row_tiles):
-    """csrc/ftx_spconv.hip gemm_nt(): 32-column tiles per block."""
+    """csrc/ftx_spconv_common.h spconv_gemm_nt(): 32-column tiles per block."""
     nt = 4 if co >= 128 else (co + 31) // 32
     if co > 128 and co % 96 == 0 and co % 128 != 0:
         nt = 3
@@ -70,7 +70,7 @@ def block_cols(co, n_pairs, kvol):
 
 
 def wgrad_config(ca, cg):
-    """csrc/ftx_spconv.hip wgrad_config(): (MI, WMG, NI, WNG) of pairs_wgrad_kernel<MI, NI, WMG, WNG>."""
+    """csrc/ftx_spconv_common.h spconv_wgrad_config(): (MI, WMG, NI, WNG) of pairs_wgrad_kernel<MI, NI, WMG, WNG>."""
     def side(c):
         if c <= 32:
             return (1, 1)
@@ -86,7 +86,7 @@ def wgrad_config(ca, cg):
 
 
 def wgrad_tile_len(lib, n_pairs, ca, cg, kvol):
-    """csrc/ftx_spconv.hip wgrad_tile_len(): pairs per weight-gradient tile."""
+    """csrc/ftx_spconv_common.h spconv_wgrad_tile_len<SpconvF32>(): pairs per weight-gradient tile."""
     mi, wmg, ni, wng = wgrad_config(ca, cg)
     mn_tiles = cdiv(ca, 32 * mi * wmg) * cdiv(cg, 32 * ni * wng)
     slots = 256 * int(lib.ftx_spconv_wgrad_resident_blocks(ca, cg))

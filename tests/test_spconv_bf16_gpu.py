@@ -38,7 +38,8 @@ def bf(t):
 
 
 def wgrad_bf16_tile_len(lib, n_pairs, ca, cg, kvol):
-    """csrc/ftx_spconv_bf16.hip wgrad_bf16_tile_len(), checked against the library's workspace query."""
+    """csrc/ftx_spconv_common.h spconv_wgrad_tile_len<SpconvBf16>() (table and step: csrc/ftx_spconv_bf16.hip), checked against the library's
+    workspace query."""
     mi, wmg, ni, wng = S.wgrad_config(ca, cg)
     mn_tiles = S.cdiv(ca, 32 * mi * wmg) * S.cdiv(cg, 32 * ni * wng)
     slots = 256 * int(lib.ftx_spconv_wgrad_bf16_table_blocks(mi, wmg, ni, wng))
