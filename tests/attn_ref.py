@@ -44,6 +44,43 @@ fault is below fp32 rounding and no bar can see it.  Two constructed cases: "asc
 has a positive component: every key tile raises the running maximum, so the rescale runs in every iteration) and "late_max" (the
 dominant key of every query is the last valid token: it sits in the ragged tile, and for most (T, split) in a key group other than 0,
 so the (m, l, O) merge has to carry it).
+
+The bf16-operand kernels (attn_fwd_bf16_kernel, attn_delta_bf16_kernel, attn_bwd_kv_bf16_kernel, attn_bwd_q_bf16_kernel) are held to
+their precision contract (csrc/ftx_attn.hip, "Precision contract") by the same method.
+
+rounded(a)                         bf16 round-to-nearest-even, as float64: what the kernels make of Q, K, V and dO.
+reference(rounded(qkv), rounded(go), scale)      THE reference of the bf16 kernels: float64 on the rounded operands, nothing else rounded.
+yardstick_bf16(qkv, go, scale)     the contract stated unfused in float64: rounded operands; P = softmax(S) rounded to bf16 as the operand
+                                   of P V and P^T dO; delta = rowsum(out * bf16(dO)); dS = P (dP - delta) scale formed from the unrounded P
+                                   and rounded to bf16 as the operand of dS K and dS^T Q.  Its lse is the reference's.
+bar_bf16(E_yard, E32_lse, max_abs_lse)           the bars, from E_yard = errors(yardstick_bf16, ...) and the float32 yardstick's lse error.
+emulate_bf16(qkv, go, scale, split)              the numpy model of the bf16 kernels: emulate's tile loop with the contract's roundings.
+
+    out, dq, dk, dv:   4 * E_yard + 4 * u * max(1, max|lse|)          (u = 2^-24 still: the accumulators and the exponent path are fp32)
+    lse:               4 * E32 + 8 * u                                 (the fp32 bar, E32 on the rounded operands)
+
+* E_yard is what the contract's two operand roundings (P, dS; relative size 2^-9 each) cost on these inputs: ~1e-3 of a gradient on
+  flat softmax rows, less where P is nearly 0 or 1 (such values round exactly or nearly so), nothing at T = 1 (P = 1).
+* The factor 4 carries over, for the same reason.  The kernels do not round the element the yardstick rounds: the forward rounds the
+  unnormalised exp2(s - m_running) and divides the fp32 sum by l afterwards (rescales by exp2(m_old - m_new) and 1 / l in between act
+  on the fp32 accumulator and keep a rounding's relative size), the yardstick rounds the normalised P; the backward rounds an fp32 P
+  rebuilt from lse and a dS formed in fp32.  Each is a rounding of relative size <= 2^-9 of the same element at another position of
+  its mantissa, so the two sets of rounding errors are independent and of one size, and the error of a sum over them is within
+  ~sqrt(2) of the yardstick's: the situation of two orders of one fp32 sum above.  Where the kernel happens to round the same value
+  (dS, which differs from the yardstick's by fp32 rounding only) its error equals the yardstick's, a ratio of 0.25.  4 leaves no room
+  for a missing or extra key, a lost tile or an operand rounded twice: tests/test_attn_bf16_host.py shows each.
+* The additive fp32 term stays.  The exponent path is the fp32 kernels': scores in the exp2 domain, P rebuilt in the backward as
+  exp2(S * sl2 - lse * log2e) with |S * sl2| ~ |lse * log2e| = x; the four roundings of size u * x are (1) the product S * sl2 (the
+  scale is no longer folded into an operand, it multiplies the fp32 score), (2), (3), (4) as above: 4 * u * |lse| relative on P.  On the
+  sharp rows of the "large" inputs (|lse| ~ 5000) the softmax is saturated, P is 0 or 1 and rounds exactly, and this term is their
+  whole error (E_yard of those inputs comes from their quiet rows); at T = 1 E_yard is exactly 0 and the term keeps the bar
+  positive.
+* lse gets the fp32 bar.  By the contract the scores are exact fp32 sums of exact products (bf16 x bf16 fits fp32), and m, l and lse
+  come from the unrounded exponentials: the kernel's lse is an fp32 evaluation of the reference's own formula on the same operands,
+  with the roundings counted above for fp32.  The yardstick's lse is float64 (E_yard["lse"] = 0), so E32 comes from
+  reference(rounded(qkv), rounded(go), scale, float32).  This is the tensor that pins the operand rounding: operands truncated instead
+  of rounded, the scale folded into Q before rounding, or a row sum over the rounded P move lse by 2^-9-sized amounts: tens to
+  thousands of bars.
 """
 import numpy as np
 import torch
@@ -57,6 +94,14 @@ LN2 = F32(0.6931471805599453)
 
 KINDS = {"gauss": 1.0, "peaked": 3.0, "large": 30.0}
 QUIET = slice(5, None, 8)      # every 8th query, from token 5
+
+# The accuracy cases of the GPU tests (tests/test_attn_fp32_gpu.py, tests/test_attn_bf16_gpu.py): (kind, T, scale).
+EDGES = [1, 31, 32, 33, 64, 127, 128, 129, 257, 578]     # below one 32-token tile, its edges, the 4-wave block's edges, the ViT's T
+ACCURACY = ([(kind, T, 0.125) for kind in ("gauss", "peaked") for T in EDGES] +
+            [(kind, 129, 0.1) for kind in ("gauss", "peaked")] +                      # a scale that is not a power of two
+            # 290: the last token lies in key tile 9, i.e. in a key group other than 0 under every split (at 257 it is tile 8: group 0)
+            [(kind, T, 0.125) for kind in ("ascending", "late_max") for T in (70, 257, 290)])
+LARGE_T = [100, 578]
 
 
 # ---------------------------------------------------------------- inputs
@@ -103,6 +148,28 @@ def reference(qkv, go, scale, dtype=torch.float64):
     return out.detach().double(), lse.detach().double(), r.grad.double()
 
 
+def rounded(a):
+    """bf16 round-to-nearest-even of a float32 array or tensor, as a float64 tensor."""
+    return _t(a, torch.float32).to(torch.bfloat16).double()
+
+
+def yardstick_bf16(qkv, go, scale):
+    """The bf16 kernels' precision contract as explicit float64 ops on the CPU (module docstring): out, lse, grad_qkv, shaped as
+    reference's."""
+    B, T, _, H, D = qkv.shape
+    rb = lambda a: a.to(torch.bfloat16).double()          # the rounding of an MFMA operand
+    q, k, v = rounded(qkv).permute(2, 0, 3, 1, 4)
+    g = rounded(go).reshape(B, T, H, D).transpose(1, 2)
+    s = (q @ k.transpose(-2, -1)) * scale
+    lse = torch.logsumexp(s, dim=-1)
+    p = s.softmax(dim=-1)
+    out = rb(p) @ v
+    delta = (out * g).sum(-1, keepdim=True)
+    ds = rb(p * (g @ v.transpose(-2, -1) - delta) * scale)
+    grad = torch.stack([ds @ k, ds.transpose(-2, -1) @ q, rb(p).transpose(-2, -1) @ g], 0).permute(1, 3, 0, 2, 4)
+    return out.transpose(1, 2).reshape(B, T, H * D), lse, grad.contiguous()
+
+
 def abs_gradients(qkv, go, scale):
     """(dQabs, dKabs), each (B, T, H, 64) float64: dPabs = |dO| |V|^T, dSabs = P (dPabs + sum_k P dPabs) scale, dQabs = dSabs |K|,
     dKabs = dSabs^T |Q|."""
@@ -140,6 +207,14 @@ def bar(E32, max_abs_lse):
     return {n: tuple(4 * e + (8 * U if n == "lse" else extra) for e in E32[n]) for n in TENSORS}
 
 
+def bar_bf16(E_yard, E32_lse, max_abs_lse):
+    """The bars for errors(...) of the bf16-operand kernels against reference(rounded(qkv), rounded(go), scale): out, dq, dk, dv from
+    E_yard = errors(yardstick_bf16(...), ...), lse from E32_lse = errors(float32 reference on the rounded operands, ...)["lse"]
+    (derivation: module docstring)."""
+    extra = 4 * U * max(1.0, float(max_abs_lse))
+    return {n: tuple(4 * e + 8 * U for e in E32_lse) if n == "lse" else tuple(4 * e + extra for e in E_yard[n]) for n in TENSORS}
+
+
 def ratios(E, bars):
     """{tensor: (L2 error / its bar, max-abs error / its bar)}."""
     return {n: tuple(e / b for e, b in zip(E[n], bars[n])) for n in TENSORS}
@@ -167,6 +242,29 @@ class Case:
         return ratios(E, self.bars), E
 
 
+class CaseBf16:
+    """Case for the bf16-operand kernels.  qkv, go: the unrounded float32 inputs (what the kernels are given); ref64 and absg: float64 on
+    the rounded operands; E_yard: the bf16 yardstick's errors; E32: the float32 reference's (on the rounded operands); E_bar: the errors
+    the bars are built from (E_yard with E32's lse), which is what format_row prints beside the measured ones."""
+
+    def __init__(self, kind, B, T, H, scale, seed=0):
+        self.kind, self.shape, self.scale = kind, (B, T, H), scale
+        self.qkv, self.go = make_inputs(kind, B, T, H, seed)
+        rq, rg = rounded(self.qkv), rounded(self.go)
+        self.ref64 = reference(rq, rg, scale, torch.float64)
+        self.absg = abs_gradients(rq, rg, scale)
+        self.max_lse = float(self.ref64[1].abs().max())
+        self.E_yard = errors(yardstick_bf16(self.qkv, self.go, scale), self.ref64, self.absg)
+        self.E32 = errors(reference(rq, rg, scale, torch.float32), self.ref64, self.absg)
+        self.E_bar = dict(self.E_yard, lse=self.E32["lse"])
+        self.bars = bar_bf16(self.E_yard, self.E32["lse"], self.max_lse)
+
+    def ratios(self, got):
+        """(ratios to the bars, errors) of got = (out, lse, grad_qkv)."""
+        E = errors(got, self.ref64, self.absg)
+        return ratios(E, self.bars), E
+
+
 def format_row(label, E32, E, r):
     """One line of profiles/attn_fp32_accuracy.txt: per tensor the yardstick's error, the measured error and its ratio to the bar
     (the max-abs figures; the L2 ones are smaller throughout)."""
@@ -176,12 +274,19 @@ def format_row(label, E32, E, r):
 # ---------------------------------------------------------------- the kernels' arithmetic in numpy fp32
 FAULTS = ("drop_last_key", "extra_zero_key", "delta_of_next_head", "p_bf16", "qk_10_bits", "ds_without_scale", "dv_misses_a_tile",
           "lse_of_next_query")
+FAULTS_BF16 = ("drop_last_key", "extra_zero_key", "delta_of_next_head", "dv_misses_a_tile", "lse_of_next_query",
+               "operands_truncated", "scale_folded_into_q", "rowsum_of_rounded_p")
 
 
 def _bf16(a):
     """round-to-nearest-even to 8 mantissa bits, as float32"""
     b = np.ascontiguousarray(a, F32).view(np.uint32)
     return ((b + 0x7FFF + ((b >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(F32)
+
+
+def _trunc16(a):
+    """truncation to 8 mantissa bits (bf16 by dropping the low half), as float32"""
+    return (np.ascontiguousarray(a, F32).view(np.uint32) & 0xFFFF0000).view(F32)
 
 
 def _trunc10(a):
@@ -218,19 +323,51 @@ def emulate(qkv, go, scale, split=1, fault=None, bwd_split=None):
     `fault` (one of FAULTS) plants one defect, for tests/test_attn_fp32_host.py to show that the bars reject it.
     Returns out, lse, grad_qkv as float32 arrays."""
     assert fault is None or fault in FAULTS, fault
+    return _emulate(qkv, go, scale, split, fault, bwd_split, False)
+
+
+def emulate_bf16(qkv, go, scale, split=1, fault=None, bwd_split=None):
+    """The bf16-operand kernels in the same tile loop, with their precision contract: Q, K, V and dO rounded to bf16 (the products of
+    such operands are exact in fp32, the sums are fp32), sl2 applied to the fp32 score, m / l / lse from the unrounded exponentials, P
+    rounded as the operand of P V and P^T dO, dS = P (dP - delta) scale formed in fp32 from the unrounded P and rounded as the operand of
+    dS^T Q and dS K, delta = rowsum(O * bf16(dO)).  `fault` (one of FAULTS_BF16): the structural faults of emulate, or a breach of the
+    contract: "operands_truncated" (Q, K, V, dO cut to bf16 instead of rounded to nearest even), "scale_folded_into_q" (sl2 multiplied
+    into Q -- K in the dK / dV pass -- before the rounding), "rowsum_of_rounded_p" (l sums the bf16 P).
+    Returns out, lse, grad_qkv as float32 arrays."""
+    assert fault is None or fault in FAULTS_BF16, fault
+    return _emulate(qkv, go, scale, split, fault, bwd_split, True)
+
+
+def _emulate(qkv, go, scale, split, fault, bwd_split, bf16):
     B, T, _, H, D = qkv.shape
     x = np.ascontiguousarray(qkv, F32).transpose(2, 0, 3, 1, 4)        # (3, B, H, T, D)
     q, k, v = x[0], x[1], x[2]
     g = np.ascontiguousarray(go, F32).reshape(B, T, H, D).transpose(0, 2, 1, 3)
     scale = F32(scale)
     sl2 = scale * LOG2E
-    qs_src, ks_src = (_trunc10(q), _trunc10(k)) if fault == "qk_10_bits" else (q, k)
-    round_p = _bf16 if fault == "p_bf16" else (lambda a: a)
+    same = lambda a: a
+    # qs, ks: the score operands where sl2 is folded in (Q in the forward and dQ, K in dK / dV); qs_src, ks_src: the other operand;
+    # score(a, b^T): the scores in the exp2 domain
+    if bf16:
+        cut = _trunc16 if fault == "operands_truncated" else _bf16
+        q, k, v, g = cut(q), cut(k), cut(v), cut(g)
+        qs_src, ks_src = q, k
+        if fault == "scale_folded_into_q":
+            qs, ks, score = _bf16(q * sl2), _bf16(k * sl2), (lambda a, bt: a @ bt)
+        else:
+            qs, ks, score = q, k, (lambda a, bt: (a @ bt) * sl2)
+        round_p = round_ds = _bf16                                       # as MFMA operands only
+        p_of_ds = same                                                   # dS is formed from the unrounded P
+        p_of_l = _bf16 if fault == "rowsum_of_rounded_p" else same
+    else:
+        qs_src, ks_src = (_trunc10(q), _trunc10(k)) if fault == "qk_10_bits" else (q, k)
+        qs, ks, score = qs_src * sl2, ks_src * sl2, (lambda a, bt: a @ bt)
+        round_p = _bf16 if fault == "p_bf16" else same
+        round_ds, p_of_ds, p_of_l = same, round_p, same
     tiles = [(t0, min(t0 + 32, T)) for t0 in range(0, T, 32)]
     t_keys = T - 1 if fault == "drop_last_key" and T > 1 else T          # the forward's key mask
 
     # forward
-    qs = qs_src * sl2
     parts = []
     for grp in range(split):
         m = np.full((B, H, T), -np.inf, F32)
@@ -243,11 +380,11 @@ def emulate(qkv, go, scale, split=1, fault=None, bwd_split=None):
                 vt = np.concatenate([vt, np.zeros_like(vt[:, :, :1])], 2)
             if kt.shape[2] == 0:
                 continue
-            s = qs @ kt.transpose(0, 1, 3, 2)
+            s = score(qs, kt.transpose(0, 1, 3, 2))
             m_new = np.maximum(m, s.max(-1))
             p = np.exp2(s - m_new[..., None])
             alpha = np.exp2(m - m_new)
-            l = l * alpha + p.sum(-1, dtype=F32)
+            l = l * alpha + p_of_l(p).sum(-1, dtype=F32)
             o = o * alpha[..., None] + round_p(p) @ vt
             m = m_new
         parts.append((m, l, o))
@@ -268,17 +405,16 @@ def emulate(qkv, go, scale, split=1, fault=None, bwd_split=None):
     def p_ds(s, rows, cols):
         p = np.exp2(s - lse2[:, :, rows, None])
         dp = g[:, :, rows] @ v[:, :, cols].transpose(0, 1, 3, 2)
-        return round_p(p), round_p(p) * (dp - delta[:, :, rows, None]) * ds_scale
+        return round_p(p), round_ds(p_of_ds(p) * (dp - delta[:, :, rows, None]) * ds_scale)
 
     add = lambda a, b: tuple(x + y for x, y in zip(a, b))
     every = slice(0, T)
-    ks = ks_src * sl2                                                       # dK, dV: groups of query tiles
-    parts = []
+    parts = []                                                              # dK, dV: groups of query tiles
     for grp in range(split):
         dv, dk = np.zeros((B, H, T, D), F32), np.zeros((B, H, T, D), F32)
         for t0, t1 in tiles[grp::split]:
             rows = slice(t0, t1)
-            p, ds = p_ds(qs_src[:, :, rows] @ ks.transpose(0, 1, 3, 2), rows, every)
+            p, ds = p_ds(score(qs_src[:, :, rows], ks.transpose(0, 1, 3, 2)), rows, every)
             if not (fault == "dv_misses_a_tile" and t1 == T):
                 dv = dv + p.transpose(0, 1, 3, 2) @ g[:, :, rows]
             dk = dk + ds.transpose(0, 1, 3, 2) @ q[:, :, rows]
@@ -289,7 +425,7 @@ def emulate(qkv, go, scale, split=1, fault=None, bwd_split=None):
         dq = np.zeros((B, H, T, D), F32)
         for t0, t1 in tiles[grp::split]:
             cols = slice(t0, t1)
-            _, ds = p_ds(qs @ ks_src[:, :, cols].transpose(0, 1, 3, 2), every, cols)
+            _, ds = p_ds(score(qs, ks_src[:, :, cols].transpose(0, 1, 3, 2)), every, cols)
             dq = dq + ds @ k[:, :, cols]
         parts.append((dq,))
     dq, = _tree(parts, add)

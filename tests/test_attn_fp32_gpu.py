@@ -3,9 +3,11 @@ run time from the float32 yardstick (tests/attn_ref.py: bar(E32, max|lse|); no t
 structural properties of both kernel families: a (batch, head) slice never sees its neighbours (bitwise), the automatic tiling is
 the documented explicit one (bitwise), nothing is read or written outside the operands (guard bands), results repeat run to run.
 
-The bf16-operand kernels keep their own bars: check_against_rounded, OUT_TOL and GRAD_TOL of tests/test_attn_bf16_gpu.py.  At T = 1
-the true dQ and dK are exactly 0 and that module's relative L2 is undefined (the kernels' dS = P (dP - delta) is a difference of two
-differently ordered sums, a few ulp, not 0), so there dQ and dK are taken relative to attn_ref.abs_gradients, against the same GRAD_TOL.
+The bf16-operand kernels have their bars in tests/test_attn_bf16_gpu.py: check_against_rounded with OUT_TOL and GRAD_TOL, and
+assert_inside_bf16_bars (bars from attn_ref.yardstick_bf16, as here from the float32 yardstick), which holds them at every tile edge
+there; here the guard-band runs and the T = 1 case assert both.  At T = 1 the true dQ and dK are exactly 0 and a relative L2 against
+them is undefined (the kernels' dS = P (dP - delta) is a difference of two differently ordered sums, a few ulp, not 0), so for GRAD_TOL
+dQ and dK are there taken relative to attn_ref.abs_gradients, as the bars take them throughout.
 
 Measured on an MI355X: profiles/attn_fp32_accuracy.txt."""
 import functools
@@ -15,14 +17,15 @@ import pytest
 import torch
 
 from tests import attn_ref as R
-from tests.test_attn_bf16_gpu import GRAD_TOL, OUT_TOL, check_against_rounded, reference as reference64, rel_l2, rounded
+from tests.test_attn_bf16_gpu import (GRAD_TOL, OUT_TOL, assert_inside_bf16_bars, case_bf16, check_against_rounded,
+                                      reference as reference64, rel_l2, rounded)
 
 pytestmark = pytest.mark.gpu
 
 EXPLICIT = [(4, 2), (2, 2), (2, 4), (1, 2), (1, 4), (1, 8)]
 TILINGS = [(0, 0)] + EXPLICIT
 ENTRIES = {"fp32": ("ftx_attn_fwd_tiled", "ftx_attn_bwd_tiled"), "bf16": ("ftx_attn_fwd_bf16", "ftx_attn_bwd_bf16")}
-EDGES = [1, 31, 32, 33, 64, 127, 128, 129, 257, 578]     # below one 32-token tile, its edges, the 4-wave block's edges, the ViT's T
+EDGES = R.EDGES               # below one 32-token tile, its edges, the 4-wave block's edges, the ViT's T
 B, H = 2, 3
 GUARD = 256                   # floats on each side of a banded operand (keeps the 16-byte alignment of the rows)
 SENTINEL = 0x7FA5A5A5         # a NaN with a payload: an output element that was never written is not finite, a band that was is changed
@@ -106,10 +109,7 @@ def bf16_inside_bars(got, qkv, go, scale, label):
 
 
 # ---------------------------------------------------------------- accuracy (fp32)
-ACCURACY = ([(kind, T, 0.125) for kind in ("gauss", "peaked") for T in EDGES] +
-            [(kind, 129, 0.1) for kind in ("gauss", "peaked")] +                      # a scale that is not a power of two
-            # 290: the last token lies in key tile 9, i.e. in a key group other than 0 under every split (at 257 it is tile 8: group 0)
-            [(kind, T, 0.125) for kind in ("ascending", "late_max") for T in (70, 257, 290)])
+ACCURACY = R.ACCURACY        # shared with tests/test_attn_bf16_gpu.py
 
 
 @pytest.mark.parametrize("tiling", TILINGS)
@@ -145,7 +145,9 @@ def test_fp32_autograd_path_is_the_same_launch():
 def test_bf16_every_tile_edge(T, tiling):
     c = case("gauss", T)
     if T == 1:
-        bf16_inside_bars(launch("bf16", c.qkv, c.go, 0.125, tiling), c.qkv, c.go, 0.125, (T, tiling))
+        got = launch("bf16", c.qkv, c.go, 0.125, tiling)
+        bf16_inside_bars(got, c.qkv, c.go, 0.125, (T, tiling))
+        assert_inside_bf16_bars(case_bf16("gauss", T), got, f"edge gauss T={T} tiling={tiling}")
     else:
         check_against_rounded(c.qkv, c.go, 0.125, tiling)
 
@@ -209,6 +211,7 @@ def test_guard_bands(prec, T, tiling):
         assert_inside_bars(c, got, f"banded T={T} tiling={tiling}")
     else:
         bf16_inside_bars(got, c.qkv, c.go, 0.125, (T, tiling))
+        assert_inside_bf16_bars(case_bf16("gauss", T, 0.125, 1, H), got, f"banded T={T} tiling={tiling}")      # the same inputs as c
     assert bitwise_equal(got, launch(prec, c.qkv, c.go, 0.125, tiling))
 
 
