@@ -111,5 +111,6 @@ def image_cfg() -> CfgNode:
 
 def image_stn_cfg() -> CfgNode:
     """The spatial-transformer image-only baseline (the reference's configs/semantic_kitti/image.yaml): learned affine resampling to
-    the ViT and back (models/image_models_stn.py), one linear head."""
-    return _single_cfg(dict(TYPE="ImageSeg", USE_IMAGE=True, late_feat_block_number=11, image_stn=True))
+    the ViT and back (models/image_models_stn.py), one linear head.  MODEL.stn_loc_impl ("library" | "ftx") chooses what runs the
+    localisation nets' convolutions: torch's library (the default) or the fused kernels of csrc/ftx_stn_loc.hip."""
+    return _single_cfg(dict(TYPE="ImageSeg", USE_IMAGE=True, late_feat_block_number=11, image_stn=True, stn_loc_impl="library"))

@@ -1277,6 +1277,98 @@ def affine_lift(src, theta, img_idx, point_batch, H, W):
     return _AffineLift.apply(src, theta, img_idx, point_batch, H, W)
 
 
+# ---------------------------------------------------------------- the spatial transformers' localisation net
+LOC_LAYERS = ((7, 8), (5, 90))     # the (k, co) csrc/ftx_stn_loc.hip serves: Conv2d(C, 8, 7) and Conv2d(8, 90, 5)
+
+
+def _loc_operands(x, weight, bias, who):
+    """(b, c, ih, iw, k, co, ph, pw, host stride array) of a strided float32 input and its contiguous Conv2d parameters, checked before
+    anything is launched."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError(f"{who} x: expected a CUDA (HIP) tensor; the product path has no CPU fallback")
+    if x.dtype != F32 or x.dim() != 4:
+        raise ValueError(f"{who} x: expected a 4-d float32 tensor, got {x.dtype} {tuple(x.shape)}")
+    b, c, ih, iw = x.shape
+    if min(b, c, ih, iw) < 1 or b > 128:
+        raise ValueError(f"{who} x: empty tensor or more than 128 frames: {tuple(x.shape)}")
+    if any(st <= 0 and sz > 1 for st, sz in zip(x.stride(), x.shape)):
+        raise ValueError(f"{who} x: strides {x.stride()} alias elements")
+    req(weight, F32, who + " weight", 4)
+    co, cw, k, k2 = weight.shape
+    if cw != c or k != k2 or (k, co) not in LOC_LAYERS:
+        raise ValueError(f"{who} weight: expected (co, {c}, k, k) with (k, co) one of {LOC_LAYERS}, got {tuple(weight.shape)}")
+    if bias is not None:
+        req(bias, F32, who + " bias", 1)
+        if bias.shape[0] != co:
+            raise ValueError(f"{who} bias: expected ({co},), got {tuple(bias.shape)}")
+    if weight.device != x.device or (bias is not None and bias.device != x.device):
+        raise ValueError(f"{who}: x and the parameters live on different devices")
+    ph, pw = (ih - k + 1) // 2, (iw - k + 1) // 2
+    if ph < 1 or pw < 1:
+        raise ValueError(f"{who}: a {ih} x {iw} input has no pooled pixel under a {k} x {k} kernel")
+    return b, c, ih, iw, k, co, ph, pw, (ctypes.c_int64 * 4)(*x.stride())
+
+
+class _LocConvPoolRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, mean):
+        L = _lib.load()
+        b, c, ih, iw, k, co, ph, pw, strides = _loc_operands(x, weight, bias, "loc_conv_pool_relu")
+        sel = _empty((b, co, ph, pw), torch.int8, x)
+        if mean:
+            out = _empty((b, co), F32, x)
+            ws_bytes = _ws_bytes("ftx_loc_conv_pool_relu_fwd_workspace_bytes", b, co, ph, pw)
+            ws = _scratch(ws_bytes, x)
+            check(L.ftx_loc_conv_pool_relu_fwd(ptr(x), strides, b, c, ih, iw, ptr(weight), ptr(bias), k, co, 0, ptr(sel), ptr(out), ptr(ws),
+                                               ws_bytes, stream()), "ftx_loc_conv_pool_relu_fwd")
+        else:
+            out = _empty((b, co, ph, pw), F32, x)
+            check(L.ftx_loc_conv_pool_relu_fwd(ptr(x), strides, b, c, ih, iw, ptr(weight), ptr(bias), k, co, ptr(out), ptr(sel), 0, 0, 0,
+                                               stream()), "ftx_loc_conv_pool_relu_fwd")
+        # x, the pooled output (the mean form: the (b, co) row) and the routing bytes; the un-pooled map never existed
+        ctx.save_for_backward(x, weight, bias, out, sel)
+        ctx.mean = bool(mean)
+        ctx.mark_non_differentiable(sel)
+        return out, sel
+
+    @staticmethod
+    def backward(ctx, go, _gsel):
+        L = _lib.load()
+        x, weight, bias, out, sel = ctx.saved_tensors
+        b, c, ih, iw, k, co, ph, pw, strides = _loc_operands(x, weight, bias, "loc_conv_pool_relu")
+        if go.shape != out.shape:
+            raise ValueError("loc_conv_pool_relu: gradient shape differs from the output's")
+        if ctx.mean:   # d mean / d pooled = 1 / (ph pw) everywhere: a (b, co) row read with zero strides, no (b, co, ph, pw) tensor
+            go = req((go * (1.0 / (ph * pw))).contiguous(), F32, "loc_conv_pool_relu grad", 2)
+            gstrides = (ctypes.c_int64 * 4)(co, 1, 0, 0)
+        else:
+            go = req(go.contiguous(), F32, "loc_conv_pool_relu grad", 4)
+            gstrides = (ctypes.c_int64 * 4)(*go.stride())
+        gx = gw = gb = None
+        if ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2]):
+            gw, gb = torch.empty_like(weight), _empty((co,), F32, weight)
+            ws_bytes = _ws_bytes("ftx_loc_conv_pool_relu_bwd_weight_workspace_bytes", b, c, ih, iw, k, co)
+            ws = _scratch(ws_bytes, x)
+            check(L.ftx_loc_conv_pool_relu_bwd_weight(ptr(x), strides, b, c, ih, iw, ptr(sel), ptr(go), gstrides, k, co, ptr(gw), ptr(gb),
+                                                      ptr(ws), ws_bytes, stream()), "ftx_loc_conv_pool_relu_bwd_weight")
+            if bias is None:
+                gb = None
+        if ctx.needs_input_grad[0]:   # skipped for stn_down: its x is the image
+            gx = torch.empty_strided(x.shape, x.stride(), dtype=F32, device=x.device)
+            check(L.ftx_loc_conv_pool_relu_bwd_data(ptr(weight), ptr(sel), ptr(go), gstrides, b, c, ih, iw, k, co, ptr(gx), strides, stream()),
+                  "ftx_loc_conv_pool_relu_bwd_data")
+        return gx, gw, gb, None
+
+
+def loc_conv_pool_relu(x, weight, bias=None, mean=False, return_sel=False):
+    """relu(max_pool2d(conv2d(x, weight, bias), 2, 2)) of a stride-1, unpadded Conv2d(C, 8, 7) or Conv2d(8, 90, 5) on csrc/ftx_stn_loc.hip:
+    x (b, c, ih, iw) float32 of any non-aliasing strides, NCHW result (b, co, ph, pw); mean=True returns its spatial mean (b, co)
+    instead, without the map.  Differentiable in x (same strides as x), weight and bias; exact float32, no float atomics, every output
+    repeats bit for bit.  return_sel adds the int8 routing map (position 0..3 of each window's maximum, -1 where the ReLU is dead)."""
+    out, sel = _LocConvPoolRelu.apply(x, weight, bias, bool(mean))
+    return (out, sel) if return_sel else out
+
+
 # ---------------------------------------------------------------- LayerNorm (+ the residual add in front of it)
 def layer_norm_supported(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == F32 and x.shape[-1] % 256 == 0 and 256 <= x.shape[-1] <= 1024

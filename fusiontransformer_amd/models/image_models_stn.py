@@ -75,10 +75,20 @@ class Net2DSeg(nn.Module):
         self.up[self.late_feat_block_number] = ScaleUpModule(input_features=self.hidden_channels, output_features=self.feat_channels,
                                                              kernel_size=16, stride=16)
 
+        self.set_loc_impl(kw.get("stn_loc_impl", None) or "library")
+
         self.linear = nn.Linear(self.feat_channels, num_classes)
         self.dual_head = dual_head
         if dual_head:
             self.linear2 = nn.Linear(self.feat_channels, num_classes)
+
+    def set_loc_impl(self, impl: str):
+        """"library" | "ftx" for the localisation nets of `stn_down` and of every `up[*].up_stn` (SpatialTransformer.set_loc_impl)."""
+        self.stn_down.set_loc_impl(impl)
+        for m in self.up.values():
+            m.up_stn.set_loc_impl(impl)
+        self.stn_loc_impl = impl
+        return self
 
     def get_img_feats(self, img_indices, block_id: str, image_shape: tuple, backbone_output: Dict):
         """reference image_models_stn.py:63-100 -> (sum N, feat_channels): the rows the reference picks out of the map that

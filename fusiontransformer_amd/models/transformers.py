@@ -596,7 +596,7 @@ class SpatialTransformer(nn.Module):
     """reference models/transformers.py:102-135, same attribute names / state_dict keys and the same identity initialisation.
 
     The localisation net (Conv 7x7 -> MaxPool -> ReLU -> Conv 5x5 -> MaxPool -> ReLU -> global average -> two Linears) runs on torch's
-    own ops; the resampling F.grid_sample(x, F.affine_grid(theta, ...)) runs on libftx without the grid: `forward` is the dense form
+    own ops by default, its convolutional part on own fused kernels after set_loc_impl("ftx"); the resampling F.grid_sample(x, F.affine_grid(theta, ...)) runs on libftx without the grid: `forward` is the dense form
     (every pixel of the target; differentiable in theta only), `lift` the point form (only the pixels the points pick; differentiable
     in x and theta)."""
 
@@ -617,8 +617,25 @@ class SpatialTransformer(nn.Module):
         self.fc_loc[2].weight.data.zero_()
         self.fc_loc[2].bias.data.copy_(torch.tensor([1, 0, 0, 0, 1, 0], dtype=torch.float))
 
+    LOC_IMPLS = ("library", "ftx")
+
+    def set_loc_impl(self, impl: str):
+        """"library": the localisation net's convolutions and pools are torch's.  "ftx": on CUDA tensors its convolutional part runs as
+        two fused conv + pool + ReLU layers of csrc/ftx_stn_loc.hip (functional.loc_conv_pool_relu), the second one straight to the
+        spatial mean.  The parameters stay in the nn.Conv2d modules either way; `fc_loc` is untouched."""
+        if impl not in self.LOC_IMPLS:
+            raise ValueError(f"stn_loc_impl must be one of {self.LOC_IMPLS}, got {impl!r}")
+        self.loc_impl = impl
+        return self
+
     def theta(self, x):
         """The (B, 2, 3) affine matrices the localisation net reads off x."""
+        if getattr(self, "loc_impl", "library") == "ftx" and x.is_cuda:
+            from .. import functional as spf
+            c1, c2 = self.localization[0], self.localization[3]
+            xs = spf.loc_conv_pool_relu(x, c1.weight, c1.bias)
+            xs = spf.loc_conv_pool_relu(xs, c2.weight, c2.bias, mean=True)
+            return self.fc_loc(xs).view(-1, 2, 3)
         # localization[6] is AdaptiveAvgPool2d(1): the plain mean is the same number, and its backward is a broadcast, not the
         # adaptive pool's scatter
         xs = self.localization[:6](x).mean((2, 3))

@@ -216,6 +216,26 @@ int ftx_affine_lift_cells(const float *theta, const int64_t *img_idx, const int3
  * that can touch it, in a fixed order.  grad_theta (NULL: skipped): (b, 2, 3), needs the workspace.  No float atomics. */
 int ftx_affine_lift_bwd(const float *src, const int64_t *src_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const float *theta, const int64_t *img_idx, const int32_t *point_batch, const float *grad_out, int64_t n, int32_t H, int32_t W, const int32_t *order, const int32_t *seg_off, float *grad_src, float *grad_theta, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the spatial transformers' localisation net (models/transformers.py:106-114) ---------
+ * One fused layer  y = relu(max_pool2d(conv2d(x, w, bias), 2, 2))  of a stride-1, unpadded k x k convolution; served (k, co) = (7, 8)
+ * and (5, 90), any c >= 1.  x (b, c, ih, iw) float32 by x_strides = four element strides (frame, channel, row, column) in HOST
+ * memory, all >= 0 (NCHW and channels-last are the same code); w (co, c, k, k) and bias (co, NULL: none) contiguous.  Pooled size
+ * ph = (ih - k + 1) / 2, pw likewise; a size with ph or pw = 0 is refused (FTX_EINVAL).  b <= 128.  The un-pooled map never exists.
+ * Exact float32 products, fixed orders of summation, no float atomics: every output repeats bit for bit.
+ *
+ * fwd: sel (b, co, ph, pw) int8 = position 0..3 (row-major, the first on a tie) of the window's maximum, -1 where the maximum is <= 0
+ * or NaN (dead ReLU, no gradient).  Exactly one of out (b, co, ph, pw) and mean (b, co) is non-NULL: mean receives the spatial mean of
+ * the pooled map instead of the map and needs the workspace (per-tile float64 sums, added in tile order). */
+size_t ftx_loc_conv_pool_relu_fwd_workspace_bytes(int32_t b, int32_t co, int32_t ph, int32_t pw);
+int ftx_loc_conv_pool_relu_fwd(const float *x, const int64_t *x_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const float *w, const float *bias, int32_t k, int32_t co, float *out, int8_t *sel, float *mean, void *workspace, size_t workspace_bytes, void *stream);
+/* grad_w (co, c, k, k) and grad_bias (co) from x, sel and the pooled gradient, which is addressed by grad_strides = four element
+ * strides (frame, channel, row, column) in HOST memory, 0 allowed: the mean's backward is g[b, co] / (ph pw) with strides (co, 1, 0, 0).
+ * Only the routed position of a window contributes.  Per-block float64 partials in the workspace, added in block order. */
+size_t ftx_loc_conv_pool_relu_bwd_weight_workspace_bytes(int32_t b, int32_t c, int32_t ih, int32_t iw, int32_t k, int32_t co);
+int ftx_loc_conv_pool_relu_bwd_weight(const float *x, const int64_t *x_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, const int8_t *sel, const float *grad, const int64_t *grad_strides, int32_t k, int32_t co, float *grad_w, float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
+/* grad_x (b, c, ih, iw) by grad_x_strides (as x_strides), every element written exactly once (a gather over the routed gradients). */
+int ftx_loc_conv_pool_relu_bwd_data(const float *w, const int8_t *sel, const float *grad, const int64_t *grad_strides, int32_t b, int32_t c, int32_t ih, int32_t iw, int32_t k, int32_t co, float *grad_x, const int64_t *grad_x_strides, void *stream);
+
 /* ---- sparse convolution (spnn.Conv3d fwd/bwd) ----------------------------
  * Pair-list gather-GEMM + ordered reduce (exact-fp32 MFMA, no float atomics, bit-reproducible):
  *   forward       tmp = pairs_gemm(A=in,   gather=pair_in,  W, 0);  out = reduce(tmp, pos,   n_out)

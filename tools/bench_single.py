@@ -42,11 +42,13 @@ def _inputs(batch, cycle, device):
     }
 
 
-def step_time(kind, batch, steps, warmup):
+def step_time(kind, batch, steps, warmup, stn_loc=None):
     from fusiontransformer_amd import config
     from fusiontransformer_amd.models.build import build_model
     from fusiontransformer_amd.trainer import TrainStep
     cfg = {"LidarSeg": config.lidar_cfg, "ImageSegBilinear": config.image_cfg, "ImageSeg": config.image_stn_cfg}[kind]()
+    if stn_loc is not None:
+        cfg.MODEL.stn_loc_impl = stn_loc
     torch.manual_seed(0)
     model, metric = build_model(cfg)
     model = model.cuda().train()
@@ -66,8 +68,11 @@ def step_time(kind, batch, steps, warmup):
     ms = e0.elapsed_time(e1) / steps
     loss = next(iter(step.last.values())).item()
     assert loss == loss, "the loss is NaN"
-    return {"model": kind, "batch": batch, "points_per_batch": list(points), "steps": steps, "warmup": warmup, "ms_per_step": ms,
-            "frames_per_s": batch * 1e3 / ms, "last_loss": loss}
+    r = {"model": kind, "batch": batch, "points_per_batch": list(points), "steps": steps, "warmup": warmup, "ms_per_step": ms,
+         "frames_per_s": batch * 1e3 / ms, "last_loss": loss}
+    if stn_loc is not None:
+        r["stn_loc_impl"] = stn_loc
+    return r
 
 
 def _graph_nodes(t):
@@ -273,6 +278,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "single_modality_steps.json"))
     ap.add_argument("--image-stn", action="store_true", help="only: step time of ImageSeg (spatial transformers) beside ImageSegBilinear, batch 4 and 1")
+    ap.add_argument("--stn-loc", default="library", choices=["library", "ftx", "both"],
+                    help="with --image-stn: what runs ImageSeg's localisation nets (cfg.MODEL.stn_loc_impl); both = one after the other")
     ap.add_argument("--native-index-ab", action="store_true", help="only: LidarSeg step time with SPVCNN.set_native_index off / on, batch 1 and 4")
     ap.add_argument("--native-train-ab", action="store_true", help="only: step time with SPVCNN.set_native_train off / on, batch 1 and 4")
     ap.add_argument("--ab-model", default="LidarSeg", choices=["LidarSeg", "middle"], help="the model of --native-train-ab")
@@ -295,12 +302,14 @@ def main():
         raise SystemExit("bench_single: at least 50 timed steps")
     if args.image_stn:
         result = {"what": "image-only train steps on synthetic KITTI-shaped frames (two alternating resident batches, HIP events, profiler "
-                          "off): ImageSeg (learned affine resampling, eager trunk, torch convolutions in the localisation nets) beside "
-                          "ImageSegBilinear (fixed nearest resampling, trunk as HIP graphs)",
+                          "off): ImageSeg (learned affine resampling, eager trunk; stn_loc_impl says what runs the localisation nets' "
+                          "convolutions: torch's library, or the fused kernels of csrc/ftx_stn_loc.hip) beside ImageSegBilinear (fixed "
+                          "nearest resampling, trunk as HIP graphs); one run each, no spread claimed",
                   "device": torch.cuda.get_device_name(0), "steps": []}
-        for kind in ("ImageSegBilinear", "ImageSeg"):
+        runs = [("ImageSegBilinear", None)] + [("ImageSeg", impl) for impl in (("library", "ftx") if args.stn_loc == "both" else (args.stn_loc,))]
+        for kind, impl in runs:
             for batch in (4, 1):
-                r = step_time(kind, batch, args.steps, args.warmup)
+                r = step_time(kind, batch, args.steps, args.warmup, stn_loc=impl)
                 print(json.dumps(r), flush=True)
                 result["steps"].append(r)
         out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "image_stn_steps.json")
