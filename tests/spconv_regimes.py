@@ -99,15 +99,19 @@ def wgrad_tile_len(lib, n_pairs, ca, cg, kvol):
     return max(length, 256)
 
 
+def wgrad_reduce_lanes(tiles, kvol):
+    """csrc/ftx_spconv_common.h launch_wgrad_reduce(): lanes TL of the ordered reduce over `tiles` partial tiles (either precision)."""
+    big = 6 * tiles // kvol if kvol > 1 else tiles
+    return 1 if big <= 4 else 4 if big <= 32 else 16
+
+
 def wgrad_regime(lib, n_pairs, ca, cg, kvol):
     """(instantiation, tile length, reduce lanes TL) of one ftx_spconv_pairs_wgrad call.  The tile count comes from the library's
     workspace query (bytes / (4 ca cg) = ceil(P / tile_len) + kvol), so the restated tile length is checked against the library."""
     length = wgrad_tile_len(lib, n_pairs, ca, cg, kvol)
     tiles = int(lib.ftx_spconv_pairs_wgrad_workspace_bytes(n_pairs, ca, cg, kvol)) // (4 * ca * cg)
     assert tiles == cdiv(n_pairs, length) + kvol, (n_pairs, ca, cg, kvol, tiles, length)
-    big = 6 * tiles // kvol if kvol > 1 else tiles
-    tl = 1 if big <= 4 else 4 if big <= 32 else 16
-    return wgrad_config(ca, cg), length, tl
+    return wgrad_config(ca, cg), length, wgrad_reduce_lanes(tiles, kvol)
 
 
 # Offset sizes of the tile-edge pair lists, per kvol: "L" stands for the weight-gradient tile length, "L-1" / "L+1" next to it,
@@ -121,9 +125,10 @@ EDGE_SIZES = {
 }
 
 
-def edge_sizes(lib, ca, cg, kvol):
+def edge_sizes(lib, ca, cg, kvol, tile_len=None):
     """EDGE_SIZES[kvol] with L resolved.  The tile length depends on the total pair count, so it is iterated to a fixed point.
-    Returns (sizes, tile_len)."""
+    tile_len: the precision's tile-length function (default: wgrad_tile_len, the fp32 kernels').  Returns (sizes, tile_len)."""
+    tile_len = tile_len or wgrad_tile_len
     def resolve(v, length):
         if isinstance(v, int):
             return v
@@ -135,7 +140,7 @@ def edge_sizes(lib, ca, cg, kvol):
     length = 256
     for _ in range(20):
         sizes = [resolve(v, length) for v in EDGE_SIZES[kvol]]
-        new = wgrad_tile_len(lib, sum(sizes), ca, cg, kvol)
+        new = tile_len(lib, sum(sizes), ca, cg, kvol)
         if new == length:
             return sizes, length
         length = new
