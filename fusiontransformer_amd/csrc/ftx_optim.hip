@@ -30,31 +30,37 @@ __global__ __launch_bounds__(256) void adam_kernel(const FtxAdamTensor *__restri
   const int64_t off = chunk_offset[blockIdx.x];
   const int64_t end = off + ADAM_CHUNK < t.n ? off + ADAM_CHUNK : t.n;
   // omb1 = 1 - beta1, omb2 = 1 - beta2 come from the host, formed in double like torch does (1.f - 0.999f is off by 1.3e-5 relative)
-  auto update = [&](float &p, float g, float &m, float &v) {
-    g = g + weight_decay * p;                       // L2 form: grad.add(param, alpha=weight_decay)
-    m = m + omb1 * (g - m);                         // exp_avg.lerp_(grad, 1 - beta1)
-    v = beta2 * v + omb2 * g * g;                   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    const float denom = sqrtf(v) * t.inv_bc2_sqrt + eps;
-    p = p - t.step_size * (m / denom);
+  // Every rounding is spelled out.  Left to the compiler's contraction, the float4 body fused beta2 * v + (omb2 * g) * g and the scalar
+  // loops did not, so the last bit of v depended on the pointers' alignment.  Which form an element gets is now a function of its place
+  // alone: FUSED for the whole groups of four counted from the chunk's offset, unfused for the 1..3 elements behind them -- what the
+  // float4 body and its scalar tail have always computed on 16-byte aligned tensors (a training run keeps its bits), and now also what a
+  // tensor at any other alignment gets.  The other four operations were contracted alike on both paths and are written as they were.
+  auto update = [&](float &p, float g, float &m, float &v, bool fused) {
+    g = __fmaf_rn(weight_decay, p, g);                                   // L2 form: grad.add(param, alpha=weight_decay)
+    m = __fmaf_rn(omb1, __fsub_rn(g, m), m);                             // exp_avg.lerp_(grad, 1 - beta1)
+    const float gg = __fmul_rn(__fmul_rn(omb2, g), g);                   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    v = fused ? __fmaf_rn(beta2, v, gg) : __fadd_rn(__fmul_rn(beta2, v), gg);
+    const float denom = __fmaf_rn(sqrtf(v), t.inv_bc2_sqrt, eps);
+    p = __fmaf_rn(-t.step_size, m / denom, p);
   };
   const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.m | (uintptr_t)t.v | (uintptr_t)t.g) & 15) == 0) && ((off & 3) == 0);
+  const int64_t end4 = off + ((end - off) & ~(int64_t)3);
   if (vec) {
-    const int64_t end4 = off + ((end - off) & ~(int64_t)3);
     for (int64_t i = off + (int64_t)threadIdx.x * 4; i < end4; i += 256 * 4) {
       float4 p = *(const float4 *)&t.p[i], m = *(const float4 *)&t.m[i], v = *(const float4 *)&t.v[i];
       const float4 g = *(const float4 *)&t.g[i];
-      update(p.x, g.x, m.x, v.x);
-      update(p.y, g.y, m.y, v.y);
-      update(p.z, g.z, m.z, v.z);
-      update(p.w, g.w, m.w, v.w);
+      update(p.x, g.x, m.x, v.x, true);
+      update(p.y, g.y, m.y, v.y, true);
+      update(p.z, g.z, m.z, v.z, true);
+      update(p.w, g.w, m.w, v.w, true);
       *(float4 *)&t.p[i] = p;
       *(float4 *)&t.m[i] = m;
       *(float4 *)&t.v[i] = v;
     }
-    for (int64_t i = end4 + threadIdx.x; i < end; i += 256) update(t.p[i], t.g[i], t.m[i], t.v[i]);
   } else {
-    for (int64_t i = off + threadIdx.x; i < end; i += 256) update(t.p[i], t.g[i], t.m[i], t.v[i]);
+    for (int64_t i = off + threadIdx.x; i < end4; i += 256) update(t.p[i], t.g[i], t.m[i], t.v[i], true);
   }
+  for (int64_t i = end4 + threadIdx.x; i < end; i += 256) update(t.p[i], t.g[i], t.m[i], t.v[i], false);
 }
 
 extern "C" int32_t ftx_adam_chunk_elements(void) { return ADAM_CHUNK; }

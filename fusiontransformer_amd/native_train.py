@@ -166,8 +166,10 @@ class NativeTrain(ne._Host):
     def trainable(self):
         return all(p.requires_grad for p in self.tp.parameters())
 
-    def begin(self, z, x0):
-        """Fill the tables of one batch and allocate its arena; raises Refused (nothing launched) for a batch the library does not take."""
+    def begin(self, z, x0, arena=None):
+        """Fill the tables of one batch and allocate its arena; raises Refused (nothing launched) for a batch the library does not take.
+        arena (optional): nbytes -> a contiguous uint8 CUDA tensor of that many bytes, 256-byte aligned, to run in instead of a fresh
+        torch.empty -- a view into a larger buffer is fine (the tests' guard bands)."""
         tp = self.tp
         try:
             layers = self.model_table()
@@ -188,7 +190,12 @@ class NativeTrain(ne._Host):
         tl = np.zeros(len(layers), dtype=TRAIN_LAYER)
         tl["momentum"] = tp.momentum
         feats = _lib.req(x0.F.contiguous(), torch.float32, "native train input features", 2)
-        arena = torch.empty((need,), dtype=torch.uint8, device=feats.device)
+        if arena is None:
+            arena = torch.empty((need,), dtype=torch.uint8, device=feats.device)
+        else:
+            arena = _lib.req(arena(need), torch.uint8, "native train arena", 1)
+            if arena.shape[0] != need or arena.data_ptr() % 256 or arena.device != feats.device:
+                raise ValueError(f"native train: the arena must be {need} bytes on {feats.device}, 256-byte aligned")
         self.runs += 1
         self.last_arena_bytes = need
         return _Run(self, layers, tl, rows, maps, pvs, tpvs, routes, groutes, (kms, z, x0, segs), feats, arena)
@@ -202,6 +209,7 @@ class _Run:
         self.routes, self.groutes, self.keep, self.feats, self.arena = routes, groutes, keep, feats, arena
         self.storage = arena.untyped_storage()
         self.base = arena.data_ptr()
+        self.origin = self.base - arena.storage_offset()      # the storage's first byte (uint8: elements are bytes); = base for a fresh arena
         self.forward_done = -1
         self.backward_next = None     # the segment whose backward comes next; None until the forward is complete, -1 when consumed
 
@@ -241,7 +249,7 @@ class _Run:
         if last:
             self.backward_next = seg
             return x, out
-        return x, _alias(self.storage, int(where.value) - self.base, (int(self.rows[level]), ch), x.device)
+        return x, _alias(self.storage, int(where.value) - self.origin, (int(self.rows[level]), ch), x.device)
 
     def _backward(self, seg, x, grad_out):
         tp = self.ex.tp
@@ -266,7 +274,7 @@ class _Run:
         grads = [g.view(e[3]) if len(e[3]) > 1 else g for g, e in zip(torch.split(flat, sp["sizes"]), sp["entries"])]
         gin = None
         if seg > 0:
-            gin = _alias(self.storage, int(where.value) - self.base, tuple(x.shape), x.device)
+            gin = _alias(self.storage, int(where.value) - self.origin, tuple(x.shape), x.device)
         return gin, grads
 
 

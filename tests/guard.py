@@ -19,6 +19,16 @@ tile height, so a whole stray tile still lands inside the band, i.e. inside the 
 view stays 256-byte aligned.  `dense_band` is the exception for the dense GEMM entries, whose header contract is "every pointer
 16-byte aligned": widths = 4 (mod 8) floats put every tensor at the weakest alignment the header permits.
 
+Bytes and a second poison (the image kernels, the index entries and the executors' arenas):
+
+  * a uint8 IMAGE (`banded_u8`) is an (h, w, 3) view with row pitch >= 3 w, starting 0..3 bytes past a 256-byte boundary, inside a larger
+    allocation whose row slack and bands hold one fill byte.  `bands_intact_u8` finds a store into the slack or a band; an OUTPUT has no
+    byte value that means "unwritten", so `written_u8` runs the kernel on two fills and wants the payload equal both times; a SOURCE is
+    built twice, slack and bands 0x00 and then 0xFF, and the result must not change (a read beside a crop view);
+  * an ARENA or a workspace that holds indices (`banded_bytes(nbytes, fill=0xFF | 0x00)`) keeps the sentinel in its bands and holds the
+    fill byte in its payload: 0xFF.. is a NaN as float32 and float64 and -1, the library's own "absent", as int32 and int64; 0x00 is the
+    second run.  The 0x7FA5A5A5 word would be a huge row index there and is never used for these.  `same_across_fills` is the check.
+
 Integer OPERANDS (gather / scatter indices, koff, pos, nbr, idx, order, seg_off) are NOT banded: a band value read as an index would
 address memory, and nothing here may cause a stray access.  Over-reads of index arrays are therefore out of scope of this helper."""
 import numpy as np
@@ -29,7 +39,8 @@ SENTINEL64 = (SENTINEL << 32) | SENTINEL
 ALIGN = 256
 WORKSPACE_BAND_BYTES = 1 << 18      # more than one 192 x 192 float32 weight-gradient tile
 
-_WORDS = {torch.float32: torch.int32, torch.int32: torch.int32, torch.float64: torch.int64, torch.int64: torch.int64}
+_WORDS = {torch.float32: torch.int32, torch.int32: torch.int32, torch.float64: torch.int64, torch.int64: torch.int64,
+          torch.uint8: torch.uint8, torch.int8: torch.int8}
 
 
 def _default_device():
@@ -73,14 +84,17 @@ def banded(shape, data=None, dtype=torch.float32, band=None, inout=False, device
     return whole, view
 
 
-def banded_bytes(nbytes, band_bytes=WORKSPACE_BAND_BYTES, device=None):
+def banded_bytes(nbytes, band_bytes=WORKSPACE_BAND_BYTES, device=None, fill=None):
     """A workspace of exactly nbytes bytes (a multiple of 4): (whole, payload), both int32 words, sentinel everywhere; the payload
-    starts 256-byte aligned."""
+    starts 256-byte aligned.  fill = 0xFF or 0x00: the payload holds that byte instead (an arena, or a workspace that holds indices);
+    the bands keep the sentinel."""
     device = device or _default_device()
     nbytes = int(nbytes)
-    assert nbytes % 4 == 0 and band_bytes % ALIGN == 0
+    assert nbytes % 4 == 0 and band_bytes % ALIGN == 0 and fill in (None, 0x00, 0xFF)
     whole = torch.full(((nbytes + 2 * band_bytes) // 4,), SENTINEL, dtype=torch.int32, device=device)
     payload = whole[band_bytes // 4:(band_bytes + nbytes) // 4]
+    if fill is not None:
+        payload.fill_(-1 if fill == 0xFF else 0)
     assert not whole.is_cuda or whole.data_ptr() % ALIGN == 0      # torch's device allocator aligns every block to 512 bytes
     return whole, payload
 
@@ -118,3 +132,53 @@ def written(view):
 
 def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and bool((_words(a.contiguous()) == _words(b.contiguous())).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------- uint8 images
+U8_BAND_BYTES = 1 << 12
+FILLS = (0x00, 0xFF)
+
+
+def banded_u8(shape, data=None, pitch=None, offset=0, fill=0xA5, device=None):
+    """An (h, w, 3) uint8 view with row pitch `pitch` >= 3 w bytes whose first byte lies `offset` (0..3) bytes past a 256-byte boundary,
+    inside a larger allocation: (whole, view).  Row slack (the pitch - 3 w bytes behind every row, the last included) and both bands
+    hold `fill`; the payload holds data, or `fill` too when data is None (an output)."""
+    device = device or _default_device()
+    h, w, ch = (int(s) for s in shape)
+    pitch = 3 * w if pitch is None else int(pitch)
+    assert ch == 3 and h >= 1 and w >= 1 and pitch >= 3 * w and 0 <= offset <= 3 and 0 <= fill <= 255
+    whole = torch.full((2 * U8_BAND_BYTES + h * pitch,), fill, dtype=torch.uint8, device=device)
+    assert not whole.is_cuda or whole.data_ptr() % ALIGN == 0
+    view = torch.as_strided(whole, (h, w, 3), (pitch, 3, 1), U8_BAND_BYTES + offset)
+    if data is not None:
+        view.copy_(data.to(device=device, dtype=torch.uint8))
+    return whole, view
+
+
+def _payload_mask_u8(whole, view):
+    h, w, _ = view.shape
+    mask = torch.zeros(whole.numel(), dtype=torch.bool, device=whole.device)
+    torch.as_strided(mask, (h, 3 * w), (view.stride(0), 1), view.storage_offset() - whole.storage_offset()).fill_(True)
+    return mask
+
+
+def bands_intact_u8(whole, view, fill=0xA5):
+    """Every byte of `whole` outside the (h, 3 w) payload of `view` -- both bands and the slack behind every row -- still holds fill."""
+    return bool((whole[~_payload_mask_u8(whole, view)] == fill).all())
+
+
+def written_u8(run, fills=(0x5A, 0xC3)):
+    """A byte has no value that means "not written": run(fill) -> (whole, view) builds a banded_u8 output holding `fill` everywhere, runs
+    the kernel into it and returns it.  Every payload byte was written iff the payload is the same for two fills (fills that differ in
+    every bit, so a byte only part of which was merged in shows too), and nothing else was written iff slack and bands hold the fill."""
+    a, b = (run(f) for f in fills)
+    intact = bands_intact_u8(a[0], a[1], fills[0]) and bands_intact_u8(b[0], b[1], fills[1])
+    return intact and bool((a[1] == b[1]).all())
+
+
+def same_across_fills(run, fills=FILLS):
+    """run(fill) -> a tensor or a tuple of tensors computed with a source's slack and bands, a workspace or an arena holding `fill`:
+    the results are bit-identical for the two fills (nothing outside the view, and nothing the kernel did not write, reaches them)."""
+    a, b = (run(f) for f in fills)
+    a, b = (a if isinstance(a, (tuple, list)) else (a,)), (b if isinstance(b, (tuple, list)) else (b,))
+    return len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))

@@ -47,10 +47,9 @@ Per entry (include/ftx.h), which of (a) (b) (c) is asserted:
     ftx_segment_build                       a b c   order (n), seg_off (m + 1) int32; also equal to a stable sort on the host
     ftx_voxelize_fwd_sorted, ftx_devoxelize_bwd_sorted, ftx_segment_sum    a b c
     ftx_lift_gather_fwd, ftx_lift_cells, ftx_resample_nearest_fwd          a b c
-  left out: ftx_sample_down_fwd / _bwd (the image branch's fused BatchNorm2d, listed under the lift in the header), the kernel-map,
-  hashing and index entries, ftx_trilinear_weights, the losses, eval, resize / jitter, Adam, ftx_rows_concat / _split / _add, the
-  ViT patch-embed / tap-stem entries and the three executors: a follow-up can reuse tests/guard.py.  Attention, the affine sampling
-  and the localisation net have guard tests of their own."""
+  every other entry that launches a kernel (sample_down, the kernel-map, hashing and index entries, the losses, the evaluation, resize /
+  jitter, Adam, the rows entries, the ViT patch-embed / tap-stem entries, the executors and the native index builder):
+  tests/test_guard_bands_rest_gpu.py.  Attention, the affine sampling and the localisation net have guard tests of their own."""
 import ctypes
 
 import pytest

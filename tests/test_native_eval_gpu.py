@@ -303,10 +303,10 @@ def test_tiny_cloud_with_one_voxel_on_the_deepest_levels():
     _same_outputs(on, off, "tiny cloud")
 
 
-def test_executor_runs_an_empty_map(env):
-    """The C entry point on a two-op program of its own: a 3x3x3 Conv3d -> BatchNorm over a map with n_pairs == 0 (the empty route), then
-    the devoxelize onto the points -- against the per-op Python path."""
-    spf, L = env
+def empty_map_program(spf):
+    """A two-op program of its own for the C entry point: a 3x3x3 Conv3d -> BatchNorm over a map with n_pairs == 0 (the empty route), then
+    the devoxelize onto the points.  Returns (args of ftx_spvcnn_eval up to the arena, arena bytes, output shape, the per-op Python path's
+    result, the tensors the tables point at)."""
     from fusiontransformer_amd import native_eval as ne
     g = gen(21)
     n, npts, ca, co, kvol = 24, 60, 32, 32, 27
@@ -332,15 +332,23 @@ def test_executor_runs_an_empty_map(env):
     pvs[0]["devox_idx"], pvs[0]["devox_weights"], pvs[0]["n_vox"], pvs[0]["level"] = idx.data_ptr(), wts.data_ptr(), n, 0
     routes = np.array([ne.ROUTES[spf._EMPTY], 0], dtype=np.int32)
     need = ne.arena_bytes(layers, ops, rows, maps, pvs, routes)
-    arena = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.empty((npts, co), dtype=torch.float32, device="cuda")
     p = ne._ptr
     args = (p(layers), 1, p(ops), 2, p(rows), p(maps), 1, p(pvs), 1, p(routes), feats.data_ptr(), 0, 0, None, None)
-    assert L.ftx_spvcnn_eval(*args, arena.data_ptr(), need - 256, out.data_ptr(), spf.stream()) == -3
-    spf.check(L.ftx_spvcnn_eval(*args, arena.data_ptr(), need, out.data_ptr(), spf.stream()), "ftx_spvcnn_eval")
     with torch.no_grad():
         y = spf.batch_norm(torch.zeros((n, co), device="cuda"), gam, bet, rm, rv, False, 0.1, EPS, relu=True)
         ref = spf.spdevoxelize(y, idx, wts)
+    keep = (neg, koff, w, gam, bet, rm, rv, feats, idx, wts, layers, ops, rows, maps, pvs, routes)
+    return args, need, (npts, co), ref, keep
+
+
+def test_executor_runs_an_empty_map(env):
+    """The C entry point on a two-op program of its own (empty_map_program) -- against the per-op Python path."""
+    spf, L = env
+    args, need, shape, ref, keep = empty_map_program(spf)
+    arena = torch.empty(need, dtype=torch.uint8, device="cuda")
+    out = torch.empty(shape, dtype=torch.float32, device="cuda")
+    assert L.ftx_spvcnn_eval(*args, arena.data_ptr(), need - 256, out.data_ptr(), spf.stream()) == -3
+    spf.check(L.ftx_spvcnn_eval(*args, arena.data_ptr(), need, out.data_ptr(), spf.stream()), "ftx_spvcnn_eval")
     assert same(out, ref)
 
 

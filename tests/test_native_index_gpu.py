@@ -308,46 +308,65 @@ def test_train_steps_with_prefetch_equal_the_twin_with_the_switch_off(kind, coun
 
 
 # ---------------------------------------------------------------- the C-caller path
-def test_c_caller_path_from_points_to_point_features(ftx_lib):
-    """ctypes only, no CoordinateManager: the three phases, then ftx_spvcnn_eval on the tables phase C wrote; z3 equals the point features
-    of the Python path (switches off)."""
+def _np_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def plain_arena(nbytes):
+    return torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+
+def c_caller_inputs():
+    """(feats (n, c_in), coords (n, 4) float32, the batch) of the C-caller recipe: two frames, at most 4000 points each."""
+    from fusiontransformer_amd.data.synth import make_batch
+    batch = make_batch([6, 7], max_points=4000)
+    return torch.from_numpy(batch["feats"]).cuda(), torch.from_numpy(batch["coords"]).float().cuda().contiguous(), batch
+
+
+def c_caller_index(L, feats, coords, arena=plain_arena, with_backward_segments=0, after=None):
+    """ctypes only, no CoordinateManager: the three phases on arenas from arena(nbytes) (uint8, of exactly the phase's own figure);
+    after(phase, arena), when given, runs behind every phase.  Returns the arenas, the two host reads and the tables phase C wrote."""
     from fusiontransformer_amd import native_eval as ne
     from fusiontransformer_amd import functional as spf
-    from fusiontransformer_amd.data.synth import make_batch
-    L = ftx_lib
-    cfg, model, net, _ = _build("lidar", seed=2)
-    model.eval()
-    batch = make_batch([6, 7], max_points=4000)
-    feats = torch.from_numpy(batch["feats"]).cuda()
-    coords = torch.from_numpy(batch["coords"]).float().cuda().contiguous()
     n, c_in = feats.shape
     st = spf.stream()
-    vp = ctypes.c_void_p
-    ptr = lambda a: a.ctypes.data_as(vp)
+    bwd = int(with_backward_segments)
 
-    def arena(nbytes):
+    def sized(nbytes):
         assert nbytes > 0, L.ftx_last_error()
-        return torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        return arena(nbytes)
+    done = after or (lambda phase, buf: None)
     pinned = torch.empty(16, dtype=torch.int32, pin_memory=True)
-    a = arena(L.ftx_spvcnn_index_levels_arena_bytes(n))
+    a = sized(L.ftx_spvcnn_index_levels_arena_bytes(n))
     spf.check(L.ftx_spvcnn_index_levels(coords.data_ptr(), n, 1.0, 1.0, a.data_ptr(), a.shape[0], pinned.data_ptr(), st), "levels")
     torch.cuda.current_stream().synchronize()                                   # host read 1
+    done("levels", a)
     off = np.array(pinned[:6].tolist(), dtype=np.int32)
-    b = arena(L.ftx_spvcnn_index_maps_arena_bytes(n, c_in, ptr(off), 0))
-    assert L.ftx_spvcnn_index_maps(coords.data_ptr(), n, 1.0, 1.0, feats.data_ptr(), c_in, ptr(off), 0, a.data_ptr(), a.shape[0], b.data_ptr(),
+    b = sized(L.ftx_spvcnn_index_maps_arena_bytes(n, c_in, _np_ptr(off), bwd))
+    assert L.ftx_spvcnn_index_maps(coords.data_ptr(), n, 1.0, 1.0, feats.data_ptr(), c_in, _np_ptr(off), bwd, a.data_ptr(), a.shape[0], b.data_ptr(),
                                    b.shape[0] - 256, pinned.data_ptr(), st) == -3, "an arena that is too small is refused"
-    spf.check(L.ftx_spvcnn_index_maps(coords.data_ptr(), n, 1.0, 1.0, feats.data_ptr(), c_in, ptr(off), 0, a.data_ptr(), a.shape[0], b.data_ptr(),
+    spf.check(L.ftx_spvcnn_index_maps(coords.data_ptr(), n, 1.0, 1.0, feats.data_ptr(), c_in, _np_ptr(off), bwd, a.data_ptr(), a.shape[0], b.data_ptr(),
                                       b.shape[0], pinned.data_ptr(), st), "maps")
     torch.cuda.current_stream().synchronize()                                   # host read 2
+    done("maps", b)
     pairs = np.array(pinned[:5].tolist(), dtype=np.int32)
-    c = arena(L.ftx_spvcnn_index_pairs_arena_bytes(n, ptr(off), ptr(pairs)))
+    c = sized(L.ftx_spvcnn_index_pairs_arena_bytes(n, _np_ptr(off), _np_ptr(pairs)))
     rows, maps, pvs = np.zeros(6, np.int64), np.zeros(9, ne.MAP), np.zeros(3, ne.PV)
-    x0 = vp()
-    spf.check(L.ftx_spvcnn_index_pairs(n, c_in, ptr(off), 0, ptr(pairs), a.data_ptr(), b.data_ptr(), b.shape[0], c.data_ptr(), c.shape[0], ptr(rows),
-                                       ptr(maps), ptr(pvs), ctypes.byref(x0), st), "pairs")
+    x0 = ctypes.c_void_p()
+    spf.check(L.ftx_spvcnn_index_pairs(n, c_in, _np_ptr(off), bwd, _np_ptr(pairs), a.data_ptr(), b.data_ptr(), b.shape[0], c.data_ptr(), c.shape[0], _np_ptr(rows),
+                                       _np_ptr(maps), _np_ptr(pvs), ctypes.byref(x0), st), "pairs")
+    torch.cuda.current_stream().synchronize()
+    done("pairs", c)
     assert list(maps["n_pairs"][:5]) == list(pairs) and rows[5] == n and x0.value
+    return dict(a=a, b=b, c=c, off=off, pairs=pairs, rows=rows, maps=maps, pvs=pvs, x0=x0, n=n, c_in=c_in, bwd=bwd)
 
-    # the model side: program, layer table, routes (the host's one routing rule, from the tables alone)
+
+def c_caller_eval(L, net, t, arena=plain_arena):
+    """ftx_spvcnn_eval on the tables c_caller_index returned: the model side (program, layer table, routes: the host's one routing rule,
+    from the tables alone), an arena of exactly ftx_spvcnn_eval_arena_bytes from arena(nbytes).  Returns (z3, the arena)."""
+    from fusiontransformer_amd import native_eval as ne
+    from fusiontransformer_amd import functional as spf
+    rows, maps, pvs = t["rows"], t["maps"], t["pvs"]
     ex = ne.NativeEval(net)
     layers = ex.model_table()
     km = lambda m: type("KM", (), dict(n_pairs=int(m["n_pairs"]), n_in=int(m["n_in"]), n_out=int(m["n_out"]), kvol=int(m["kvol"]),
@@ -362,11 +381,23 @@ def test_c_caller_path_from_points_to_point_features(ftx_lib):
             l = layers[layer]
             routes[i] = ne.ROUTES[spf._conv_route(kms[map_], bool(l["transposed"]), int(l["ca"]), int(l["co"]), int(l["kvol"]), int(rows[level]), False)]
     need = ne.arena_bytes(layers, ex.ops, rows, maps, pvs, routes)
-    work = torch.empty(need, dtype=torch.uint8, device="cuda")
-    z3 = torch.empty((n, ex.program.out_channels), dtype=torch.float32, device="cuda")
+    work = arena(need)
+    z3 = torch.empty((t["n"], ex.program.out_channels), dtype=torch.float32, device="cuda")
     spf._stream_scratch()
-    spf.check(L.ftx_spvcnn_eval(ptr(layers), len(layers), ptr(ex.ops), len(ex.ops), ptr(rows), ptr(maps), 9, ptr(pvs), 3, ptr(routes), x0, 0, 2, None, None,
-                                work.data_ptr(), need, z3.data_ptr(), st), "ftx_spvcnn_eval")
+    spf.check(L.ftx_spvcnn_eval(_np_ptr(layers), len(layers), _np_ptr(ex.ops), len(ex.ops), _np_ptr(rows), _np_ptr(maps), 9, _np_ptr(pvs), 3, _np_ptr(routes),
+                                t["x0"], 0, 2, None, None, work.data_ptr(), need, z3.data_ptr(), spf.stream()), "ftx_spvcnn_eval")
+    torch.cuda.synchronize()
+    return z3, work
+
+
+def test_c_caller_path_from_points_to_point_features(ftx_lib):
+    """ctypes only, no CoordinateManager: the three phases, then ftx_spvcnn_eval on the tables phase C wrote; z3 equals the point features
+    of the Python path (switches off)."""
+    L = ftx_lib
+    cfg, model, net, _ = _build("lidar", seed=2)
+    model.eval()
+    feats, coords, batch = c_caller_inputs()
+    z3, _ = c_caller_eval(L, net, c_caller_index(L, feats, coords))
     from fusiontransformer_amd.sparse import SparseTensor
     with torch.no_grad():
         ref = net(SparseTensor(feats, torch.from_numpy(batch["coords"]).int().cuda()))
