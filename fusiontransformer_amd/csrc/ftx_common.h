@@ -24,6 +24,16 @@ __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + 
 // Arena pieces start on 256-byte boundaries.
 inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
+// Consecutive pieces of an arena or workspace: take(bytes) is the offset of the next piece, `end` the size so far.
+struct Offsets256 {
+  int64_t end = 0;
+  int64_t take(int64_t bytes) {
+    const int64_t at = end;
+    end += align256(bytes);
+    return at;
+  }
+};
+
 // Grid for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8, no more.
 inline unsigned grid_for(int64_t work, int block) {
   int64_t g = ceil_div(work, block);

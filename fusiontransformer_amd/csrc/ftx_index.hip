@@ -5,7 +5,7 @@
 // 16-byte coordinate loads, coalesced int32 stores.
 #include <cstring>
 #include <cstdlib>
-#include "ftx_common.h"
+#include "ftx_index_ops.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <string>
@@ -63,16 +63,7 @@ extern "C" int ftx_hash_kernel(const int32_t *coords, int64_t n, const int32_t *
 }
 
 __global__ void floor_coords_kernel(const float4 *__restrict__ pc, int64_t n, int stride, int4 *__restrict__ out) {
-  const float s = (float)stride;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 p = pc[i];
-    int4 o;
-    o.x = (int)floorf(p.x / s) * stride;
-    o.y = (int)floorf(p.y / s) * stride;
-    o.z = (int)floorf(p.z / s) * stride;
-    o.w = (int)p.w;
-    out[i] = o;
-  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = floor_point(pc[i], stride);
 }
 
 extern "C" int ftx_floor_coords(const float *pc, int64_t n, int32_t stride, int32_t *out, void *stream) {
@@ -99,38 +90,14 @@ __global__ void table_init_kernel(int64_t *__restrict__ tk, int32_t *__restrict_
 
 __global__ void table_insert_kernel(const int64_t *__restrict__ keys, int64_t n, int64_t *__restrict__ tk, int32_t *__restrict__ tv,
                                     int64_t cap) {
-  const uint64_t mask = (uint64_t)cap - 1;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t key = keys[i];
-    uint64_t slot = slot_mix((uint64_t)key) & mask;
-    for (int64_t probe = 0; probe < cap; ++probe) {
-      unsigned long long prev = atomicCAS((unsigned long long *)&tk[slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
-      if (prev == (unsigned long long)kEmptyKey || prev == (unsigned long long)key) {
-        atomicMin(&tv[slot], (int32_t)i);
-        break;
-      }
-      slot = (slot + 1) & mask;
-    }
-  }
-}
-
-__device__ inline int32_t table_lookup(int64_t key, const int64_t *__restrict__ tk, const int32_t *__restrict__ tv, uint64_t mask,
-                                       int64_t cap) {
-  uint64_t slot = slot_mix((uint64_t)key) & mask;
-  for (int64_t probe = 0; probe < cap; ++probe) {
-    int64_t cur = tk[slot];
-    if (cur == key) return tv[slot];
-    if (cur == kEmptyKey) return -1;
-    slot = (slot + 1) & mask;
-  }
-  return -1;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    table_insert(keys[i], (int32_t)i, tk, tv, cap);
 }
 
 __global__ void table_query_kernel(const int64_t *__restrict__ q, int64_t nq, const int64_t *__restrict__ tk,
                                    const int32_t *__restrict__ tv, int64_t cap, int32_t *__restrict__ out) {
-  const uint64_t mask = (uint64_t)cap - 1;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = table_lookup(q[i], tk, tv, mask, cap);
+    out[i] = table_lookup(q[i], tk, tv, cap);
 }
 
 static bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
@@ -177,8 +144,6 @@ __global__ void iota_kernel(int32_t *__restrict__ v, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = (int32_t)i;
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct UniqueLayout {
   size_t off_keys, off_vals_in, off_vals_sorted, off_tmp, tmp_bytes, total;
 };
@@ -193,12 +158,13 @@ static int unique_layout(int64_t n, UniqueLayout *L) {
     set_error("ftx_unique: rocprim size query failed");
     return FTX_ELAUNCH;
   }
-  L->off_keys = 0;
-  L->off_vals_in = align256(L->off_keys + sizeof(int64_t) * n);
-  L->off_vals_sorted = align256(L->off_vals_in + sizeof(int32_t) * n);
-  L->off_tmp = align256(L->off_vals_sorted + sizeof(int32_t) * n);
+  Offsets256 o;
+  L->off_keys = o.take(sizeof(int64_t) * n);
+  L->off_vals_in = o.take(sizeof(int32_t) * n);
+  L->off_vals_sorted = o.take(sizeof(int32_t) * n);
   L->tmp_bytes = sort_bytes > uniq_bytes ? sort_bytes : uniq_bytes;
-  L->total = align256(L->off_tmp + L->tmp_bytes);
+  L->off_tmp = o.take(L->tmp_bytes);
+  L->total = o.end;
   return FTX_OK;
 }
 
@@ -258,11 +224,7 @@ __global__ void sorted_rank_kernel(const int64_t *__restrict__ sorted, const int
   if (m > cap) m = cap;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t key = q[i];
-    int64_t lo = 0, hi = m;
-    while (lo < hi) {
-      int64_t mid = (lo + hi) >> 1;
-      if (sorted[mid] < key) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = lower_bound(sorted, m, key);
     rank[i] = (lo < m && sorted[lo] == key) ? (int32_t)lo : -1;
   }
 }
@@ -306,19 +268,8 @@ extern "C" int ftx_rotate_points(const float *points, int64_t n, const float *ro
 }
 
 // ---------------------------------------------------------------- downsample / gather of coordinate rows
-__device__ inline int floor_div(int a, int b) {
-  int q = a / b;
-  return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
-}
-
 __global__ void downsample_kernel(const int4 *__restrict__ c, int64_t n, int ratio, int4 *__restrict__ out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int4 v = c[i];
-    v.x = floor_div(v.x, ratio) * ratio;
-    v.y = floor_div(v.y, ratio) * ratio;
-    v.z = floor_div(v.z, ratio) * ratio;
-    out[i] = v;
-  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = level_coord(c[i], ratio);
 }
 
 extern "C" int ftx_downsample_coords(const int32_t *coords, int64_t n, int32_t ratio, int32_t *out, void *stream) {
@@ -347,7 +298,7 @@ extern "C" int ftx_gather_coords(const int32_t *src, const int32_t *index, int64
 // torchsparse's spdownsample does -- is a chain of five (hash, sort, unique, read the count back) rounds; floor division composes
 // (floor(floor(x/2)/2) = floor(x/4)), so here every level is hashed straight from the points, the L x N (level tag | hash) keys are sorted
 // ONCE, and ONE host read returns all level sizes.  Same sets, same order, same coordinates as the chain (tested bit for bit).
-constexpr int LV_MAX = 8;               // level tags live in bits 60..62 of the key (hashes are 60-bit)
+constexpr int LV_MAX = 8;               // level tags live in bits 60..62 of the key (level_key)
 struct LevelStrides { int32_t s[LV_MAX]; };
 
 __global__ void levels_hash_kernel(const int4 *__restrict__ pts, int64_t n, LevelStrides st, int nl, int64_t *__restrict__ keys, int32_t *__restrict__ vals) {
@@ -355,10 +306,8 @@ __global__ void levels_hash_kernel(const int4 *__restrict__ pts, int64_t n, Leve
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int l = (int)(e / n);
     const int64_t i = e - (int64_t)l * n;
-    const int4 c = pts[i];
-    const int s = st.s[l];
-    const int64_t h = fnv_hash4(floor_div(c.x, s) * s, floor_div(c.y, s) * s, floor_div(c.z, s) * s, c.w);
-    keys[e] = ((int64_t)l << 60) | h;
+    const int4 c = level_coord(pts[i], st.s[l]);
+    keys[e] = level_key(l, fnv_hash4(c.x, c.y, c.z, c.w));
     vals[e] = (int32_t)i;
   }
 }
@@ -370,18 +319,12 @@ __global__ void levels_offsets_kernel(const int64_t *__restrict__ uniq, const in
   if (l > nl) return;
   const int64_t total = *n_unique;
   if (l == nl) { level_off[nl] = (int32_t)total; return; }
-  const int64_t want = (int64_t)l << 60;      // first key >= (l << 60)
-  int64_t lo = 0, hi = total;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (uniq[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  level_off[l] = (int32_t)lo;
+  level_off[l] = (int32_t)lower_bound(uniq, total, level_key(l, 0));      // first key that carries the tag
 }
 __global__ void levels_strip_kernel(int64_t *__restrict__ uniq, const int32_t *__restrict__ n_unique) {
   const int64_t total = *n_unique;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
-    uniq[i] &= 0x0FFFFFFFFFFFFFFFLL;
+    uniq[i] &= kLevelHashMask;
 }
 
 struct LevelsLayout {
@@ -398,14 +341,15 @@ static int levels_layout(int64_t n, int nl, LevelsLayout *L) {
     set_error("ftx_levels_unique: rocprim size query failed");
     return FTX_ELAUNCH;
   }
-  L->off_keys = 0;
-  L->off_keys_sorted = align256(L->off_keys + sizeof(int64_t) * m);
-  L->off_vals_in = align256(L->off_keys_sorted + sizeof(int64_t) * m);
-  L->off_vals_sorted = align256(L->off_vals_in + sizeof(int32_t) * m);
-  L->off_count = align256(L->off_vals_sorted + sizeof(int32_t) * m);
-  L->off_tmp = align256(L->off_count + 256);
+  Offsets256 o;
+  L->off_keys = o.take(sizeof(int64_t) * m);
+  L->off_keys_sorted = o.take(sizeof(int64_t) * m);
+  L->off_vals_in = o.take(sizeof(int32_t) * m);
+  L->off_vals_sorted = o.take(sizeof(int32_t) * m);
+  L->off_count = o.take(256);
   L->tmp_bytes = sort_bytes > uniq_bytes ? sort_bytes : uniq_bytes;
-  L->total = align256(L->off_tmp + L->tmp_bytes);
+  L->off_tmp = o.take(L->tmp_bytes);
+  L->total = o.end;
   return FTX_OK;
 }
 
@@ -472,13 +416,7 @@ __global__ void level_segments_kernel(const int64_t *__restrict__ sorted_keys, i
                                       int32_t *__restrict__ seg_off) {
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v <= m; v += (int64_t)gridDim.x * blockDim.x) {
     if (v == m) { seg_off[m] = (int32_t)n; continue; }
-    const int64_t want = (tag << 60) | uniq[v];
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sorted_keys[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    seg_off[v] = (int32_t)lo;
+    seg_off[v] = (int32_t)lower_bound(sorted_keys, n, level_key(tag, uniq[v]));
   }
 }
 extern "C" int ftx_level_segments(const int64_t *sorted_keys, int64_t n, const int64_t *uniq, int64_t m, int32_t level, int32_t *seg_off, void *stream) {
@@ -490,13 +428,8 @@ extern "C" int ftx_level_segments(const int64_t *sorted_keys, int64_t n, const i
 
 // coords of one level: out[r] = floor_div(points[first[r]], stride) * stride (batch column kept): the rows of that level in hash order
 __global__ void level_coords_kernel(const int4 *__restrict__ pts, const int32_t *__restrict__ first, int64_t n, int stride, int4 *__restrict__ out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int4 v = pts[first[i]];
-    v.x = floor_div(v.x, stride) * stride;
-    v.y = floor_div(v.y, stride) * stride;
-    v.z = floor_div(v.z, stride) * stride;
-    out[i] = v;
-  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = level_coord(pts[first[i]], stride);
 }
 extern "C" int ftx_level_coords(const int32_t *points, const int32_t *first_index, int64_t n, int32_t stride, int32_t *out, void *stream) {
   FTX_REQUIRE(n >= 0 && stride >= 1, "ftx_level_coords: bad size / stride");
@@ -512,14 +445,13 @@ extern "C" int ftx_level_coords(const int32_t *points, const int32_t *first_inde
 __global__ void kernel_map_kernel(const int4 *__restrict__ oc, int64_t n_out, const int32_t *__restrict__ offsets, int k,
                                   const int64_t *__restrict__ tk, const int32_t *__restrict__ tv, int64_t cap,
                                   int32_t *__restrict__ nbr) {
-  const uint64_t mask = (uint64_t)cap - 1;
   const int64_t total = n_out * k;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     int kk = (int)(e / n_out);
     int64_t o = e - (int64_t)kk * n_out;
     int4 c = oc[o];
     int64_t h = fnv_hash4(c.x + offsets[kk * 3 + 0], c.y + offsets[kk * 3 + 1], c.z + offsets[kk * 3 + 2], c.w);
-    nbr[e] = table_lookup(h, tk, tv, mask, cap);
+    nbr[e] = table_lookup(h, tk, tv, cap);
   }
 }
 
@@ -535,40 +467,11 @@ extern "C" int ftx_kernel_map_build(const int32_t *out_coords, int64_t n_out, co
 }
 
 // ---------------------------------------------------------------- trilinear weights
-// float32 arithmetic in upstream calc_ti_weights' operation order; corner order (bx,by,bz) with z fastest
-// (= KernelRegion(2, s, 1) offsets).
+// trilinear_row (ftx_index_ops.h) per point: float32 arithmetic in upstream calc_ti_weights' operation order
 __global__ void trilinear_kernel(const float4 *__restrict__ pc, const int32_t *__restrict__ idx, int64_t n, int scale,
                                  float *__restrict__ w) {
-  const float s = (float)scale;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 p = pc[i];
-    float fx, fy, fz;
-    if (scale != 1) {
-      fx = floorf(p.x / s) * s; fy = floorf(p.y / s) * s; fz = floorf(p.z / s) * s;
-    } else {
-      fx = floorf(p.x); fy = floorf(p.y); fz = floorf(p.z);
-    }
-    float cx = fx + s, cy = fy + s, cz = fz + s;
-    // float32 throughout, in upstream's operation order (torchsparse calc_ti_weights works in the dtype of `pc`, float32):
-    // three-factor product, division by scale^3, zero for absent corners, sum of the 8, division by (sum + 1e-8)
-    const float lo[3] = {p.x - fx, p.y - fy, p.z - fz};
-    const float hi[3] = {cx - p.x, cy - p.y, cz - p.z};
-    float ws[8];
-    float sum = 0.f;
-    const float inv = s * s * s;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      int bx = (c >> 2) & 1, by = (c >> 1) & 1, bz = c & 1;
-      float v = ((bx ? lo[0] : hi[0]) * (by ? lo[1] : hi[1])) * (bz ? lo[2] : hi[2]);
-      if (scale != 1) v = v / inv;
-      if (idx[i * 8 + c] < 0) v = 0.f;
-      ws[c] = v;
-      sum += v;
-    }
-    const float den = sum + 1e-8f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) w[i * 8 + c] = ws[c] / den;
-  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    trilinear_row(pc[i], idx + i * 8, scale, w + i * 8);
 }
 
 extern "C" int ftx_trilinear_weights(const float *pc, const int32_t *idx, int64_t n, int32_t scale, float *weights, void *stream) {

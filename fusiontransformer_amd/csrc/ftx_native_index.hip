@@ -5,15 +5,16 @@
 // The per-level entry points launch a handful of latency-bound kernels per level, five (or nine, or three) times over.  Here every
 // repeated step is ONE launch over all its instances: a descriptor passed by value (kernel arguments; at most twelve instances, so no
 // table has to be copied to the device) gives each instance its pointers, sizes and the first element it owns in the launch's
-// flat index space.  The dependent chain then has the depth of one level.  The arithmetic of every step is that of the per-level
-// kernel it replaces (ftx_index.hip, ftx_spconv.hip, ftx_pointvoxel.hip), so the outputs are equal bit for bit: smallest row wins
-// for duplicate keys in the hash table, pair lists are in (k, o) order.
+// flat index space.  The dependent chain then has the depth of one level.  The arithmetic of every step is the per-level kernel's
+// (ftx_index.hip, ftx_spconv.hip, ftx_pointvoxel.hip) because both call the same element functions (ftx_index_ops.h), so the outputs
+// are equal bit for bit: smallest row wins for duplicate keys in the hash table, pair lists are in (k, o) order.  What is this
+// file's own is which instance an element belongs to, where its arrays lie, and the validity scan over all maps at once.
 //
 // Memory: three caller-owned arenas, one per phase, each sized by a host-only function from the values known when the phase is
 // issued (A: n; B: n, c_in and the level sizes; C: the level sizes and the pair counts).  Every region is 256-byte aligned.
 // Temporaries (sort and scan workspaces) are the tail of arenas A and B.
 #include <cstring>
-#include "ftx_common.h"
+#include "ftx_index_ops.h"
 #include "ftx_spvcnn_tables.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -61,25 +62,20 @@ int make_layout(const char *who, int64_t n, int32_t c_in, const int32_t *off, co
   LAY_REQUIRE(n * 24 < 0x7fffffff, "%s: n = %lld is too large for int32 rows", who, (long long)n);
   L.n = n;
   L.c = c_in;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t at = o;
-    o += align256(bytes);
-    return at;
-  };
+  Offsets256 o;
   const int64_t m = n * kNL;
-  L.a_coords = take(16 * n);
-  L.a_points = take(16 * n);
-  L.a_uniq = take(8 * m);
-  L.a_first = take(4 * m);
-  L.a_skeys = take(8 * m);
-  L.a_order = take(4 * m);
-  L.a_level_off = take(256);
+  L.a_coords = o.take(16 * n);
+  L.a_points = o.take(16 * n);
+  L.a_uniq = o.take(8 * m);
+  L.a_first = o.take(4 * m);
+  L.a_skeys = o.take(8 * m);
+  L.a_order = o.take(4 * m);
+  L.a_level_off = o.take(256);
   // ftx_levels_unique's workspace: keys, sorted keys, two value arrays (24 B per key) and the sort / unique temporaries, which no host-only
   // formula gives exactly; this bound is checked against ftx_levels_workspace_bytes when the phase is issued (FTX_EWORKSPACE if it falls short)
   L.a_ws_bytes = align256(40 * m + (4 << 20));
-  L.a_ws = take(L.a_ws_bytes);
-  L.a_total = o;
+  L.a_ws = o.take(L.a_ws_bytes);
+  L.a_total = o.end;
   if (!off) return FTX_OK;
 
   LAY_REQUIRE(c_in >= 4 && c_in % 4 == 0 && c_in <= 1024, "%s: c_in = %d must be a multiple of 4 in [4, 1024]", who, c_in);
@@ -93,13 +89,13 @@ int make_layout(const char *who, int64_t n, int32_t c_in, const int32_t *off, co
     L.cap[l] = ftx_hashtable_capacity(sz);
   }
   L.off[kNL] = off[kNL];
-  o = 0;
+  o = Offsets256();
   for (int l = 0; l < kNL; ++l) {
-    L.b_coords[l] = take(16 * L.nl[l]);
-    L.b_tkeys[l] = take(8 * L.cap[l]);
-    L.b_tvals[l] = take(4 * L.cap[l]);
+    L.b_coords[l] = o.take(16 * L.nl[l]);
+    L.b_tkeys[l] = o.take(8 * L.cap[l]);
+    L.b_tvals[l] = o.take(4 * L.cap[l]);
   }
-  L.b_x0 = take(4 * L.nl[0] * c_in);
+  L.b_x0 = o.take(4 * L.nl[0] * c_in);
   int64_t e = 0;
   for (int mi = 0; mi < kNM; ++mi) {
     const bool sub = mi < kNL;
@@ -111,61 +107,61 @@ int make_layout(const char *who, int64_t n, int32_t c_in, const int32_t *off, co
   }
   L.map_start[kNM] = e;
   LAY_REQUIRE(e < 0x7fffffff, "%s: the kernel maps have too many entries for int32 positions", who);
-  L.b_nbr = take(4 * e);
-  L.b_pos = take(4 * e);
-  for (int mi = 0; mi < kNM; ++mi) L.b_koff[mi] = take(4 * (L.map_k[mi] + 1));
-  L.b_mapbase = take(4 * 16);
-  L.b_paircounts = take(4 * 16);
-  L.b_pos_t2 = o;
-  for (int i = 0; i < 4; ++i) L.pos_t2[i] = take(4 * 8 * L.nl[i]);
-  L.b_pos_t2_bytes = o - L.b_pos_t2;
+  L.b_nbr = o.take(4 * e);
+  L.b_pos = o.take(4 * e);
+  for (int mi = 0; mi < kNM; ++mi) L.b_koff[mi] = o.take(4 * (L.map_k[mi] + 1));
+  L.b_mapbase = o.take(4 * 16);
+  L.b_paircounts = o.take(4 * 16);
+  L.b_pos_t2 = o.end;
+  for (int i = 0; i < 4; ++i) L.pos_t2[i] = o.take(4 * 8 * L.nl[i]);
+  L.b_pos_t2_bytes = o.end - L.b_pos_t2;
   for (int i = 0; i < 4; ++i) {
-    L.pair_in2[i] = take(4 * L.nl[i]);
-    L.pair_out2[i] = take(4 * L.nl[i]);
+    L.pair_in2[i] = o.take(4 * L.nl[i]);
+    L.pair_out2[i] = o.take(4 * L.nl[i]);
   }
-  for (int j = 0; j < kNPV; ++j) L.vidx[j] = take(4 * n);
-  L.b_vcnt = o;
-  for (int j = 0; j < kNPV; ++j) L.vcnt[j] = take(4 * L.nl[kPvLevel[j]]);
-  L.b_vcnt_bytes = o - L.b_vcnt;
+  for (int j = 0; j < kNPV; ++j) L.vidx[j] = o.take(4 * n);
+  L.b_vcnt = o.end;
+  for (int j = 0; j < kNPV; ++j) L.vcnt[j] = o.take(4 * L.nl[kPvLevel[j]]);
+  L.b_vcnt_bytes = o.end - L.b_vcnt;
   for (int j = 0; j < kNPV; ++j) {
-    L.vseg[j] = take(4 * (L.nl[kPvLevel[j]] + 1));
-    L.didx[j] = take(32 * n);
-    L.dw[j] = take(32 * n);
+    L.vseg[j] = o.take(4 * (L.nl[kPvLevel[j]] + 1));
+    L.didx[j] = o.take(32 * n);
+    L.dw[j] = o.take(32 * n);
   }
   if (with_bwd) {
-    const int64_t d = take(4 * 8 * n * kNPV);      // the three sorted entry lists back to back: one sort writes them
+    const int64_t d = o.take(4 * 8 * n * kNPV);      // the three sorted entry lists back to back: one sort writes them
     for (int j = 0; j < kNPV; ++j) {
       L.dorder[j] = d + 32 * n * j;
-      L.dseg[j] = take(4 * (L.nl[kPvLevel[j]] + 1));
+      L.dseg[j] = o.take(4 * (L.nl[kPvLevel[j]] + 1));
     }
   }
   L.n_blocks = ceil_div(e, kScanChunk);
-  L.b_bsum = take(4 * L.n_blocks);
+  L.b_bsum = o.take(4 * L.n_blocks);
   if (with_bwd) {
     const int64_t ne = 8 * n * kNPV;
-    L.b_skin = take(4 * ne);
-    L.b_skout = take(4 * ne);
-    L.b_svin = take(4 * ne);
+    L.b_skin = o.take(4 * ne);
+    L.b_skout = o.take(4 * ne);
+    L.b_svin = o.take(4 * ne);
     // radix sort temporaries: bounded like arena A's, checked against rocprim's own figure when the phase is issued
     L.b_stmp_bytes = align256(12 * ne + (4 << 20));
-    L.b_stmp = take(L.b_stmp_bytes);
+    L.b_stmp = o.take(L.b_stmp_bytes);
   }
-  L.b_total = o;
+  L.b_total = o.end;
   if (!pairs) return FTX_OK;
 
-  o = 0;
+  o = Offsets256();
   for (int l = 0; l < kNL; ++l) {
     LAY_REQUIRE(pairs[l] >= 0 && pairs[l] <= 27 * L.nl[l], "%s: level %d: %d pairs is outside 0 .. 27 * %lld", who, l, pairs[l], (long long)L.nl[l]);
     L.pairs[l] = pairs[l];
   }
-  L.c_pos_t = o;
-  for (int l = 0; l < kNL; ++l) L.pos_t3[l] = take(4 * 27 * L.nl[l]);
-  L.c_pos_t_bytes = o - L.c_pos_t;
+  L.c_pos_t = o.end;
+  for (int l = 0; l < kNL; ++l) L.pos_t3[l] = o.take(4 * 27 * L.nl[l]);
+  L.c_pos_t_bytes = o.end - L.c_pos_t;
   for (int l = 0; l < kNL; ++l) {
-    L.pair_in3[l] = take(4 * L.pairs[l]);
-    L.pair_out3[l] = take(4 * L.pairs[l]);
+    L.pair_in3[l] = o.take(4 * L.pairs[l]);
+    L.pair_out3[l] = o.take(4 * L.pairs[l]);
   }
-  L.c_total = o < 256 ? 256 : o;
+  L.c_total = o.end < 256 ? 256 : o.end;
   return FTX_OK;
 }
 
@@ -182,35 +178,6 @@ void export_layout(const Lay &L, int64_t *w) {
   static_assert(3 + 6 + 4 * kNL + 1 + 3 * kNM + 12 + 7 * kNPV + 3 * kNL == kLayoutWords, "layout words");
 }
 
-// ---------------------------------------------------------------- device helpers (the per-level kernels' own, ftx_index.hip)
-__device__ inline int nx_floor_div(int a, int b) {
-  int q = a / b;
-  return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
-}
-
-__device__ inline int32_t nx_lookup(int64_t key, const int64_t *__restrict__ tk, const int32_t *__restrict__ tv, int64_t cap) {
-  const uint64_t mask = (uint64_t)cap - 1;
-  uint64_t slot = slot_mix((uint64_t)key) & mask;
-  for (int64_t probe = 0; probe < cap; ++probe) {
-    int64_t cur = tk[slot];
-    if (cur == key) return tv[slot];
-    if (cur == kEmptyKey) return -1;
-    slot = (slot + 1) & mask;
-  }
-  return -1;
-}
-
-// floor_coords_kernel's row: floor(p / s) * s per axis, the batch column cast
-__device__ inline int4 nx_floor_point(float4 p, int stride) {
-  const float s = (float)stride;
-  int4 o;
-  o.x = (int)floorf(p.x / s) * stride;
-  o.y = (int)floorf(p.y / s) * stride;
-  o.z = (int)floorf(p.z / s) * stride;
-  o.w = (int)p.w;
-  return o;
-}
-
 // ---------------------------------------------------------------- phase A: rescale + floor
 // new_float_coord of initial_voxelize: (x * init_res) / after_res in float32, where the division by a host scalar is the multiplication
 // by its float32 reciprocal that the tensor library performs; then floor_coords(., 1)
@@ -224,7 +191,7 @@ __global__ void nx_rescale_floor_kernel(const float4 *__restrict__ pc, int64_t n
       p.z = __fmul_rn(__fmul_rn(p.z, mul), inv);
       zc[i] = p;
     }
-    pts[i] = nx_floor_point(p, 1);
+    pts[i] = floor_point(p, 1);
   }
 }
 
@@ -268,24 +235,8 @@ __global__ void nx_levels_kernel(LevelsDesc D) {
     const int stride = D.stride[l];
     int32_t f = D.first[e];
     f = f < 0 ? 0 : (f >= D.n_points ? D.n_points - 1 : f);   // a true first-occurrence row is inside; offsets that are not phase A's must not read outside
-    int4 v = D.pts[f];
-    v.x = nx_floor_div(v.x, stride) * stride;
-    v.y = nx_floor_div(v.y, stride) * stride;
-    v.z = nx_floor_div(v.z, stride) * stride;
-    D.coords[l][r] = v;
-    const int64_t key = D.uniq[e];
-    const int64_t cap = D.cap[l];
-    const uint64_t mask = (uint64_t)cap - 1;
-    int64_t *tk = D.tk[l];
-    uint64_t slot = slot_mix((uint64_t)key) & mask;
-    for (int64_t probe = 0; probe < cap; ++probe) {
-      unsigned long long prev = atomicCAS((unsigned long long *)&tk[slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
-      if (prev == (unsigned long long)kEmptyKey || prev == (unsigned long long)key) {
-        atomicMin(&D.tv[l][slot], (int32_t)r);
-        break;
-      }
-      slot = (slot + 1) & mask;
-    }
+    D.coords[l][r] = level_coord(D.pts[f], stride);
+    table_insert(D.uniq[e], (int32_t)r, D.tk[l], D.tv[l], D.cap[l]);
   }
 }
 
@@ -314,8 +265,8 @@ __global__ void nx_point_query_kernel(PvDesc D) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int j = (int)(e / D.n);
     const int64_t i = e - (int64_t)j * D.n;
-    const int4 c = nx_floor_point(D.zc[i], D.stride[j]);
-    const int32_t r = nx_lookup(fnv_hash4(c.x, c.y, c.z, c.w), D.tk[j], D.tv[j], D.cap[j]);
+    const int4 c = floor_point(D.zc[i], D.stride[j]);
+    const int32_t r = table_lookup(fnv_hash4(c.x, c.y, c.z, c.w), D.tk[j], D.tv[j], D.cap[j]);
     D.vidx[j][i] = r;
     if (r >= 0 && r < D.m[j]) atomicAdd(&D.vcnt[j][r], 1);
   }
@@ -328,14 +279,7 @@ __global__ void nx_level_segments_kernel(PvDesc D) {
     const int j = nx_find(D.seg_start, kNPV, e);
     const int64_t v = e - D.seg_start[j], m = D.m[j];
     if (v == m) { D.vseg[j][m] = (int32_t)D.n; continue; }
-    const int64_t want = ((int64_t)D.level[j] << 60) | D.uniq[j][v];
-    const int64_t *sk = D.skeys[j];
-    int64_t lo = 0, hi = D.n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sk[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    D.vseg[j][v] = (int32_t)lo;
+    D.vseg[j][v] = (int32_t)lower_bound(D.skeys[j], D.n, level_key(D.level[j], D.uniq[j][v]));
   }
 }
 
@@ -354,14 +298,6 @@ struct NbrDesc {
   int64_t starts[kNM + kNPV + 1];
 };
 
-__device__ inline void nx_offset(int ks, int kk, int stride, int &dx, int &dy, int &dz) {
-  if (ks == 27) {           // odd kernels enumerate x fastest
-    dx = (kk % 3 - 1) * stride; dy = ((kk / 3) % 3 - 1) * stride; dz = (kk / 9 - 1) * stride;
-  } else {                  // even kernels z fastest, offsets 0 / +stride
-    dx = ((kk >> 2) & 1) * stride; dy = ((kk >> 1) & 1) * stride; dz = (kk & 1) * stride;
-  }
-}
-
 __global__ void nx_nbr_kernel(NbrDesc D) {
   const int64_t total = D.starts[kNM + kNPV];
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -373,14 +309,14 @@ __global__ void nx_nbr_kernel(NbrDesc D) {
     int4 c;
     if (I.corners) {
       kk = (int)(loc & 7);
-      c = nx_floor_point(((const float4 *)I.src)[loc >> 3], I.stride);
+      c = floor_point(((const float4 *)I.src)[loc >> 3], I.stride);
     } else {
       kk = (int)(loc / I.rows);
       c = ((const int4 *)I.src)[loc - (int64_t)kk * I.rows];
     }
     int dx, dy, dz;
-    nx_offset(I.k, kk, I.stride, dx, dy, dz);
-    I.out[loc] = nx_lookup(fnv_hash4(c.x + dx, c.y + dy, c.z + dz, c.w), I.tk, I.tv, I.cap);
+    kernel_offset(I.k, kk, I.stride, dx, dy, dz);
+    I.out[loc] = table_lookup(fnv_hash4(c.x + dx, c.y + dy, c.z + dz, c.w), I.tk, I.tv, I.cap);
   }
 }
 
@@ -390,35 +326,7 @@ __global__ void nx_trilinear_kernel(PvDesc D) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int j = (int)(e / D.n);
     const int64_t i = e - (int64_t)j * D.n;
-    const int scale = D.stride[j];
-    const int32_t *idx = D.didx[j];
-    float *w = D.dw[j];
-    const float s = (float)scale;
-    float4 p = D.zc[i];
-    float fx, fy, fz;
-    if (scale != 1) {
-      fx = floorf(p.x / s) * s; fy = floorf(p.y / s) * s; fz = floorf(p.z / s) * s;
-    } else {
-      fx = floorf(p.x); fy = floorf(p.y); fz = floorf(p.z);
-    }
-    float cx = fx + s, cy = fy + s, cz = fz + s;
-    const float lo[3] = {p.x - fx, p.y - fy, p.z - fz};
-    const float hi[3] = {cx - p.x, cy - p.y, cz - p.z};
-    float ws[8];
-    float sum = 0.f;
-    const float inv = s * s * s;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      int bx = (c >> 2) & 1, by = (c >> 1) & 1, bz = c & 1;
-      float v = ((bx ? lo[0] : hi[0]) * (by ? lo[1] : hi[1])) * (bz ? lo[2] : hi[2]);
-      if (scale != 1) v = v / inv;
-      if (idx[i * 8 + c] < 0) v = 0.f;
-      ws[c] = v;
-      sum += v;
-    }
-    const float den = sum + 1e-8f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) w[i * 8 + c] = ws[c] / den;
+    trilinear_row(D.zc[i], D.didx[j] + i * 8, D.stride[j], D.dw[j] + i * 8);
   }
 }
 
@@ -518,15 +426,10 @@ __global__ void nx_koff_kernel(MapsDesc D) {
   if (m >= kNM || kk > D.k[m]) return;
   const int64_t s = D.start[m];
   const int32_t base = D.pos[s];
-  if (kk < D.k[m]) {
-    D.koff[m][kk] = D.pos[s + (int64_t)kk * D.n_out[m]] - base;
-    if (kk == 0) D.mapbase[m] = base;
-  } else {
-    const int64_t last = s + (int64_t)D.k[m] * D.n_out[m] - 1;
-    const int32_t total = D.pos[last] + (D.nbr[last] >= 0 ? 1 : 0) - base;
-    D.koff[m][kk] = total;
-    if (m < kNL) D.paircounts[m] = total;
-  }
+  const int32_t v = koff_entry(D.nbr + s, D.pos + s, D.n_out[m], D.k[m], kk, base);
+  D.koff[m][kk] = v;
+  if (kk == 0) D.mapbase[m] = base;
+  if (kk == D.k[m] && m < kNL) D.paircounts[m] = v;
 }
 
 // pairs_scatter_kernel for maps [first, first + count): pos turns from the scan into the position in the map's own pair list (or -1)
@@ -536,18 +439,7 @@ __global__ void nx_pairs_kernel(MapsDesc D, int first, int count) {
     const int m = first + nx_find(D.start + first, count, e);
     const int64_t loc = e - D.start[m], n_out = D.n_out[m], n_in = D.n_in[m];
     if (loc >= D.k[m] * n_out) continue;      // padding
-    const int32_t i = D.nbr[e];
-    const int32_t p = D.pos[e] - D.mapbase[m];
-    if (i >= 0 && i < n_in && p >= 0 && p < D.cap[m]) {
-      const int kk = (int)(loc / n_out);
-      const int64_t o = loc - (int64_t)kk * n_out;
-      D.pair_in[m][p] = i;
-      D.pair_out[m][p] = (int32_t)o;
-      D.pos_t[m][(int64_t)kk * n_in + i] = p;
-      D.pos[e] = p;
-    } else {
-      D.pos[e] = -1;
-    }
+    D.pos[e] = pair_entry(D.nbr[e], D.pos[e] - D.mapbase[m], loc, n_out, n_in, D.cap[m], D.pair_in[m], D.pair_out[m], D.pos_t[m]);
   }
 }
 
@@ -560,8 +452,7 @@ __global__ void nx_dseg_prepare_kernel(PvDesc D) {
     const int j = (int)(e / per);
     const int64_t i = e - (int64_t)j * per;
     const int32_t k = D.dw[j][i] != 0.f ? D.didx[j][i] : -1;
-    const bool ok = k >= 0 && k < D.m[j];
-    D.keys_in[e] = (int32_t)(D.kbase[j] + (ok ? k : D.m[j]));   // dropped entries sort to the end of their instance
+    D.keys_in[e] = (int32_t)(D.kbase[j] + segment_key(k, D.m[j]));   // dropped entries sort to the end of their instance
     D.vals_in[e] = (int32_t)i;
   }
 }
@@ -571,14 +462,7 @@ __global__ void nx_dseg_offsets_kernel(PvDesc D) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int j = nx_find(D.seg_start, kNPV, e);
     const int64_t v = e - D.seg_start[j];
-    const int32_t want = (int32_t)(D.kbase[j] + v);
-    const int32_t *sk = D.keys_out + (int64_t)j * per;
-    int64_t lo = 0, hi = per;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sk[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    D.dseg[j][v] = (int32_t)lo;
+    D.dseg[j][v] = (int32_t)lower_bound(D.keys_out + (int64_t)j * per, per, (int32_t)(D.kbase[j] + v));
   }
 }
 

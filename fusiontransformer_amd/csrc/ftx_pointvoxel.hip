@@ -4,7 +4,7 @@
 // wave cover consecutive 16-byte pieces of the same row (coalesced 128..1024 B).
 #include <cstring>
 #include <cstdlib>
-#include "ftx_common.h"
+#include "ftx_index_ops.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -152,8 +152,6 @@ extern "C" int ftx_devoxelize_bwd(const float *grad_out, const int32_t *idx, con
 // are sorted by destination row once per (batch, stride); each destination then sums its own
 // entries in ascending entry order -> plain loads/stores at stream rate instead of the ~1.3 TB/s
 // float-atomic rate, and bit-reproducible.
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct SegLayout {
   size_t off_keys_in, off_keys_out, off_vals_in, off_tmp, tmp_bytes, total;
 };
@@ -166,12 +164,13 @@ static int seg_layout(int64_t n, int64_t m, SegLayout *L) {
     set_error("ftx_segment_build: rocprim size query failed");
     return FTX_ELAUNCH;
   }
-  L->off_keys_in = 0;
-  L->off_keys_out = align256(sizeof(int32_t) * n);
-  L->off_vals_in = align256(L->off_keys_out + sizeof(int32_t) * n);
-  L->off_tmp = align256(L->off_vals_in + sizeof(int32_t) * n);
+  Offsets256 o;
+  L->off_keys_in = o.take(sizeof(int32_t) * n);
+  L->off_keys_out = o.take(sizeof(int32_t) * n);
+  L->off_vals_in = o.take(sizeof(int32_t) * n);
   L->tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-  L->total = align256(L->off_tmp + L->tmp_bytes);
+  L->off_tmp = o.take(L->tmp_bytes);
+  L->total = o.end;
   return FTX_OK;
 }
 
@@ -185,11 +184,10 @@ extern "C" size_t ftx_segment_workspace_bytes(int64_t n, int64_t m) {
 __global__ void seg_prepare_kernel(const int32_t *__restrict__ keys, int64_t n, int64_t m, int32_t *__restrict__ keys_in,
                                    int32_t *__restrict__ vals_in, int32_t *__restrict__ counts) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int32_t k = keys[i];
-    bool ok = k >= 0 && k < m;
-    keys_in[i] = ok ? k : (int32_t)m;   // invalid entries sort to the end
+    const int32_t k = segment_key(keys[i], m);
+    keys_in[i] = k;
     vals_in[i] = (int32_t)i;
-    if (ok) atomicAdd(&counts[k], 1);
+    if (k < m) atomicAdd(&counts[k], 1);
   }
 }
 

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <cstdlib>
 #include "ftx_bn_eval_op.h"
+#include "ftx_index_ops.h"
 #include "ftx_spconv_common.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -48,11 +49,7 @@ extern "C" size_t ftx_kernel_map_count_workspace_bytes(int64_t n_out, int32_t k)
 
 __global__ void koff_kernel(const int32_t *__restrict__ nbr, const int32_t *__restrict__ scan, int64_t n_out, int k, int32_t *__restrict__ koff) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < k) koff[t] = scan[(int64_t)t * n_out];
-  if (t == k) {
-    int64_t last = (int64_t)k * n_out - 1;
-    koff[k] = scan[last] + (nbr[last] >= 0 ? 1 : 0);
-  }
+  if (t <= k) koff[t] = koff_entry(nbr, scan, n_out, k, t, 0);
 }
 
 extern "C" int ftx_kernel_map_count(const int32_t *nbr, int64_t n_out, int32_t k, int32_t *pos, int32_t *koff, void *workspace,
@@ -91,17 +88,8 @@ __global__ void pairs_scatter_kernel(const int32_t *__restrict__ nbr, int64_t n_
                                      int64_t cap) {
   const int64_t total = n_out * k;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    int32_t i = nbr[e];
-    int32_t p = pos[e];
-    if (i >= 0 && i < n_in && p < cap) {
-      int kk = (int)(e / n_out);
-      int64_t o = e - (int64_t)kk * n_out;
-      pair_in[p] = i;
-      pair_out[p] = (int32_t)o;
-      pos_t[(int64_t)kk * n_in + i] = p;
-    } else {
-      pos[e] = -1;
-    }
+    // pos[e] is this map's own scan, never negative, and already the position where there is a pair
+    if (pair_entry(nbr[e], pos[e], e, n_out, n_in, cap, pair_in, pair_out, pos_t) < 0) pos[e] = -1;
   }
 }
 
