@@ -446,7 +446,9 @@ class _Devoxelize(torch.autograd.Function):
 
 def spdevoxelize(feats, idx, weights, seg=None):
     """spf.spdevoxelize (8-corner weighted gather of voxel rows onto points); `seg` =
-    devoxelize_segments(idx, weights, m) makes the backward atomic-free."""
+    devoxelize_segments(idx, weights, m) makes the backward atomic-free.  Differentiable in feats only: the trilinear weights are data
+    of the point cloud, and weights that ask for a gradient are refused."""
+    _refuse_grad(weights, "spdevoxelize", "weights", "they are computed from the point coordinates, detach them")
     return _Devoxelize.apply(feats, idx, weights, seg)
 
 
@@ -736,6 +738,7 @@ class _RowsLinear(torch.autograd.Function):
         co, ca = weight.shape
         if x.shape[1] != ca:
             raise ValueError("linear: shape mismatch")
+        _channel_operands(x, co, "linear", optional=("bias",), bias=bias)
         ctx.save_for_backward(x, weight)
         ctx.has_bias, ctx.bf16 = bias is not None, bf16
         return _rows_gemm(x, weight, 1, bias, co, bf16)
@@ -761,6 +764,8 @@ class _RowsMatmul(torch.autograd.Function):
     def forward(ctx, x, kernel, bf16=False):
         x = req(x.contiguous(), F32, "matmul x", 2)
         kernel = req(kernel.contiguous(), F32, "matmul kernel", 2)
+        if x.shape[1] != kernel.shape[0]:
+            raise ValueError("matmul: shape mismatch")
         ctx.save_for_backward(x, kernel)
         ctx.bf16 = bf16
         return _rows_gemm(x, kernel, 0, None, kernel.shape[1], bf16)
@@ -834,12 +839,35 @@ def _bn_operands(residual, gamma, beta, n, c, who, params):
     return residual
 
 
+def _channel_operands(like, c, who, optional=(), **named):
+    """Per-channel float32 vectors that reach a kernel as raw pointers (a bias, BatchNorm parameters, running statistics): each a
+    CUDA tensor on `like`'s device, contiguous, 1-d, `c` long; the names in `optional` may be None.  Checked before anything is launched."""
+    for nm, t in named.items():
+        if t is None and nm in optional:
+            continue
+        req(t, F32, f"{who} {nm}", 1)
+        if t.shape[0] != c:
+            raise ValueError(f"{who} {nm}: expected ({c},), got {tuple(t.shape)}")
+        if t.device != like.device:
+            raise ValueError(f"{who} {nm}: lives on another device than the rows it is applied to")
+
+
+def _refuse_grad(t, who, name, hint):
+    """An input the node has no gradient for must not ask for one: autograd would hand back None without a word."""
+    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"{who}: no gradient is produced for {name} ({hint})")
+
+
+_RUNNING = ("running_mean", "running_var")      # the training kernels take NULL for "no update" (include/ftx.h)
+
+
 class _BatchNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, remask):
         x = req(x.contiguous(), F32, "bn x", 2)
         n, c = x.shape
         residual = _bn_operands(residual, gamma, beta, n, c, "bn", "parameter length != channels")
+        _channel_operands(x, c, "bn", optional=_RUNNING, running_mean=running_mean, running_var=running_var)    # written in place
         y = torch.empty_like(x)
         mean = _empty((c,), F32, x)
         invstd = _empty((c,), F32, x)
@@ -875,23 +903,29 @@ class _BatchNormEval(torch.autograd.Function):
         L = _lib.load()
         x = req(x.contiguous(), F32, "bn x", 2)
         n, c = x.shape
-        if residual is not None:
-            residual = req(residual.contiguous(), F32, "bn residual", 2)
+        residual = _bn_operands(residual, gamma, beta, n, c, "bn", "parameter length != channels")
+        _channel_operands(x, c, "bn", running_mean=running_mean, running_var=running_var)
         y = torch.empty_like(x)
         check(L.ftx_bn_eval_fwd(ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(eps), n, c, int(relu),
                                 ptr(y), stream()), "ftx_bn_eval_fwd")
-        ctx.save_for_backward(y, gamma, running_var)
+        # x and running_mean are read by d gamma alone: kept only for a gamma that asks (the executors and model.eval() under no_grad never do)
+        need_gamma = ctx.needs_input_grad[2]
+        ctx.save_for_backward(y, gamma, running_var, x if need_gamma else None, running_mean if need_gamma else None)
         ctx.eps, ctx.relu, ctx.has_res = float(eps), int(relu), residual is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        # Eval-mode gradients are elementwise; torch device ops (no library call needed).
-        y, gamma, running_var = ctx.saved_tensors
+        # Eval-mode gradients are elementwise (torch device ops); the parameter gradients are column sums (ftx_colsum: float64, fixed order).
+        y, gamma, running_var, x, running_mean = ctx.saved_tensors
         dy = gy * (y > 0) if ctx.relu else gy
-        scale = gamma * torch.rsqrt(running_var + ctx.eps)
+        invstd = torch.rsqrt(running_var + ctx.eps)
+        scale = gamma * invstd
         gx = dy * scale
-        return gx, (dy if ctx.has_res else None), None, None, None, None, None, None
+        sums = colsum if gy.shape[1] % 4 == 0 else (lambda t: t.sum(0))
+        ggamma = sums(dy * ((x - running_mean) * invstd)) if ctx.needs_input_grad[2] else None
+        gbeta = sums(dy) if ctx.needs_input_grad[3] else None
+        return gx, (dy if ctx.has_res else None), ggamma, gbeta, None, None, None, None
 
 
 class _ConvBNTrain(torch.autograd.Function):
@@ -909,6 +943,7 @@ class _ConvBNTrain(torch.autograd.Function):
         kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
         kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
         residual = _bn_operands(residual, gamma, beta, n_out, co, "conv_bn", "BatchNorm parameter length != output channels")
+        _channel_operands(feats, co, "conv_bn", optional=_RUNNING, running_mean=running_mean, running_var=running_var)    # written in place
         stats = _empty((2, co), F32, feats)              # row 0: batch mean, row 1: 1 / sqrt(var + eps)
         x = _empty((n_out, co), F32, feats)
         y = torch.empty_like(x)
@@ -1141,7 +1176,8 @@ class _ResampleNearest(torch.autograd.Function):
 
 
 def resample_nearest(x, size):
-    """nn.Upsample(size) (nearest) on NCHW."""
+    """nn.Upsample(size) (nearest) on NCHW.  The backward adds with float atomics: up to two target pixels per source pixel (any
+    downsample) it is exact in any order; an upsample's gradient is right to rounding, not bit-reproducible."""
     return _ResampleNearest.apply(x, size[0], size[1])
 
 
@@ -1378,10 +1414,10 @@ def _ln_forward(x, y, weight, bias, eps, y_bias=None):
     L = _lib.load()
     shape = x.shape
     c = shape[-1]
+    if y is not None and (not isinstance(y, torch.Tensor) or y.numel() != x.numel() or y.shape[-1] != c):
+        raise ValueError("add_layer_norm: x and y differ in shape")
     x2 = req(x.contiguous().view(-1, c), F32, "layer_norm x", 2)
     y2 = req(y.contiguous().view(-1, c), F32, "layer_norm y", 2) if y is not None else None
-    if y2 is not None and y2.shape != x2.shape:
-        raise ValueError("add_layer_norm: x and y differ in shape")
     for t, nm in ((weight, "weight"), (bias, "bias"), (y_bias, "y_bias")):
         if t is None and nm == "y_bias":
             continue
@@ -1438,11 +1474,7 @@ class _AddLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gs, gh):
-        s, weight, stats = ctx.saved_tensors
-        if gh is None:                                   # the normalised output was not used: only the sum's gradient passes
-            g = gs if gs is not None else torch.zeros(ctx.shape, dtype=F32, device=s.device)
-            gyb = colsum(g.reshape(-1, g.shape[-1])) if ctx.with_y_bias else None
-            return g, g, gyb, None, None, None
+        s, weight, stats = ctx.saved_tensors            # autograd hands an unused output's gradient over as zeros: gs and gh are tensors
         gx, gparams = _ln_backward(gh, gs, s, weight, stats, ctx.with_y_bias)
         gx = gx.view(ctx.shape)
         return gx, gx, (gparams[2] if ctx.with_y_bias else None), gparams[0], gparams[1], None
@@ -1542,6 +1574,7 @@ def _dense_gemm(a, w, w_kn, epi, bias=None, pre_in=None, with_pre=False, mode="b
     L = _lib.load()
     m, kr = a.shape
     n = w.shape[1] if w_kn else w.shape[0]
+    _channel_operands(a, n, "vit " + mode + " gemm", optional=("bias",), bias=bias)
     out = _empty((m, n), F32, a)
     pre = _empty((m, n), F32, a) if with_pre else None
     _log_launch("vit_gemm_" + mode, dict(m=m, n=n, k=kr, w_kn=w_kn, epi=epi), lambda: check(getattr(L, "ftx_dense_gemm_" + mode)(
@@ -1609,6 +1642,7 @@ class _VitMlp(torch.autograd.Function):
         x2 = req(x.reshape(-1, x.shape[-1]).contiguous(), F32, "vit_mlp x", 2)
         w1 = req(w1.contiguous(), F32, "vit_mlp fc1 weight", 2)
         w2 = req(w2.contiguous(), F32, "vit_mlp fc2 weight", 2)
+        _channel_operands(x2, w2.shape[0], "vit_mlp", optional=("b2",), b2=b2)      # before fc1 is launched, not between the two GEMMs
         h, pre = _dense_gemm(x2, w1, 0, EPI_BIAS_GELU, bias=b1, with_pre=True, mode=mode)
         y, _ = _dense_gemm(h, w2, 0, EPI_BIAS if b2 is not None else EPI_NONE, bias=b2, mode=mode)
         ctx.save_for_backward(x2, w1, pre, h, w2)
@@ -1667,7 +1701,9 @@ class _SampleDown(torch.autograd.Function):
         b, c, h, w = img.shape
         if c != 3 or conv_w.numel() != 9:
             raise ValueError("sample_down: the fused kernel is the 3 -> 3 channel BilinearModule of the reference")
+        w_shape = conv_w.shape          # (3, 3), or (3, 3, 1, 1) as nn.Conv2d keeps it: the gradient goes back in that shape
         conv_w = req(conv_w.contiguous().view(3, 3), F32, "sample_down conv weight", 2)
+        _channel_operands(img, 3, "sample_down", conv_b=conv_b, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
         out = _empty((b, 3, int(oh), int(ow)), F32, img)
         saved = torch.empty((33,), dtype=torch.float64, device=img.device)
         ws_bytes = int(L.ftx_sample_down_workspace_bytes())
@@ -1676,7 +1712,7 @@ class _SampleDown(torch.autograd.Function):
                                     ptr(running_var), float(momentum), float(eps), int(bool(training)), ptr(out), ptr(saved), ptr(ws), ws_bytes, stream()),
               "ftx_sample_down_fwd")
         ctx.save_for_backward(img, conv_w, conv_b, gamma, saved)
-        ctx.training = bool(training)
+        ctx.training, ctx.w_shape = bool(training), w_shape
         ctx.dims = (b, h, w, int(oh), int(ow))
         return out
 
@@ -1694,11 +1730,13 @@ class _SampleDown(torch.autograd.Function):
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=go.device)
         check(L.ftx_sample_down_bwd(ptr(img), ptr(go), b, h, w, oh, ow, ptr(conv_w), ptr(conv_b), ptr(gamma), ptr(saved), ptr(gw), ptr(gb), ptr(gg),
                                     ptr(gbeta), ptr(ws), ws_bytes, stream()), "ftx_sample_down_bwd")
-        return None, gw, gb, gg, gbeta, None, None, None, None, None, None, None
+        return None, gw.view(ctx.w_shape), gb, gg, gbeta, None, None, None, None, None, None, None
 
 
 def sample_down(img, conv_w, conv_b, gamma, beta, running_mean, running_var, momentum, eps, training, size):
-    """Conv1x1(3->3) + ReLU + BatchNorm2d + nearest pick, fused (image_models_billinear.py:8-24)."""
+    """Conv1x1(3->3) + ReLU + BatchNorm2d + nearest pick, fused (image_models_billinear.py:8-24).  Differentiable in the convolution's
+    and the BatchNorm's parameters; img is the input image, and an img that asks for a gradient is refused."""
+    _refuse_grad(img, "sample_down", "img", "the fused kernel is for the input image")
     return _SampleDown.apply(img, conv_w, conv_b, gamma, beta, running_mean, running_var, momentum, eps, training, size[0], size[1])
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import loss_metric_ref as R
+from tests.nolaunch import NoLaunch as _NoLaunch
 
 pytestmark = pytest.mark.gpu
 
@@ -199,16 +200,6 @@ def test_c_abi_refuses_bad_sizes_before_any_launch(ftx_lib):
         assert call(nn, cc, ws_bytes) != 0, (nn, cc, ws_bytes)
         assert text in L.ftx_last_error(), (nn, cc, ws_bytes)
     torch.cuda.synchronize()
-
-
-class _NoLaunch:
-    """Stands in for libftx: any launch is a test failure, so a bad operand can never reach a kernel."""
-
-    def ftx_fusion_loss_workspace_bytes(self):
-        return 1 << 14
-
-    def ftx_fusion_loss_mix(self, *args):
-        raise AssertionError("launched")
 
 
 BAD_OPERANDS = ("cw_float64", "cw_cpu", "cw_short", "cw_long", "cw_2d", "cw_strided", "conf3d_int32", "conf2d_int32", "conf3d_small",

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import loss_metric_ref as R
+from tests.nolaunch import NoLaunch as _NoLaunch
 from tests.seg_loss_ref import seg_oracle
 
 pytestmark = pytest.mark.gpu
@@ -243,16 +244,6 @@ def test_c_abi_refuses_bad_sizes_before_any_launch(ftx_lib):
     assert b"null pointer" in L.ftx_last_error()
     torch.cuda.synchronize()
     assert not loss.any() and not grad.any()
-
-
-class _NoLaunch:
-    """Stands in for libftx: any launch is a test failure, so a bad operand can never reach a kernel."""
-
-    def ftx_seg_loss_workspace_bytes(self):
-        return 1 << 14
-
-    def ftx_seg_loss(self, *args):
-        raise AssertionError("launched")
 
 
 BAD_OPERANDS = ("cw_float64", "cw_cpu", "cw_short", "cw_long", "cw_2d", "cw_strided", "conf_int32", "conf_small", "conf_flat", "conf_cpu",
