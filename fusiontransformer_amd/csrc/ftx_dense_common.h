@@ -1,9 +1,16 @@
-// What the dense MFMA GEMM families of the ViT trunk's Linears share (ftx_dense_bf16.hip, ftx_dense_split.hip): the fp32 epilogue of the
-// GEMM kernels, the tile and split rules, and the host layer behind the extern "C" entries.  A family brings its kernels and a small
-// description (DenseBf16, DenseSplit): the entry names that front its messages, and two launch hooks.  The pieces that need a single
-// definition (the rules, dense_wgrad_reduce_kernel, the plain entries) are defined in ftx_dense_bf16.hip.
+// What the dense MFMA GEMM families of the ViT trunk's Linears share (ftx_dense_bf16.hip, ftx_dense_split.hip): everything but the way an
+// fp32 operand becomes bf16 pieces and what is done with the pieces.  Here are the fp32 epilogue, the A-addressing forms, the tile and
+// split rules, the one GEMM kernel and the one weight-gradient kernel (dense_gemm_kernel, dense_wgrad_kernel) and the host layer behind
+// the extern "C" entries.  A family brings its entries and a description P (DenseBf16, DenseSplit), which says, and alone says:
+//   P::NP, P::BK, P::STRIDE   bf16 images per operand, reduction elements staged per step, bf16 per LDS row, each with its reason
+//   P::MIN_BLOCKS             the blocks per CU the kernels' registers are held to
+//   P::pieces(float4)         the one place an operand is rounded or split: NP bf16x4
+//   P::PROD, P::sum           the piece products of a 16-wide k-step, in order, each with its accumulator; the accumulators' one fp32 sum
+//   P::gemm_name, ...         the entries' names, as they front every message
+// The kernels do not ask which family they serve.  What needs a single definition (the rules, dense_wgrad_reduce_kernel,
+// dense_tokens_head_kernel, the plain entries) is defined in ftx_dense_common.hip.
 //
-// Where the rows of A live and what happens to a finished sum is a policy of the GEMM kernels (DenseRows, DensePatches, DenseTapRows
+// Where the rows of A live and what happens to a finished sum is a policy of the GEMM kernel (DenseRows, DensePatches, DenseTapRows
 // below): the tile rule, the staging, the MFMA order and the reduction order do not depend on it, so a form returns the bits of the
 // plain entry run on a materialised copy of its A.
 #pragma once
@@ -135,10 +142,318 @@ int dense_tile_entry(const char *me, int32_t form, int64_t m, int32_t n, int32_t
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------------------------------
-// host: the entries, generic over a family F:
-//   F::gemm_name, F::wgrad_name, F::patch_name, F::tap_name   the entries' names, as they front every message
-//   F::gemm<MI, NI, EPI, WKN>(grid, st, form, args)   launches the GEMM kernel of that instantiation on an A-addressing form
-//   F::wgrad(grid, st, G, X, M, N, K, len, part, dW)  launches the weight-gradient kernel
+// device: the two kernels, generic over a description P (the header comment lists its members), on v_mfma_f32_32x32x16_bf16.
+//
+// Operand maps (ftx_spconv_bf16.hip, cdna_hip_programming.md section 3): lane (r = lane & 31, h = lane >> 5) holds row r, k = 8h + j of
+// both fragments of a 16-wide k-step, read with one ds_read_b128 from a bf16 LDS image whose rows are k-contiguous.  mfma(F1, F2)
+// leaves C[row of F1][row of F2] with F2's row on the lane and four consecutive F1 rows in accumulator registers 4q..4q+3
+// ((g&3) + 8(g>>2) + 4h), so every store below is a float4 along the output row.
+// ---------------------------------------------------------------------------------------
+// The staging geometry of a description: the block's 256 threads move one float4 each per pass.
+template <class P>
+struct DenseStage {
+  static_assert(kDenseGranule % P::BK == 0, "the entry admits every multiple of kDenseGranule as the reduction");
+  static constexpr int F4 = P::BK / 4;      // float4 per staged row
+  static constexpr int ROWS = 256 / F4;     // rows per pass: thread -> (row tid / F4, float4 tid % F4)
+  static constexpr int passes(int rows) { return rows / ROWS; }   // float4 per thread and step of an operand of that many rows
+  // a [reduction][channel] operand stored transposed: item = (reduction pair, channel float4), two float4 per item
+  static constexpr int pair_items(int channels) { return (P::BK / 2) * (channels / 4) / 256; }   // channels * BK / 2048
+};
+
+// One float4 of a staged row to offset o of every image: the pieces of four consecutive reduction elements.
+template <class P>
+__device__ inline void dense_store_row(__bf16 *img, int img_len, int o, float4 v) {
+  const typename P::Pieces4 s = P::pieces(v);
+#pragma unroll
+  for (int c = 0; c < P::NP; ++c) *(bf16x4 *)&img[c * img_len + o] = s.p[c];
+}
+
+// Two float4 of reduction rows 2kp, 2kp+1 at channels ch .. ch+3, stored TRANSPOSED into image rows ch .. ch+3 as packed pairs.
+template <class P>
+__device__ inline void dense_store_pairs(__bf16 *img, int img_len, int ch, int kp, float4 v0, float4 v1) {
+  const typename P::Pieces4 x0 = P::pieces(v0), x1 = P::pieces(v1);
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int c = 0; c < P::NP; ++c) *(bf16x2 *)&img[c * img_len + (ch + e) * P::STRIDE + 2 * kp] = (bf16x2){x0.p[c][e], x1.p[c][e]};
+}
+
+// Registers 4q .. 4q+3 of the accumulators of one sub-tile as one finished float4: P::sum, the one add in front of the epilogue.
+template <class P>
+__device__ inline float4 dense_sum4(const f32x16 (&acc)[P::NACC], int q) {
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float a[P::NACC];
+#pragma unroll
+    for (int c = 0; c < P::NACC; ++c) a[c] = acc[c][4 * q + e];
+    v[e] = P::sum(a);
+  }
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// ---------------------------------------------------------------------------------------
+// out[m][n] = epilogue( sum_k A[m][k] B[k][n] ) over the pieces of P,  B = W^T with W stored [N][K] (WKN = false: nn.Linear's weight,
+// the forward) or B = W stored [K][N] (WKN = true: the data gradient dX = dY W).
+//
+// Block = 4 waves as 2 x 2, tile (64 MI) x (64 NI); wave (wm, wn) owns MI x NI 32 x 32 sub-tiles.  NP LDS images per operand,
+// [piece][row][k] bf16; the next step's global loads are issued before this step's MFMAs (register staging, the pairs_gemm_bf16 pipeline).
+// Rows past M and columns past N load clamped, always-valid addresses and are never stored.
+// AF says where A's rows live and what the epilogue does: DenseRows is the (M, K) matrix with dense_epilogue<EPI>, DensePatches the
+// patch embedding's unfold of an image, DenseTapRows the token buffer behind its leading rows.  Nothing else here depends on it, so
+// every form sums the same products in the same order.
+// ---------------------------------------------------------------------------------------
+template <class P, int MI, int NI, int EPI, bool WKN, class AF>
+__global__ __launch_bounds__(256, P::MIN_BLOCKS) void dense_gemm_kernel(const AF af, const float *__restrict__ W, const float *__restrict__ bias,
+                                                                        const float *__restrict__ pre_in, int64_t M, int N, int K,
+                                                                        float *__restrict__ out, float *__restrict__ pre_out) {
+  using S = DenseStage<P>;
+  constexpr int BM = 64 * MI, BN = 64 * NI;
+  constexpr int AP = S::passes(BM);   // float4 of A per thread and step
+  constexpr int BP = S::passes(BN);   // the same count for B in either orientation
+  constexpr int BQ = S::pair_items(BN);
+  static_assert(BP == 2 * BQ, "either orientation of W is the same number of float4");
+  constexpr int AIMG = BM * P::STRIDE, BIMG = BN * P::STRIDE;
+  __shared__ __attribute__((aligned(16))) __bf16 As[P::NP * AIMG];   // [piece][m][k]
+  __shared__ __attribute__((aligned(16))) __bf16 Bs[P::NP * BIMG];   // [piece][n][k]
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int64_t m0 = (int64_t)blockIdx.y * BM;
+  const int n0 = blockIdx.x * BN;
+
+  // row-major staging (A, and W stored [N][K]): pass p covers rows ROWS p .. ROWS p + ROWS - 1
+  const int srow = tid / S::F4, sk4 = (tid % S::F4) * 4;
+  const float *arow[AP];
+#pragma unroll
+  for (int p = 0; p < AP; ++p) {
+    int64_t r = m0 + p * S::ROWS + srow;
+    arow[p] = af.row(r < M ? r : M - 1);
+  }
+  const float *brow[BP];
+  // WKN: item e = (k pair kp, column float4 n4); two float4 per item (rows 2kp, 2kp+1), stored as packed k pairs
+  int bkp[WKN ? BQ : 1], bn4[WKN ? BQ : 1];
+  if constexpr (!WKN) {
+#pragma unroll
+    for (int p = 0; p < BP; ++p) {
+      int r = n0 + p * S::ROWS + srow;
+      brow[p] = W + (int64_t)(r < N ? r : N - 1) * K + sk4;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < BQ; ++q) {
+      const int e = q * 256 + tid;
+      bn4[q] = (e % (BN / 4)) * 4;
+      bkp[q] = e / (BN / 4);
+      int n = n0 + bn4[q];
+      brow[2 * q] = W + (int64_t)(2 * bkp[q]) * N + (n + 4 <= N ? n : N - 4);
+      brow[2 * q + 1] = brow[2 * q] + N;
+    }
+  }
+
+  f32x16 acc[MI][NI][P::NACC];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+      for (int c = 0; c < P::NACC; ++c)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[i][j][c][g] = 0.f;
+
+  float4 ra[AP], rb[BP];
+  auto load_step = [&](int c0) {
+    const int64_t ak = af.koff(c0 + sk4);   // where the form keeps reduction index c0 + sk4 of a row
+#pragma unroll
+    for (int p = 0; p < AP; ++p) ra[p] = *(const float4 *)(arow[p] + ak);
+    if constexpr (!WKN) {
+#pragma unroll
+      for (int p = 0; p < BP; ++p) rb[p] = *(const float4 *)(brow[p] + c0);
+    } else {
+#pragma unroll
+      for (int p = 0; p < BP; ++p) rb[p] = *(const float4 *)(brow[p] + (int64_t)c0 * N);
+    }
+  };
+  // the ONE place the operands become bf16 (P::pieces): fp32 registers -> the LDS images
+  auto store_step = [&]() {
+#pragma unroll
+    for (int p = 0; p < AP; ++p) dense_store_row<P>(As, AIMG, (p * S::ROWS + srow) * P::STRIDE + sk4, ra[p]);
+    if constexpr (!WKN) {
+#pragma unroll
+      for (int p = 0; p < BP; ++p) dense_store_row<P>(Bs, BIMG, (p * S::ROWS + srow) * P::STRIDE + sk4, rb[p]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < BQ; ++q) dense_store_pairs<P>(Bs, BIMG, bn4[q], bkp[q], rb[2 * q], rb[2 * q + 1]);
+    }
+  };
+
+  const __bf16 *ap = &As[(wm * 32 * MI + l31) * P::STRIDE + 8 * half];
+  const __bf16 *bp = &Bs[(wn * 32 * NI + l31) * P::STRIDE + 8 * half];
+  load_step(0);
+  for (int c0 = 0; c0 < K; c0 += P::BK) {
+    store_step();
+    __syncthreads();
+    if (c0 + P::BK < K) load_step(c0 + P::BK);   // the next step's global loads fly under this step's MFMAs
+#pragma unroll
+    for (int s = 0; s < P::BK / 16; ++s) {
+      bf16x8 af[P::NP][MI], bf[P::NP][NI];
+#pragma unroll
+      for (int c = 0; c < P::NP; ++c) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i) af[c][i] = *(const bf16x8 *)(ap + c * AIMG + i * 32 * P::STRIDE + 16 * s);
+#pragma unroll
+        for (int j = 0; j < NI; ++j) bf[c][j] = *(const bf16x8 *)(bp + c * BIMG + j * 32 * P::STRIDE + 16 * s);
+      }
+      // P::PROD[t] = (W piece, A piece, accumulator).  rows: n, columns (lanes): m.  The MI x NI sub-tiles between two uses of one
+      // accumulator hide the MFMA's latency.
+#pragma unroll
+      for (int t = 0; t < P::NPROD; ++t)
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+          for (int j = 0; j < NI; ++j)
+            acc[i][j][P::PROD[t][2]] = mfma_bf16(bf[P::PROD[t][0]][j], af[P::PROD[t][1]][i], acc[i][j][P::PROD[t][2]]);
+    }
+    __syncthreads();
+  }
+
+  // lane (l31, half) of sub-tile (i, j): output row m, columns n .. n+3 in registers 4q .. 4q+3
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int64_t m = m0 + wm * 32 * MI + i * 32 + l31;
+    if (m >= M) continue;
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + wn * 32 * NI + j * 32 + 8 * q + 4 * half;
+        if (n >= N) continue;
+        af.template store<EPI>(dense_sum4<P>(acc[i][j], q), m, n, N, bias, pre_in, out, pre_out);
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// weight gradient: dW[n][k] = sum_m G[m][n] X[m][k] over the pieces of P     (G = dY [M][N], X [M][K], both row-major over the reduction
+// index m)
+//
+// Block = (128-column tile of k, 128-row tile of n, split s of the rows); 4 waves as 2 x 2, each 64 x 64.  Each step stages P::BK rows:
+// float4 loads along the channels, stored TRANSPOSED as m-contiguous bf16 images [piece][channel][m] with two rows packed per 32-bit LDS
+// write (the register stage of pairs_wgrad_bf16_kernel).  Rows past the split are zeroed on the block-uniform last step.
+// A split count of 1 writes dW directly; otherwise each split writes its own (N x K) partial and dense_wgrad_reduce_kernel adds them.
+// ---------------------------------------------------------------------------------------
+template <class P>
+__global__ __launch_bounds__(256, P::MIN_BLOCKS) void dense_wgrad_kernel(const float *__restrict__ G, const float *__restrict__ X, int64_t M, int N,
+                                                                         int K, int64_t split_len, float *__restrict__ part,
+                                                                         float *__restrict__ dW) {
+  constexpr int T = kDenseDwTile;
+  constexpr int ITEMS = DenseStage<P>::pair_items(T);   // (row pair, float4) items per thread and operand
+  constexpr int IMG = T * P::STRIDE;
+  __shared__ __attribute__((aligned(16))) __bf16 Gt[P::NP * IMG];   // [piece][n][m]
+  __shared__ __attribute__((aligned(16))) __bf16 Xt[P::NP * IMG];   // [piece][k][m]
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int wm = wave & 1, wn = wave >> 1;   // wm: k half, wn: n half
+  const int k0 = blockIdx.x * T, n0 = blockIdx.y * T;
+  const int64_t lo = (int64_t)blockIdx.z * split_len;
+  const int64_t hi = lo + split_len < M ? lo + split_len : M;
+
+  int rp[ITEMS], c4[ITEMS], gcol[ITEMS], xcol[ITEMS];
+#pragma unroll
+  for (int q = 0; q < ITEMS; ++q) {
+    const int e = q * 256 + tid;
+    c4[q] = (e % (T / 4)) * 4;
+    rp[q] = e / (T / 4);
+    gcol[q] = n0 + c4[q] + 4 <= N ? n0 + c4[q] : N - 4;   // clamped columns reach only image rows that are never stored
+    xcol[q] = k0 + c4[q] + 4 <= K ? k0 + c4[q] : K - 4;
+  }
+
+  f32x16 acc[2][2][P::NACC];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int c = 0; c < P::NACC; ++c)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[i][j][c][g] = 0.f;
+
+  float4 rg[ITEMS][2], rx[ITEMS][2];
+  auto load_step = [&](int64_t r0) {
+#pragma unroll
+    for (int q = 0; q < ITEMS; ++q)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        int64_t r = r0 + 2 * rp[q] + h;
+        r = r < M ? r : M - 1;
+        rg[q][h] = *(const float4 *)&G[r * N + gcol[q]];
+        rx[q][h] = *(const float4 *)&X[r * K + xcol[q]];
+      }
+  };
+  auto store_step = [&](int64_t r0) {
+    if (r0 + P::BK > hi) {   // block-uniform: the split's last step
+#pragma unroll
+      for (int q = 0; q < ITEMS; ++q)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          if (r0 + 2 * rp[q] + h >= hi) rg[q][h] = rx[q][h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // the ONE place the operands become bf16 (P::pieces)
+#pragma unroll
+    for (int q = 0; q < ITEMS; ++q) {
+      dense_store_pairs<P>(Gt, IMG, c4[q], rp[q], rg[q][0], rg[q][1]);
+      dense_store_pairs<P>(Xt, IMG, c4[q], rp[q], rx[q][0], rx[q][1]);
+    }
+  };
+
+  const __bf16 *xp = &Xt[(wm * 64 + l31) * P::STRIDE + 8 * half];
+  const __bf16 *gp = &Gt[(wn * 64 + l31) * P::STRIDE + 8 * half];
+  load_step(lo);
+  for (int64_t r0 = lo; r0 < hi; r0 += P::BK) {
+    store_step(r0);
+    __syncthreads();
+    if (r0 + P::BK < hi) load_step(r0 + P::BK);
+#pragma unroll
+    for (int s = 0; s < P::BK / 16; ++s) {
+      bf16x8 xf[P::NP][2], gf[P::NP][2];
+#pragma unroll
+      for (int c = 0; c < P::NP; ++c) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) xf[c][i] = *(const bf16x8 *)(xp + c * IMG + i * 32 * P::STRIDE + 16 * s);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) gf[c][j] = *(const bf16x8 *)(gp + c * IMG + j * 32 * P::STRIDE + 16 * s);
+      }
+      // P::PROD[t] = (X piece, G piece, accumulator): the GEMM's list.  rows: k, columns (lanes): n
+#pragma unroll
+      for (int t = 0; t < P::NPROD; ++t)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[i][j][P::PROD[t][2]] = mfma_bf16(xf[P::PROD[t][0]][i], gf[P::PROD[t][1]][j], acc[i][j][P::PROD[t][2]]);
+    }
+    __syncthreads();
+  }
+
+  float *dst = gridDim.z == 1 ? dW : part + (int64_t)blockIdx.z * N * K;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = n0 + wn * 64 + j * 32 + l31;
+    if (n >= N) continue;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = k0 + wm * 64 + i * 32 + 8 * q + 4 * half;
+        if (k < K) *(float4 *)&dst[(int64_t)n * K + k] = dense_sum4<P>(acc[i][j], q);
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// host: the entries, generic over a family F: its description (above) and the names of its entries.  Every launch is 256 threads.
 // ---------------------------------------------------------------------------------------
 struct DenseGemmArgs {
   const float *A, *W, *bias, *pre_in;
@@ -147,14 +462,19 @@ struct DenseGemmArgs {
   float *out, *pre_out;
 };
 
+template <class F, int MI, int NI, int EPI, bool WKN, class AF>
+void dense_launch(dim3 grid, hipStream_t st, const AF &af, const DenseGemmArgs &a) {
+  dense_gemm_kernel<F, MI, NI, EPI, WKN, AF><<<grid, 256, 0, st>>>(af, a.W, a.bias, a.pre_in, a.M, a.N, a.K, a.out, a.pre_out);
+}
+
 template <class F, int MI, int NI, bool WKN>
 void dense_launch_epi(int epi, dim3 grid, hipStream_t st, const DenseGemmArgs &a) {
   const DenseRows rows = {a.A, a.K};
   switch (epi) {
-    case FTX_EPI_NONE: F::template gemm<MI, NI, FTX_EPI_NONE, WKN>(grid, st, rows, a); break;
-    case FTX_EPI_BIAS: F::template gemm<MI, NI, FTX_EPI_BIAS, WKN>(grid, st, rows, a); break;
-    case FTX_EPI_BIAS_GELU: F::template gemm<MI, NI, FTX_EPI_BIAS_GELU, WKN>(grid, st, rows, a); break;
-    default: F::template gemm<MI, NI, FTX_EPI_DGELU, WKN>(grid, st, rows, a); break;
+    case FTX_EPI_NONE: dense_launch<F, MI, NI, FTX_EPI_NONE, WKN>(grid, st, rows, a); break;
+    case FTX_EPI_BIAS: dense_launch<F, MI, NI, FTX_EPI_BIAS, WKN>(grid, st, rows, a); break;
+    case FTX_EPI_BIAS_GELU: dense_launch<F, MI, NI, FTX_EPI_BIAS_GELU, WKN>(grid, st, rows, a); break;
+    default: dense_launch<F, MI, NI, FTX_EPI_DGELU, WKN>(grid, st, rows, a); break;
   }
 }
 
@@ -198,9 +518,9 @@ void dense_launch_form(const Form &form, const DenseGemmArgs &a, hipStream_t st)
   int mi, ni;
   dense_gemm_tile(a.M, a.N, &mi, &ni);
   const dim3 grid((unsigned)ceil_div(a.N, 64 * ni), (unsigned)ceil_div(a.M, 64 * mi));
-  if (mi == 2) F::template gemm<2, 2, FTX_EPI_BIAS, false>(grid, st, form, a);
-  else if (ni == 2) F::template gemm<1, 2, FTX_EPI_BIAS, false>(grid, st, form, a);
-  else F::template gemm<1, 1, FTX_EPI_BIAS, false>(grid, st, form, a);
+  if (mi == 2) dense_launch<F, 2, 2, FTX_EPI_BIAS, false>(grid, st, form, a);
+  else if (ni == 2) dense_launch<F, 1, 2, FTX_EPI_BIAS, false>(grid, st, form, a);
+  else dense_launch<F, 1, 1, FTX_EPI_BIAS, false>(grid, st, form, a);
 }
 
 // tokens[f][0] = cls + pos[0], tokens[f][1] = dist + pos[1] (T0 = 2): the rows in front of the patches (dense_tokens_head_kernel)
@@ -282,7 +602,7 @@ int dense_wgrad_entry(const float *G, const float *X, int64_t m, int32_t n, int3
   }
   float *part = (float *)workspace;
   const dim3 grid((unsigned)ceil_div(k, kDenseDwTile), (unsigned)ceil_div(n, kDenseDwTile), (unsigned)splits);
-  F::wgrad(grid, st, G, X, m, n, k, len, part, dW);
+  dense_wgrad_kernel<F><<<grid, 256, 0, st>>>(G, X, m, n, k, len, part, dW);
   if (splits > 1) dense_wgrad_reduce(part, splits, (int64_t)n * k / 4, dW, st);
   return check_launch(me);
 }

@@ -401,7 +401,8 @@ int ftx_attn_bwd_tiled(const float *qkv, const float *out, const float *grad_out
 int ftx_attn_fwd_bf16(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw, int32_t split, void *stream);
 int ftx_attn_bwd_bf16(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split, void *stream);
 
-/* ---- bf16-operand ViT Linears (timm Mlp / Attention qkv, proj, fc1, fc2: models/transformers.py:36-55) (csrc/ftx_dense_bf16.hip) ----
+/* ---- bf16-operand ViT Linears (timm Mlp / Attention qkv, proj, fc1, fc2: models/transformers.py:36-55) (csrc/ftx_dense_bf16.hip: the
+ *      family's description and entries; the kernels, shared with the split entries below: csrc/ftx_dense_common.h) ----
  * Precision contract: the MFMA operands -- A and W of the GEMM, dY and X of the weight gradient -- are rounded to bf16
  * (round-to-nearest-even) from their stored fp32 values as they are staged; nothing else is rounded.  Accumulation is fp32
  * (v_mfma_f32_32x32x16_bf16), and all storage stays fp32: A, W, bias, out, pre_in / pre_out and dW.  Bias, GELU and the GELU
@@ -428,7 +429,8 @@ int ftx_dense_wgrad_bf16(const float *dY, const float *X, int64_t m, int32_t n, 
  * dW (n, k) over m rows) picks.  Launches nothing. */
 int ftx_dense_bf16_tile(int32_t form, int64_t m, int32_t n, int32_t k, int32_t *tile_m_host, int32_t *tile_n_host, int32_t *split_host);
 
-/* ---- fp32-accurate ViT Linears on the bf16 MFMA: three-piece operand split (csrc/ftx_dense_split.hip) ----
+/* ---- fp32-accurate ViT Linears on the bf16 MFMA: three-piece operand split (csrc/ftx_dense_split.hip: the family's
+ *      description and entries; the kernels: csrc/ftx_dense_common.h) ----
  * The same GEMM, epilogues, weight gradient, argument rules, error texts and m == 0 behaviour as the bf16-operand entries above, for
  * the fp32 model: no operand bit is discarded below the stated range, and the result is fp32-class (measured: DESIGN section 5).
  * Precision contract:
@@ -705,7 +707,7 @@ int ftx_spvcnn_index_maps(const float *coords, int64_t n, float init_res, float 
 int ftx_spvcnn_index_pairs(int64_t n, int32_t c_in, const int32_t *level_off_host, int32_t with_backward_segments, const int32_t *pair_counts_host, void *arena_a, void *arena_b, size_t arena_b_bytes, void *arena_c, size_t arena_c_bytes, int64_t *rows_host, void *maps_host, void *pvs_host, const float **x0, void *stream);
 
 /* ---- the ViT image branch in eval mode: patch embedding, tap stems and the trunk executor (models/transformers.py:16-45,90-100,
- *      models/image_models_billinear.py:8-24,88-126) (csrc/ftx_dense_common.h, csrc/ftx_exec_vit.hip) ----
+ *      models/image_models_billinear.py:8-24,88-126) (csrc/ftx_dense_common.h, csrc/ftx_dense_common.hip, csrc/ftx_exec_vit.hip) ----
  * Two A-addressing forms of the dense GEMM families above.  The tile rule, the piece split, the accumulator order and the reduction
  * order are those of ftx_dense_gemm_split / ftx_dense_gemm_bf16 (the precision contracts above hold unchanged), so each form returns
  * the bits of that entry run with FTX_EPI_BIAS on a materialised copy of its A, followed by its own epilogue.
