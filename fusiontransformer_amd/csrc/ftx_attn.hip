@@ -745,10 +745,7 @@ static int attn_bwd_entry(const float *qkv, const float *out, const float *grad_
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE(qkv && out && grad_out && lse && grad_qkv && workspace, "%s: null pointer", me);
   FTX_REQUIRE(attn_tiling_built(qw, split), "%s%s: (%d, %d) is not a built tiling", me, F::tiled, qw, split);
-  if (workspace_bytes < ftx_attn_bwd_workspace_bytes(b, t, h)) {
-    set_error("%s: workspace %zu < required %zu", me, workspace_bytes, ftx_attn_bwd_workspace_bytes(b, t, h));
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < ftx_attn_bwd_workspace_bytes(b, t, h)) return workspace_short(me, workspace_bytes, ftx_attn_bwd_workspace_bytes(b, t, h));
   hipStream_t st = (hipStream_t)stream;
   float *delta = (float *)workspace;
   const int64_t rows = (int64_t)b * t * h;

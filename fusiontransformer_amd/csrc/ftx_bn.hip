@@ -3,106 +3,11 @@
 // (models/spvcnn.py:30-31,71-79,100-102,164-180).  HBM-bound: x is read twice in the
 // forward (statistics, apply) and the output written once; statistics accumulate in
 // float64 so mean/var do not depend on how rows are split over workgroups.
-#include <cstdlib>
-#include <map>
-#include <mutex>
-#include <utility>
 #include "ftx_common.h"
 #include "ftx_bn_eval_op.h"
 #include "ftx_lastblock.h"
 
 using namespace ftx;
-
-// ---- per-(device, stream) ticket buffer (ftx_lastblock.h) ------------------------------------------------------------------------
-// The statistics kernels hand their column totals to "the last block to finish"; the tickets and the group rows live in a small
-// buffer that belongs to ONE stream of ONE device (launches of a stream are serialised, the last user of a counter puts it back to
-// zero).  The CALLER can own it: ftx_stream_scratch_bytes() / ftx_stream_scratch_attach(stream, ptr, bytes) hand the library a buffer
-// of the caller's, ftx_stream_scratch_reset(stream) clears the tickets (after a kernel died mid-flight), ftx_stream_scratch_release
-// gives it back.  Only a stream nobody attached a buffer to gets a library allocation, at first use (freed by release).
-namespace ftx {
-namespace {
-struct ScratchEntry {
-  StreamScratch sc;
-  void *owned;      // non-null: allocated here (hipMalloc), freed by release
-};
-std::mutex g_scratch_mu;
-std::map<std::pair<int, hipStream_t>, ScratchEntry> g_scratch;
-
-constexpr size_t scratch_counter_bytes() { return 512 * ((sizeof(uint32_t) * (1 + LB_MAX_GROUPS) + 511) / 512); }
-constexpr size_t scratch_group_bytes() { return sizeof(double) * (size_t)LB_MAX_GROUPS * 2 * LB_MAX_COLS; }
-
-int current_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) (void)hipGetLastError();
-  return dev;
-}
-}  // namespace
-
-StreamScratch stream_scratch(hipStream_t st) {
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  const auto key = std::make_pair(current_device(), st);     // the legacy stream has the same handle on every device
-  auto it = g_scratch.find(key);
-  if (it != g_scratch.end()) return it->second.sc;
-  StreamScratch sc{nullptr, nullptr};
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-    set_error("stream_scratch: first use of a stream inside a capture (attach a buffer, or run the op once on that stream, before capturing)");
-    return sc;
-  }
-  (void)hipGetLastError();
-  char *base = nullptr;
-  if (hipMalloc((void **)&base, scratch_counter_bytes() + scratch_group_bytes()) != hipSuccess ||
-      hipMemsetAsync(base, 0, scratch_counter_bytes(), st) != hipSuccess) {
-    set_error("stream_scratch: cannot allocate the per-stream ticket buffer (%s)", hipGetErrorString(hipGetLastError()));
-    if (base) (void)hipFree(base);
-    return sc;
-  }
-  sc.counters = (uint32_t *)base;
-  sc.gpart = (double *)(base + scratch_counter_bytes());
-  g_scratch[key] = ScratchEntry{sc, base};
-  return sc;
-}
-}  // namespace ftx
-
-extern "C" size_t ftx_stream_scratch_bytes(void) { return scratch_counter_bytes() + scratch_group_bytes(); }
-
-extern "C" int ftx_stream_scratch_attach(void *stream, void *buffer, size_t bytes) {
-  FTX_REQUIRE(buffer && ((uintptr_t)buffer & 255) == 0, "ftx_stream_scratch_attach: the buffer must be non-null and 256-byte aligned");
-  FTX_REQUIRE(bytes >= ftx_stream_scratch_bytes(), "ftx_stream_scratch_attach: %zu bytes < ftx_stream_scratch_bytes() = %zu", bytes, ftx_stream_scratch_bytes());
-  hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  const auto key = std::make_pair(current_device(), st);
-  if (hipMemsetAsync(buffer, 0, scratch_counter_bytes(), st) != hipSuccess) return check_launch("ftx_stream_scratch_attach memset");
-  auto it = g_scratch.find(key);
-  if (it != g_scratch.end() && it->second.owned) {
-    // kernels already queued on the stream may still use the library's buffer: free it when they are done
-    if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-    (void)hipFree(it->second.owned);
-  }
-  StreamScratch sc{(uint32_t *)buffer, (double *)((char *)buffer + scratch_counter_bytes())};
-  g_scratch[key] = ScratchEntry{sc, nullptr};
-  return FTX_OK;
-}
-
-extern "C" int ftx_stream_scratch_reset(void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  auto it = g_scratch.find(std::make_pair(current_device(), st));
-  if (it == g_scratch.end()) return FTX_OK;      // nothing to clear
-  if (hipMemsetAsync(it->second.sc.counters, 0, scratch_counter_bytes(), st) != hipSuccess) return check_launch("ftx_stream_scratch_reset");
-  return FTX_OK;
-}
-
-extern "C" int ftx_stream_scratch_release(void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  auto it = g_scratch.find(std::make_pair(current_device(), st));
-  if (it == g_scratch.end()) return FTX_OK;
-  if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();      // the buffer goes back to its owner: nothing may still use it
-  if (it->second.owned) (void)hipFree(it->second.owned);
-  g_scratch.erase(it);
-  return FTX_OK;
-}
 
 // Grid of the statistics passes.  They stream 1-3 row matrices once and are bound by loads in flight, not by bytes: at 128 rows per
 // block the 81k-row level ran 635 blocks (2.5 per CU) and reached 1.7 TB/s.  48 rows per block, at most 2048 blocks: constants, because
@@ -155,8 +60,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float *__restrict
                                                          double *part, StreamScratch sc) {
   // part: gridDim.x rows [2][c], then the totals row [2][c] written by the last block to finish (ftx_lastblock.h)
   extern __shared__ double sh[];  // [2][RL][c]
-  const int c4 = c >> 2;
-  const int RL = 256 / c4 > 0 ? 256 / c4 : 1;
+  const auto [c4, RL] = row_lanes(c);
   const int tid = threadIdx.x;
   const int cg = tid % c4, rl = tid / c4;
   const int64_t rows_per_block = ceil_div(n, (int64_t)gridDim.x);
@@ -194,21 +98,8 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float *__restrict
       const int64_t o0 = r * c + cg * 4;
       accumulate(*(const float4 *)&x[o0], gy ? *(const float4 *)&gy[o0] : zero4, y ? *(const float4 *)&y[o0] : zero4);
     }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      sh[(0 * RL + rl) * c + cg * 4 + v] = s0[v];
-      sh[(1 * RL + rl) * c + cg * 4 + v] = s1[v];
-    }
   }
-  __syncthreads();
-  for (int j = tid; j < 2 * c; j += 256) {
-    int which = j / c, col = j - which * c;
-    double s = 0;
-    for (int q = 0; q < RL; ++q) s += sh[(which * RL + q) * c + col];
-    lb_store(&part[((int64_t)blockIdx.x * 2 + which) * c + col], s);
-  }
-  __syncthreads();   // sh is free again: 2 * RL * c = 2048 doubles >= 256 + 2c for c <= 512
-  last_block_totals(part, (int)gridDim.x, c, sc, sh, StoreTotals{part + (int64_t)gridDim.x * 2 * c, c});
+  colstats_block_tail(s0, s1, rl, cg, RL, c, sh, part, sc);
 }
 
 // mean / invstd of a column from its two totals, in float64 (every apply block computes the same values; block 0 also stores them
@@ -229,8 +120,7 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float *__restri
                                                            float momentum, float *__restrict__ running_mean, float *__restrict__ running_var,
                                                            float *__restrict__ save_mean, float *__restrict__ save_invstd, int64_t n, int c,
                                                            int relu, float *__restrict__ y) {
-  const int c4 = c >> 2;
-  const int RL = 256 / c4 > 0 ? 256 / c4 : 1;
+  const auto [c4, RL] = row_lanes(c);
   const int cg = threadIdx.x % c4, rl = threadIdx.x / c4;
   if (rl >= RL) return;
   const int col = cg * 4;
@@ -279,9 +169,7 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float *__restri
 }
 
 static unsigned bn_apply_grid(int64_t n, int c) {
-  const int c4 = c / 4;
-  const int rl = 256 / c4 > 0 ? 256 / c4 : 1;
-  int64_t g = ceil_div(n, 2 * (int64_t)rl);   // two rows per thread
+  int64_t g = ceil_div(n, 2 * (int64_t)row_lanes(c).RL);   // two rows per thread
   if (g > 4096) g = 4096;
   return (unsigned)(g < 1 ? 1 : g);
 }
@@ -292,12 +180,6 @@ static int bn_check(const char *who, int64_t n, int c) {
   return FTX_OK;
 }
 
-static size_t bn_partial_lds(int c) {
-  int c4 = c / 4;
-  int RL = 256 / c4 > 0 ? 256 / c4 : 1;
-  return sizeof(double) * 2 * RL * c;
-}
-
 extern "C" int ftx_bn_train_fwd(const float *x, const float *residual, const float *gamma, const float *beta, float *running_mean,
                                 float *running_var, float momentum, float eps, int64_t n, int32_t c, int32_t relu, float *y,
                                 float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes, void *stream) {
@@ -306,16 +188,13 @@ extern "C" int ftx_bn_train_fwd(const float *x, const float *residual, const flo
   FTX_REQUIRE(n >= 1, "ftx_bn_train_fwd: needs at least one row");
   FTX_REQUIRE(x && gamma && beta && y && save_mean && save_invstd && workspace, "ftx_bn_train_fwd: null pointer");
   FTX_REQUIRE(c <= 512, "ftx_bn_train_fwd: c > 512 unsupported");
-  if (workspace_bytes < ftx_bn_workspace_bytes(n, c)) {
-    set_error("ftx_bn_train_fwd: workspace %zu < required %zu", workspace_bytes, ftx_bn_workspace_bytes(n, c));
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < ftx_bn_workspace_bytes(n, c)) return workspace_short("ftx_bn_train_fwd", workspace_bytes, ftx_bn_workspace_bytes(n, c));
   hipStream_t st = (hipStream_t)stream;
   const StreamScratch sc = stream_scratch(st);
   if (!sc.counters) return FTX_ELAUNCH;
   const int nb = bn_blocks(n);
   double *part = (double *)workspace;
-  bn_partial_kernel<FwdOp><<<nb, 256, bn_partial_lds(c), st>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n, c, part, sc);
+  bn_partial_kernel<FwdOp><<<nb, 256, colstats_lds_bytes(c), st>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n, c, part, sc);
   bn_apply_fwd_kernel<<<bn_apply_grid(n, c), 256, 0, st>>>(x, residual, gamma, beta, part + (size_t)nb * 2 * c, eps, momentum, running_mean,
                                                            running_var, save_mean, save_invstd, n, c, relu, y);
   return check_launch("ftx_bn_train_fwd");
@@ -343,15 +222,7 @@ __global__ void bn_apply_eval_kernel(const float *__restrict__ x, const float *_
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     int col = (int)(e % c4) * 4;
     float4 xv = *(const float4 *)&x[e * 4];
-    float o[4] = {xv.x, xv.y, xv.z, xv.w};
-    float rr[4] = {0, 0, 0, 0};
-    if (res) {
-      float4 t = *(const float4 *)&res[e * 4];
-      rr[0] = t.x; rr[1] = t.y; rr[2] = t.z; rr[3] = t.w;
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) o[v] = bn_eval_elem(o[v], rm[col + v], rv[col + v], eps, gamma[col + v], beta[col + v], rr[v], relu);
-    *(float4 *)&y[e * 4] = make_float4(o[0], o[1], o[2], o[3]);
+    *(float4 *)&y[e * 4] = bn_eval_apply4(xv, res, e * 4, rm, rv, eps, gamma, beta, col, relu);
   }
 }
 
@@ -372,8 +243,7 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const float *__restri
                                                            const float *__restrict__ invstd, const double *__restrict__ sums, int64_t n, int c,
                                                            int relu, float *__restrict__ gx, float *__restrict__ gres,
                                                            float *__restrict__ grad_gamma, float *__restrict__ grad_beta) {
-  const int c4 = c >> 2;
-  const int RL = 256 / c4 > 0 ? 256 / c4 : 1;
+  const auto [c4, RL] = row_lanes(c);
   const int cg = threadIdx.x % c4, rl = threadIdx.x / c4;
   if (rl >= RL) return;
   const int col = cg * 4;
@@ -439,117 +309,15 @@ extern "C" int ftx_bn_train_bwd(const float *grad_y, const float *x, const float
   FTX_REQUIRE(!relu || remask || y, "ftx_bn_train_bwd: relu needs the forward output y (or beta, when no residual went into it)");
   const int rmode = !relu ? 0 : (remask ? 2 : 1);
   FTX_REQUIRE(c <= 512, "ftx_bn_train_bwd: c > 512 unsupported");
-  if (workspace_bytes < ftx_bn_workspace_bytes(n, c)) {
-    set_error("ftx_bn_train_bwd: workspace %zu < required %zu", workspace_bytes, ftx_bn_workspace_bytes(n, c));
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < ftx_bn_workspace_bytes(n, c)) return workspace_short("ftx_bn_train_bwd", workspace_bytes, ftx_bn_workspace_bytes(n, c));
   hipStream_t st = (hipStream_t)stream;
   const StreamScratch sc = stream_scratch(st);
   if (!sc.counters) return FTX_ELAUNCH;
   const int nb = bn_blocks(n);
   double *part = (double *)workspace;
   double *sums = part + (size_t)nb * 2 * c;   // written by the last block of the statistics pass
-  bn_partial_kernel<BwdOp><<<nb, 256, bn_partial_lds(c), st>>>(x, grad_y, rmode == 1 ? y : nullptr, save_mean, save_invstd, gamma, beta, rmode, n, c, part, sc);
+  bn_partial_kernel<BwdOp><<<nb, 256, colstats_lds_bytes(c), st>>>(x, grad_y, rmode == 1 ? y : nullptr, save_mean, save_invstd, gamma, beta, rmode, n, c, part, sc);
   bn_apply_bwd_kernel<<<bn_apply_grid(n, c), 256, 0, st>>>(grad_y, x, y, gamma, beta, save_mean, save_invstd, sums, n, c, rmode, grad_x, grad_residual,
                                                            grad_gamma, grad_beta);
   return check_launch("ftx_bn_train_bwd");
-}
-
-// ---------------------------------------------------------------------------------------
-// Column sums of a row-major (rows, cols) float32 matrix: the bias gradient of every Linear of the ViT trunk and of the point
-// branch (the reference reaches it through autograd's sum_to reduction: models/transformers.py:16-45, timm Mlp / Attention).
-// Pass 1: block = up to 256 columns (<= 64 lanes x float4 of a row) x (256 / lanes) row lanes over one chunk of rows -> one float64 partial row;
-// pass 2: 16 lanes per column sum the chunk rows (every 16th each, combined in lane order).  Float64 throughout: the rounding to float32 happens once.
-// A (1, M) x (M, N) library GEMM took 14 us for the 2312 x 768..3072 gradients, 48 times per step; these two take 3-6 us together.
-// ---------------------------------------------------------------------------------------
-// geometry of pass 1: c4w float4 column groups per row (<= 64: 1 KB of a row per wave), RL = 256 / c4w row lanes, `chunks` row ranges
-struct ColsumGeom {
-  int c4w, rl, slab, chunks;
-};
-static ColsumGeom colsum_geom(int64_t rows, int cols) {
-  ColsumGeom g;
-  const int c4 = (cols + 3) / 4;
-  g.c4w = c4 < 64 ? c4 : 64;
-  g.rl = 256 / g.c4w;
-  g.slab = g.c4w * 4;
-  int64_t ch = ceil_div(rows, (int64_t)g.rl * 8);   // ~8 rows per thread
-  if (ch > 256) ch = 256;
-  g.chunks = (int)(ch < 1 ? 1 : ch);
-  return g;
-}
-extern "C" size_t ftx_colsum_workspace_bytes(int64_t rows, int32_t cols) {
-  if (rows <= 0 || cols <= 0) return 256;
-  return sizeof(double) * (size_t)colsum_geom(rows, cols).chunks * (size_t)cols + 256;
-}
-
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const float *__restrict__ x, int64_t rows, int cols, int c4w, int RL,
-                                                             double *__restrict__ part) {
-  __shared__ double sh[1024];   // [RL][slab], RL * slab <= 256 * 4
-  const int slab = c4w * 4;
-  const int cq = threadIdx.x % c4w, rl = threadIdx.x / c4w;
-  const int col = blockIdx.x * slab + cq * 4;
-  const int64_t per = ceil_div(rows, (int64_t)gridDim.y);
-  const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < rows ? r0 + per : rows;
-  if (rl < RL) {
-    double s[4] = {0, 0, 0, 0};
-    if (col < cols) {
-      int64_t r = r0 + rl;
-      for (; r + RL < r1; r += 2 * RL) {   // two rows in flight per thread
-        const float4 a = *(const float4 *)&x[r * cols + col], b = *(const float4 *)&x[(r + RL) * cols + col];
-        s[0] += (double)a.x; s[1] += (double)a.y; s[2] += (double)a.z; s[3] += (double)a.w;
-        s[0] += (double)b.x; s[1] += (double)b.y; s[2] += (double)b.z; s[3] += (double)b.w;
-      }
-      for (; r < r1; r += RL) {
-        const float4 a = *(const float4 *)&x[r * cols + col];
-        s[0] += (double)a.x; s[1] += (double)a.y; s[2] += (double)a.z; s[3] += (double)a.w;
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) sh[rl * slab + cq * 4 + v] = s[v];
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < slab; j += 256) {
-    const int c = blockIdx.x * slab + j;
-    if (c < cols) {
-      double t = 0;
-      for (int q = 0; q < RL; ++q) t += sh[q * slab + j];
-      part[(int64_t)blockIdx.y * cols + c] = t;
-    }
-  }
-}
-
-// pass 2: block = 16 columns x 16 chunk lanes; a lane sums every 16th partial row (independent loads), the 16 lanes are combined in order
-__global__ __launch_bounds__(256) void colsum_final_kernel(const double *__restrict__ part, int chunks, int cols, float *__restrict__ out) {
-  __shared__ double sh[16][16];
-  const int cw = threadIdx.x & 15, cl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cw;
-  double s = 0;
-  if (c < cols) {
-#pragma unroll 4
-    for (int k = cl; k < chunks; k += 16) s += part[(int64_t)k * cols + c];
-  }
-  sh[cl][cw] = s;
-  __syncthreads();
-  if (cl == 0 && c < cols) {
-    double t = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += sh[q][cw];
-    out[c] = (float)t;
-  }
-}
-
-extern "C" int ftx_colsum(const float *x, int64_t rows, int32_t cols, float *out, void *workspace, size_t workspace_bytes, void *stream) {
-  FTX_REQUIRE(rows >= 0 && cols >= 4 && cols % 4 == 0, "ftx_colsum: cols must be a positive multiple of 4 (got %d)", cols);
-  FTX_REQUIRE(out && workspace && (x || rows == 0), "ftx_colsum: null pointer");
-  if (workspace_bytes < ftx_colsum_workspace_bytes(rows, cols)) {
-    set_error("ftx_colsum: workspace %zu < required %zu", workspace_bytes, ftx_colsum_workspace_bytes(rows, cols));
-    return FTX_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const ColsumGeom g = colsum_geom(rows, cols);
-  double *part = (double *)workspace;
-  dim3 grid((unsigned)ceil_div(cols, g.slab), (unsigned)g.chunks);
-  colsum_partial_kernel<<<grid, 256, 0, st>>>(x, rows, cols, g.c4w, g.rl, part);
-  colsum_final_kernel<<<(unsigned)ceil_div(cols, 16), 256, 0, st>>>(part, g.chunks, cols, out);
-  return check_launch("ftx_colsum");
 }

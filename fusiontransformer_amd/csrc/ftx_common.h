@@ -50,6 +50,20 @@ inline unsigned grid_for(int64_t work, int block) {
     }                                          \
   } while (0)
 
+// The refusal of a workspace that is too small: `if (workspace_bytes < need) return workspace_short(who, workspace_bytes, need);`
+inline int workspace_short(const char *who, size_t have, size_t need) {
+  set_error("%s: workspace %zu < required %zu", who, have, need);
+  return FTX_EWORKSPACE;
+}
+
+// nn.Upsample(size) nearest source index in float32, exactly as ATen computes it:
+// src = min((int)floorf(dst * ((float)n_in / (float)n_out)), n_in - 1).
+__device__ inline int nearest_src(int dst, int n_in, int n_out) {
+  float scale = (float)n_in / (float)n_out;
+  int s = (int)floorf((float)dst * scale);
+  return s < n_in - 1 ? s : n_in - 1;
+}
+
 // FNV-1a over the four int32 words of a coordinate row, folded to 60 bits
 // (torchsparse v1.1.0 hash kernel; call sites models/utils.py:19,74-78).
 __host__ __device__ inline int64_t fnv_hash4(int32_t x, int32_t y, int32_t z, int32_t b) {

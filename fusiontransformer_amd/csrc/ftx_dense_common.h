@@ -596,10 +596,7 @@ int dense_wgrad_entry(const float *G, const float *X, int64_t m, int32_t n, int3
   int splits;
   const int64_t len = dense_wgrad_split_len(m, n, k, &splits);
   const size_t need = dense_wgrad_partial_bytes(splits, n, k);
-  if (need > 0 && (!workspace || workspace_bytes < need)) {
-    set_error("%s: workspace %zu < required %zu", me, workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
+  if (need > 0 && (!workspace || workspace_bytes < need)) return workspace_short(me, workspace_bytes, need);
   float *part = (float *)workspace;
   const dim3 grid((unsigned)ceil_div(k, kDenseDwTile), (unsigned)ceil_div(n, kDenseDwTile), (unsigned)splits);
   dense_wgrad_kernel<F><<<grid, 256, 0, st>>>(G, X, m, n, k, len, part, dW);

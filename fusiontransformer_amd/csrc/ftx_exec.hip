@@ -1,5 +1,5 @@
-// Native eval-mode executor of the SPVCNN LiDAR branch (include/ftx.h: ftx_spvcnn_eval) and the two row kernels it needs where the
-// Python path uses torch (channel concatenation, row-wise add).
+// Native eval-mode executor of the SPVCNN LiDAR branch (include/ftx.h: ftx_spvcnn_eval).  Where the Python path uses torch (channel
+// concatenation, row-wise add) it issues the row kernels of ftx_rows.hip.
 //
 // The network is a static op program that the host emits once per model (fusiontransformer_amd/native_eval.py) over numbered buffers
 // ("slots"); it is validated against the model and batch tables by the checker both SPVCNN executors share (ftx_spvcnn_program.h);
@@ -10,46 +10,6 @@
 #include "ftx_spvcnn_program.h"
 
 using namespace ftx;
-
-// ---------------------------------------------------------------- row kernels
-// out[r] = a[r] ++ b[r] (channel concatenation); ca, cb multiples of 4, 16-byte accesses
-__global__ void rows_concat_kernel(const float *__restrict__ a, const float *__restrict__ b, int64_t n, int ca, int cb, float *__restrict__ out) {
-  const int cv = (ca + cb) >> 2, av = ca >> 2;
-  const int64_t total = n * cv;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = e / cv;
-    const int j = (int)(e - r * cv);
-    const float4 v = j < av ? *(const float4 *)&a[r * ca + 4 * j] : *(const float4 *)&b[r * cb + 4 * (j - av)];
-    *(float4 *)&out[e * 4] = v;
-  }
-}
-
-extern "C" int ftx_rows_concat(const float *a, int32_t ca, const float *b, int32_t cb, int64_t n, float *out, void *stream) {
-  FTX_REQUIRE(n >= 0, "ftx_rows_concat: n < 0");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && cb >= 4 && cb % 4 == 0, "ftx_rows_concat: channels must be multiples of 4 (ca=%d cb=%d)", ca, cb);
-  if (n == 0) return FTX_OK;
-  FTX_REQUIRE(a && b && out, "ftx_rows_concat: null pointer");
-  rows_concat_kernel<<<grid_for(n * ((ca + cb) / 4), 256), 256, 0, (hipStream_t)stream>>>(a, b, n, ca, cb, out);
-  return check_launch("ftx_rows_concat");
-}
-
-// out = a + b over (n, c) rows, one fp32 add per element; out may be a or b (every element is read before it is written, by its own thread)
-__global__ void rows_add_kernel(const float *a, const float *b, int64_t total4, float *out) {
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total4; e += (int64_t)gridDim.x * blockDim.x) {
-    const float4 x = *(const float4 *)&a[e * 4];
-    const float4 y = *(const float4 *)&b[e * 4];
-    *(float4 *)&out[e * 4] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
-  }
-}
-
-extern "C" int ftx_rows_add(const float *a, const float *b, int64_t n, int32_t c, float *out, void *stream) {
-  FTX_REQUIRE(n >= 0, "ftx_rows_add: n < 0");
-  FTX_REQUIRE(c >= 4 && c % 4 == 0, "ftx_rows_add: channels must be a multiple of 4 (c=%d)", c);
-  if (n == 0) return FTX_OK;
-  FTX_REQUIRE(a && b && out, "ftx_rows_add: null pointer");
-  rows_add_kernel<<<grid_for(n * (c / 4), 256), 256, 0, (hipStream_t)stream>>>(a, b, n * (c / 4), out);
-  return check_launch("ftx_rows_add");
-}
 
 // ---------------------------------------------------------------- plan (the checker of the program: ftx_spvcnn_program.h)
 namespace {

@@ -1,5 +1,5 @@
-// Native training executor of the SPVCNN LiDAR branch (include/ftx.h: ftx_spvcnn_train_fwd / _bwd) and the row kernel its backward
-// needs where the Python path slices a gradient (ftx_rows_split, the backward of ftx_rows_concat).
+// Native training executor of the SPVCNN LiDAR branch (include/ftx.h: ftx_spvcnn_train_fwd / _bwd).  Where the Python path slices a
+// gradient its backward issues ftx_rows_split (ftx_rows.hip, the backward of ftx_rows_concat).
 //
 // The program, the model table and the batch tables are the eval executor's (ftx_exec.hip), and one checker validates them for both
 // (ftx_spvcnn_program.h: check_program, which also says where this executor asks more of a program); the forward issues the train-mode form of
@@ -11,32 +11,6 @@
 #include "ftx_spvcnn_program.h"
 
 using namespace ftx;
-
-// ---------------------------------------------------------------- row kernel
-// a[r], b[r] = in[r][:ca], in[r][ca:] (the backward of the channel concatenation); ca, cb multiples of 4, 16-byte accesses
-__global__ void rows_split_kernel(const float *__restrict__ in, int64_t n, int ca, int cb, float *__restrict__ a, float *__restrict__ b) {
-  const int cv = (ca + cb) >> 2, av = ca >> 2;
-  const int64_t total = n * cv;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = e / cv;
-    const int j = (int)(e - r * cv);
-    const float4 v = *(const float4 *)&in[e * 4];
-    if (j < av)
-      *(float4 *)&a[r * ca + 4 * j] = v;
-    else
-      *(float4 *)&b[r * cb + 4 * (j - av)] = v;
-  }
-}
-
-extern "C" int ftx_rows_split(const float *in, int64_t n, int32_t ca, int32_t cb, float *a, float *b, void *stream) {
-  FTX_REQUIRE(n >= 0, "ftx_rows_split: n < 0");
-  FTX_REQUIRE(ca >= 4 && ca % 4 == 0 && cb >= 4 && cb % 4 == 0, "ftx_rows_split: channels must be multiples of 4 (ca=%d cb=%d)", ca, cb);
-  if (n == 0) return FTX_OK;
-  FTX_REQUIRE(in && a && b, "ftx_rows_split: null pointer");
-  FTX_REQUIRE((((uintptr_t)in | (uintptr_t)a | (uintptr_t)b) & 15) == 0, "ftx_rows_split: pointers must be 16-byte aligned");
-  rows_split_kernel<<<grid_for(n * ((ca + cb) / 4), 256), 256, 0, (hipStream_t)stream>>>(in, n, ca, cb, a, b);
-  return check_launch("ftx_rows_split");
-}
 
 // ---------------------------------------------------------------- plan
 namespace {

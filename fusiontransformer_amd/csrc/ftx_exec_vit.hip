@@ -1,5 +1,5 @@
-// Native eval-mode executor of the ViT image branch (include/ftx.h: ftx_vit_eval) and the row kernel it needs where the Python path
-// uses torch (the residual stream as one tensor, transformers._materialize).
+// Native eval-mode executor of the ViT image branch (include/ftx.h: ftx_vit_eval).  Where the Python path uses torch (the residual
+// stream as one tensor, transformers._materialize) it issues ftx_rows_add_bias (ftx_rows.hip).
 //
 // The trunk is three host tables (model, blocks, taps; fusiontransformer_amd/native_image.py writes them from the module tree).  This
 // file validates them, places every intermediate in the caller's arena and issues, per block, exactly what transformers.Block.chain
@@ -13,32 +13,6 @@
 #include "ftx_common.h"
 
 using namespace ftx;
-
-// ---------------------------------------------------------------- row kernel
-// out = r + (p + pb), pb (c) broadcast over the rows: two fp32 adds per element in that order; p == NULL: out = r
-__global__ __launch_bounds__(256) void rows_add_bias_kernel(const float *__restrict__ r, const float *__restrict__ p, const float *__restrict__ pb,
-                                                            int64_t total4, int c4, float *__restrict__ out) {
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total4; e += (int64_t)gridDim.x * blockDim.x) {
-    float4 x = *(const float4 *)&r[e * 4];
-    if (p) {
-      const float4 y = *(const float4 *)&p[e * 4];
-      const float4 b = *(const float4 *)&pb[(e % c4) * 4];
-      x = make_float4(x.x + (y.x + b.x), x.y + (y.y + b.y), x.z + (y.z + b.z), x.w + (y.w + b.w));
-    }
-    *(float4 *)&out[e * 4] = x;
-  }
-}
-
-extern "C" int ftx_rows_add_bias(const float *r, const float *p, const float *pb, int64_t n, int32_t c, float *out, void *stream) {
-  FTX_REQUIRE(n >= 0, "ftx_rows_add_bias: n < 0");
-  FTX_REQUIRE(c >= 4 && c % 4 == 0, "ftx_rows_add_bias: channels must be a multiple of 4 (c=%d)", c);
-  FTX_REQUIRE((p == nullptr) == (pb == nullptr), "ftx_rows_add_bias: p and pb are given together or not at all");
-  if (n == 0) return FTX_OK;
-  FTX_REQUIRE(r && out, "ftx_rows_add_bias: null pointer");
-  FTX_REQUIRE((((uintptr_t)r | (uintptr_t)p | (uintptr_t)pb | (uintptr_t)out) & 15) == 0, "ftx_rows_add_bias: pointers must be 16-byte aligned");
-  rows_add_bias_kernel<<<grid_for(n * (c / 4), 256), 256, 0, (hipStream_t)stream>>>(r, p, pb, n * (c / 4), c / 4, out);
-  return check_launch("ftx_rows_add_bias");
-}
 
 // ---------------------------------------------------------------- tables (layouts documented in include/ftx.h)
 namespace {

@@ -189,10 +189,7 @@ extern "C" int ftx_unique_sorted(const int64_t *keys, int64_t n, int64_t *uniq, 
   UniqueLayout L;
   int rc = unique_layout(n, &L);
   if (rc != FTX_OK) return rc;
-  if (workspace_bytes < L.total) {
-    set_error("ftx_unique_sorted: workspace %zu < required %zu", workspace_bytes, L.total);
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < L.total) return workspace_short("ftx_unique_sorted", workspace_bytes, L.total);
   char *ws = (char *)workspace;
   int64_t *keys_sorted = (int64_t *)(ws + L.off_keys);
   int32_t *vals_in = (int32_t *)(ws + L.off_vals_in);
@@ -380,10 +377,7 @@ extern "C" int ftx_levels_unique(const int32_t *points, int64_t n, const int32_t
   LevelsLayout L;
   int rc = levels_layout(n, n_levels, &L);
   if (rc != FTX_OK) return rc;
-  if (workspace_bytes < L.total) {
-    set_error("ftx_levels_unique: workspace %zu < required %zu", workspace_bytes, L.total);
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < L.total) return workspace_short("ftx_levels_unique", workspace_bytes, L.total);
   char *ws = (char *)workspace;
   // sorted_keys / order (optional outputs): the n_levels x n (tag | hash) keys in sorted order and the point of each -- level l owns
   // [l*n, (l+1)*n): its points sorted by voxel, stable, i.e. the sorted segments of spvoxelize at that stride (ftx_level_segments)

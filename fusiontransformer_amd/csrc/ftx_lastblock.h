@@ -143,4 +143,43 @@ struct StoreTotals {
   }
 };
 
+// Row-lane geometry of the column-statistics and BatchNorm apply kernels: a block of 256 threads is c4 = c / 4 float4 column groups
+// times RL row lanes (thread tid: column group tid % c4, row lane tid / c4; lanes >= RL idle when c4 does not divide 256).
+struct RowLanes {
+  int c4, RL;
+};
+__host__ __device__ constexpr RowLanes row_lanes(int c) {
+  const int c4 = c >> 2;
+  return RowLanes{c4, 256 / c4 > 0 ? 256 / c4 : 1};
+}
+// dynamic LDS of a column-statistics kernel: sh[2][RL][c] doubles
+constexpr size_t colstats_lds_bytes(int c) { return sizeof(double) * 2 * row_lanes(c).RL * c; }
+static_assert(row_lanes(4).RL == 256 && row_lanes(96).RL == 10 && row_lanes(512).RL == 2 && row_lanes(1024).RL == 1, "RL = max(256 / (c / 4), 1)");
+static_assert(colstats_lds_bytes(4) == 16384 && colstats_lds_bytes(96) == 15360 && colstats_lds_bytes(512) == 16384, "sizeof(double) * 2 * RL * c");
+
+// The end of a column-statistics kernel (bn_partial_kernel, spconv_reduce_stats_kernel), from every thread of the block: thread
+// (column group cg, row lane rl) brings the float64 sums s0 / s1 of its four columns; the RL lanes of a column are combined in lane order
+// into the block's row part[blockIdx.x][2][c], and the last block to finish leaves the column totals [2][c] behind the gridDim.x rows
+// (what ftx_bn_train_fwd_totals and the apply kernels read).  sh: the kernel's [2][RL][c] doubles.
+__device__ inline void colstats_block_tail(const double (&s0)[4], const double (&s1)[4], int rl, int cg, int RL, int c, double *sh, double *part,
+                                           StreamScratch sc) {
+  const int tid = threadIdx.x;
+  if (rl < RL) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      sh[(0 * RL + rl) * c + cg * 4 + v] = s0[v];
+      sh[(1 * RL + rl) * c + cg * 4 + v] = s1[v];
+    }
+  }
+  __syncthreads();
+  for (int j = tid; j < 2 * c; j += 256) {
+    int which = j / c, col = j - which * c;
+    double s = 0;
+    for (int q = 0; q < RL; ++q) s += sh[(which * RL + q) * c + col];
+    lb_store(&part[((int64_t)blockIdx.x * 2 + which) * c + col], s);
+  }
+  __syncthreads();   // sh is free again: 2 * RL * c = 2048 doubles >= 256 + 2c for c <= 512
+  last_block_totals(part, (int)gridDim.x, c, sc, sh, StoreTotals{part + (int64_t)gridDim.x * 2 * c, c});
+}
+
 }  // namespace ftx

@@ -11,6 +11,7 @@
 // eager formulation become one launch forward and two backward.  HBM-bound: a row is 3 KB; one wave per row, the row lives in
 // registers (C = 256 * VPL floats, VPL float4 per lane), statistics by wave shuffles, no LDS in the forward.
 #include "ftx_common.h"
+#include "ftx_chunk_rows.h"
 
 using namespace ftx;
 
@@ -139,26 +140,6 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const float *__restrict
     part[(int64_t)blockIdx.x * (NP * C) + j] = ((double)sh[0][j] + (double)sh[1][j]) + ((double)sh[2][j] + (double)sh[3][j]);
 }
 
-// out[c] = sum over the chunk rows of part[k][c], 16 lanes per column (every 16th row each, combined in lane order)
-__global__ __launch_bounds__(256) void ln_params_final_kernel(const double *__restrict__ part, int chunks, int cols, float *__restrict__ out) {
-  __shared__ double sh[16][16];
-  const int cw = threadIdx.x & 15, cl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cw;
-  double s = 0;
-  if (c < cols) {
-#pragma unroll 4
-    for (int k = cl; k < chunks; k += 16) s += part[(int64_t)k * cols + c];
-  }
-  sh[cl][cw] = s;
-  __syncthreads();
-  if (cl == 0 && c < cols) {
-    double t = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += sh[q][cw];
-    out[c] = (float)t;
-  }
-}
-
 static int ln_check(const char *who, int64_t rows, int c) {
   FTX_REQUIRE(rows >= 0, "%s: rows < 0", who);
   FTX_REQUIRE(c >= 256 && c <= 1024 && c % 256 == 0, "%s: the row length must be 256, 512, 768 or 1024 (got %d)", who, c);
@@ -196,10 +177,8 @@ extern "C" int ftx_add_layernorm_bwd(const float *grad_h, const float *grad_s, c
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE(rows >= 1, "ftx_add_layernorm_bwd: needs at least one row");
   FTX_REQUIRE(grad_h && s && gamma && mean && rstd && grad_x && grad_params && workspace, "ftx_add_layernorm_bwd: null pointer");
-  if (workspace_bytes < ftx_layernorm_bwd_workspace_bytes(rows, c)) {
-    set_error("ftx_add_layernorm_bwd: workspace %zu < required %zu", workspace_bytes, ftx_layernorm_bwd_workspace_bytes(rows, c));
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < ftx_layernorm_bwd_workspace_bytes(rows, c))
+    return workspace_short("ftx_add_layernorm_bwd", workspace_bytes, ftx_layernorm_bwd_workspace_bytes(rows, c));
   hipStream_t st = (hipStream_t)stream;
   const int rpb = ln_rows_per_block(rows);
   const int nb = (int)ceil_div(rows, rpb);
@@ -217,6 +196,6 @@ extern "C" int ftx_add_layernorm_bwd(const float *grad_h, const float *grad_s, c
     default: FTX_LN_BWD(4); break;
   }
 #undef FTX_LN_BWD
-  ln_params_final_kernel<<<(unsigned)ceil_div(np * c, 16), 256, 0, st>>>(part, nb, np * c, grad_params);
+  chunk_rows_sum_kernel<<<(unsigned)ceil_div(np * c, 16), 256, 0, st>>>(part, nb, np * c, grad_params);
   return check_launch("ftx_add_layernorm_bwd");
 }

@@ -4,25 +4,13 @@
 // both SegIoU confusion matrices, in one pass over the points: ~40 small framework launches and the
 // host synchronisations of the boolean-mask indexing become 3 launches and none.
 #include "ftx_common.h"
+#include "ftx_reduce.h"
 
 using namespace ftx;
 
 constexpr int LC_MAX = 32;      // classes held in registers
 constexpr int LOSS_BLOCKS = 256;
 constexpr int WSUM_BLOCKS = 64;
-
-__device__ inline double loss_block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sh[w];
-  return r;
-}
 
 // wpart[b] = sum of w[label_i] over block b's contiguous slice of the points (the normaliser of the weighted-mean cross-entropy is
 // the sum of the WSUM_BLOCKS slices in slice order: loss_wsum_total).  Depends on the labels only.  One block of 1024 threads took
@@ -37,7 +25,7 @@ __global__ __launch_bounds__(256) void loss_wsum_kernel(const int64_t *__restric
     int64_t y = label[i];
     if (y >= 0 && y < c) s += cw ? (double)cw[y] : 1.0;
   }
-  double r = loss_block_sum(s, sh);
+  double r = block_sum(s, sh);
   if (threadIdx.x == 0) wpart[blockIdx.x] = r;
 }
 __device__ inline double loss_wsum_total(const double *__restrict__ wpart) {
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
     store_row<C>(g3 + i * c, g);
     store_row<C>(g2 + i * c, h);
   }
-  double r0 = loss_block_sum(a_ce3, sh), r1 = loss_block_sum(a_ce2, sh), r2 = loss_block_sum(a_kl2, sh), r3 = loss_block_sum(a_kl3, sh);
+  double r0 = block_sum(a_ce3, sh), r1 = block_sum(a_ce2, sh), r2 = block_sum(a_kl2, sh), r3 = block_sum(a_kl3, sh);
   if (threadIdx.x == 0) {
     double *p = part + (int64_t)blockIdx.x * 4;
     p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r3;
@@ -207,7 +195,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const double *__rest
   for (int j = 0; j < 4; ++j) v[j] = b < nb ? part[(int64_t)b * 4 + j] : 0.0;
   double s[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) s[j] = loss_block_sum(v[j], sh);
+  for (int j = 0; j < 4; ++j) s[j] = block_sum(v[j], sh);
   if (threadIdx.x != 0) return;
   const double W = loss_wsum_total(wpart);
   const double ce3 = s[0] / W, ce2 = s[1] / W, kl2 = s[2] / (double)n, kl3 = s[3] / (double)n;
@@ -298,7 +286,7 @@ __global__ __launch_bounds__(256) void seg_loss_main_kernel(const float *__restr
       store_row<C>(grad + i * c, g);
     }
   }
-  const double r = loss_block_sum(a_ce, sh);
+  const double r = block_sum(a_ce, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
   __syncthreads();
   if (conf)
@@ -311,7 +299,7 @@ __global__ __launch_bounds__(256) void seg_loss_finalize_kernel(const double *__
                                                                 float *__restrict__ loss) {
   __shared__ double sh[4];
   const int b = threadIdx.x;
-  const double s = loss_block_sum(b < nb ? part[b] : 0.0, sh);
+  const double s = block_sum(b < nb ? part[b] : 0.0, sh);
   if (threadIdx.x != 0) return;
   loss[0] = (float)(s / loss_wsum_total(wpart));
 }

@@ -202,10 +202,7 @@ extern "C" int ftx_segment_build(const int32_t *keys, int64_t n, int64_t m, int3
   SegLayout L;
   int rc = seg_layout(n, m, &L);
   if (rc != FTX_OK) return rc;
-  if (workspace_bytes < L.total) {
-    set_error("ftx_segment_build: workspace %zu < required %zu", workspace_bytes, L.total);
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < L.total) return workspace_short("ftx_segment_build", workspace_bytes, L.total);
   char *ws = (char *)workspace;
   int32_t *keys_in = (int32_t *)(ws + L.off_keys_in), *keys_out = (int32_t *)(ws + L.off_keys_out), *vals_in = (int32_t *)(ws + L.off_vals_in);
   void *tmp = ws + L.off_tmp;
@@ -304,14 +301,6 @@ extern "C" int ftx_segment_sum(const float *src, const int32_t *order, const int
 }
 
 // ---------------------------------------------------------------- lift gather
-// nn.Upsample(size) nearest source index in float32, exactly as ATen computes it:
-// src = min((int)floorf(dst * ((float)n_in / (float)n_out)), n_in - 1).
-__device__ inline int nearest_src(int dst, int n_in, int n_out) {
-  float scale = (float)n_in / (float)n_out;
-  int s = (int)floorf((float)dst * scale);
-  return s < n_in - 1 ? s : n_in - 1;
-}
-
 __global__ void lift_gather_fwd_kernel(const float *__restrict__ grid, const int64_t *__restrict__ img_idx,
                                        const int32_t *__restrict__ pb, int64_t n, int gh, int gw, int c, int H, int W,
                                        float *__restrict__ out) {

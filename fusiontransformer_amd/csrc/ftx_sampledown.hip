@@ -7,30 +7,12 @@
 // the last two sums do not depend on the incoming gradient and are produced by the forward
 // statistics pass (xhat m x_c = is*(v x_c - mean m x_c)); only the picked pixels carry dy.
 #include "ftx_common.h"
+#include "ftx_reduce.h"
 
 using namespace ftx;
 
 constexpr int SD_NSUM = 27;   // v(3) v^2(3) m(3) m*x_c(9) v*x_c(9)
 constexpr int SD_BLOCKS = 512;
-
-__device__ inline int sd_nearest(int dst, int n_in, int n_out) {
-  float scale = (float)n_in / (float)n_out;
-  int s = (int)floorf((float)dst * scale);
-  return s < n_in - 1 ? s : n_in - 1;
-}
-
-__device__ inline double block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sh[w];
-  return r;  // valid on thread 0
-}
 
 __global__ __launch_bounds__(256) void sd_stats_kernel(const float *__restrict__ img, int64_t hw, int b, const float *__restrict__ w9,
                                                        const float *__restrict__ b3, double *__restrict__ part) {
@@ -119,7 +101,7 @@ __global__ void sd_pick_kernel(const float *__restrict__ img, int b, int h, int 
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
     int64_t bi = p / ohw, q = p - bi * ohw;
     int oy = (int)(q / ow), ox = (int)(q - (int64_t)oy * ow);
-    int64_t pix = (int64_t)sd_nearest(oy, h, oh) * w + sd_nearest(ox, w, ow);
+    int64_t pix = (int64_t)nearest_src(oy, h, oh) * w + nearest_src(ox, w, ow);
     const float *base = img + bi * 3 * hw + pix;
     float x0 = base[0], x1 = base[hw], x2 = base[2 * hw];
 #pragma unroll
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(256) void sd_bwd_kernel(const float *__restrict__ i
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
     int64_t bi = p / ohw, q = p - bi * ohw;
     int oy = (int)(q / ow), ox = (int)(q - (int64_t)oy * ow);
-    int64_t pix = (int64_t)sd_nearest(oy, h, oh) * w + sd_nearest(ox, w, ow);
+    int64_t pix = (int64_t)nearest_src(oy, h, oh) * w + nearest_src(ox, w, ow);
     const float *base = img + bi * 3 * hw + pix;
     float x[3] = {base[0], base[hw], base[2 * hw]};
 #pragma unroll

@@ -64,10 +64,7 @@ extern "C" int ftx_kernel_map_count(const int32_t *nbr, int64_t n_out, int32_t k
   FTX_REQUIRE(nbr && pos && workspace, "ftx_kernel_map_count: null pointer");
   FTX_REQUIRE(n_out * k < 0x7fffffff, "ftx_kernel_map_count: map too large for int32 positions");
   size_t need = ftx_kernel_map_count_workspace_bytes(n_out, k);
-  if (workspace_bytes < need) {
-    set_error("ftx_kernel_map_count: workspace %zu < required %zu", workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < need) return workspace_short("ftx_kernel_map_count", workspace_bytes, need);
   size_t bytes = workspace_bytes;
   auto it = rocprim::make_transform_iterator(nbr, IsValid());
   // pos temporarily holds the exclusive scan of the validity flags (k-major = sorted by (k, row))
@@ -300,20 +297,25 @@ __global__ void spconv_reduce_kernel(const float *__restrict__ tmp, const int32_
   }
 }
 
+// Grid of the two plain reduces: one thread per float4 of the output, at most 8192 blocks of 256.
+static unsigned reduce_grid(int64_t n, int co) {
+  int64_t g = ceil_div(n * (co / 4), 256);
+  if (g > 8192) g = 8192;
+  return (unsigned)g;
+}
+
 extern "C" int ftx_spconv_reduce(const float *tmp, const int32_t *pos, int64_t n, int32_t co, int32_t kvol, float *out, void *stream) {
   FTX_REQUIRE(n >= 0 && kvol >= 1 && co >= 4 && co % 4 == 0, "ftx_spconv_reduce: bad size");
   if (n == 0) return FTX_OK;
   FTX_REQUIRE(pos && out, "ftx_spconv_reduce: null pointer");
-  int64_t work = n * (co / 4);
-  int64_t g = ceil_div(work, 256);
-  if (g > 8192) g = 8192;
+  const unsigned g = reduce_grid(n, co);
   hipStream_t st = (hipStream_t)stream;
   if (kvol == 27)
-    spconv_reduce_kernel<27><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
+    spconv_reduce_kernel<27><<<g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
   else if (kvol == 8)
-    spconv_reduce_kernel<8><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
+    spconv_reduce_kernel<8><<<g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
   else
-    spconv_reduce_kernel<0><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
+    spconv_reduce_kernel<0><<<g, 256, 0, st>>>(tmp, pos, n, co, kvol, out);
   return check_launch("ftx_spconv_reduce");
 }
 
@@ -331,15 +333,7 @@ __global__ void spconv_reduce_bn_eval_kernel(const float *__restrict__ tmp, cons
     int64_t r = e / cv;
     int j = (int)(e - r * cv) * 4;
     const float4 acc = reduce_row<KVOL>(tmp, pos, n, co, KVOL, r, j);
-    float o[4] = {acc.x, acc.y, acc.z, acc.w};
-    float rr[4] = {0, 0, 0, 0};
-    if (res) {
-      float4 t = *(const float4 *)&res[r * co + j];
-      rr[0] = t.x; rr[1] = t.y; rr[2] = t.z; rr[3] = t.w;
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) o[v] = bn_eval_elem(o[v], rm[j + v], rv[j + v], eps, gamma[j + v], beta[j + v], rr[v], relu);
-    *(float4 *)&out[r * co + j] = make_float4(o[0], o[1], o[2], o[3]);
+    *(float4 *)&out[r * co + j] = bn_eval_apply4(acc, res, r * co + j, rm, rv, eps, gamma, beta, j, relu);
   }
 }
 
@@ -350,13 +344,12 @@ extern "C" int ftx_spconv_reduce_bn_eval(const float *tmp, const int32_t *pos, i
   FTX_REQUIRE(kvol == 27 || kvol == 8, "ftx_spconv_reduce_bn_eval: kvol must be 8 or 27, got %d", kvol);
   if (n == 0) return FTX_OK;
   FTX_REQUIRE(pos && out && gamma && beta && running_mean && running_var, "ftx_spconv_reduce_bn_eval: null pointer");
-  int64_t g = ceil_div(n * (co / 4), 256);
-  if (g > 8192) g = 8192;
+  const unsigned g = reduce_grid(n, co);
   hipStream_t st = (hipStream_t)stream;
   if (kvol == 27)
-    spconv_reduce_bn_eval_kernel<27><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, residual, gamma, beta, running_mean, running_var, eps, relu, out);
+    spconv_reduce_bn_eval_kernel<27><<<g, 256, 0, st>>>(tmp, pos, n, co, residual, gamma, beta, running_mean, running_var, eps, relu, out);
   else
-    spconv_reduce_bn_eval_kernel<8><<<(unsigned)g, 256, 0, st>>>(tmp, pos, n, co, residual, gamma, beta, running_mean, running_var, eps, relu, out);
+    spconv_reduce_bn_eval_kernel<8><<<g, 256, 0, st>>>(tmp, pos, n, co, residual, gamma, beta, running_mean, running_var, eps, relu, out);
   return check_launch("ftx_spconv_reduce_bn_eval");
 }
 
@@ -369,8 +362,7 @@ template <int KVOL>
 __global__ __launch_bounds__(256) void spconv_reduce_stats_kernel(const float *__restrict__ tmp, const int32_t *__restrict__ pos, int64_t n, int co,
                                                                   int kvol, float *__restrict__ out, double *part, StreamScratch sc) {
   extern __shared__ double sh[];  // [2][RL][co]
-  const int cv = co >> 2;
-  const int RL = 256 / cv;
+  const auto [cv, RL] = row_lanes(co);
   const int tid = threadIdx.x;
   const int cg = tid % cv, rl = tid / cv;
   const int64_t rows_per_block = ceil_div(n, (int64_t)gridDim.x);
@@ -387,28 +379,13 @@ __global__ __launch_bounds__(256) void spconv_reduce_stats_kernel(const float *_
       s0[2] += (double)acc.z; s1[2] += (double)acc.z * (double)acc.z;
       s0[3] += (double)acc.w; s1[3] += (double)acc.w * (double)acc.w;
     }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      sh[(0 * RL + rl) * co + j + v] = s0[v];
-      sh[(1 * RL + rl) * co + j + v] = s1[v];
-    }
   }
-  __syncthreads();
-  for (int e = tid; e < 2 * co; e += 256) {
-    int which = e / co, col = e - which * co;
-    double s = 0;
-    for (int q = 0; q < RL; ++q) s += sh[(which * RL + q) * co + col];
-    lb_store(&part[((int64_t)blockIdx.x * 2 + which) * co + col], s);
-  }
-  // column totals [2][co] behind the nb partial rows, by the last block to finish (ftx_lastblock.h): what ftx_bn_train_fwd_totals reads
-  __syncthreads();   // sh is free again: 2 * RL * co = 2048 doubles >= 256 + 2 co for co <= 512
-  last_block_totals(part, (int)gridDim.x, co, sc, sh, StoreTotals{part + (int64_t)gridDim.x * 2 * co, co});
+  colstats_block_tail(s0, s1, rl, cg, RL, co, sh, part, sc);
 }
 
 extern "C" int32_t ftx_spconv_reduce_stats_blocks(int64_t n, int32_t co) {
   if (n <= 0 || co < 4) return 1;
-  const int rl = 256 / (co / 4) > 0 ? 256 / (co / 4) : 1;
-  int64_t b = ceil_div(n, 2 * rl);   // ~2 rows per thread
+  int64_t b = ceil_div(n, 2 * row_lanes(co).RL);   // ~2 rows per thread
   if (b > 2048) b = 2048;
   return (int32_t)(b < 1 ? 1 : b);
 }
@@ -421,8 +398,7 @@ extern "C" int ftx_spconv_reduce_stats(const float *tmp, const int32_t *pos, int
   hipStream_t st = (hipStream_t)stream;
   const StreamScratch sc = stream_scratch(st);
   if (!sc.counters) return FTX_ELAUNCH;
-  const int rl = 256 / (co / 4);
-  const size_t lds = sizeof(double) * 2 * rl * co;
+  const size_t lds = colstats_lds_bytes(co);
   if (kvol == 27)
     spconv_reduce_stats_kernel<27><<<nb, 256, lds, st>>>(tmp, pos, n, co, kvol, out, part, sc);
   else if (kvol == 8)

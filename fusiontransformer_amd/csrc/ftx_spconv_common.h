@@ -472,10 +472,7 @@ int spconv_wgrad_entry(const float *A, int64_t rows_a, const int32_t *idx_a, con
   const int tile_len = spconv_wgrad_tile_len<F>(n_pairs, ca, cg, kvol);
   const int64_t tiles = spconv_wgrad_tiles_ub(n_pairs, tile_len, kvol);
   const size_t need = sizeof(float) * (size_t)tiles * mat;
-  if (!workspace || workspace_bytes < need) {
-    set_error("%s: workspace %zu < required %zu", me, workspace_bytes, need);
-    return FTX_EWORKSPACE;
-  }
+  if (!workspace || workspace_bytes < need) return workspace_short(me, workspace_bytes, need);
   const PairsWgradArgs a = {A, rows_a, idx_a, G, rows_g, idx_g, koff, ca, cg, kvol, tile_len, (float *)workspace, dW, (int)n_pairs};
   const WgradCfg c = spconv_wgrad_config(ca, cg);
   const dim3 grid((unsigned)tiles, (unsigned)ceil_div(ca, 32 * c.mi * c.wmg), (unsigned)ceil_div(cg, 32 * c.ni * c.wng));

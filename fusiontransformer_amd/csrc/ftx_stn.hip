@@ -18,6 +18,7 @@
 //               written exactly once.
 #include "ftx_common.h"
 #include "ftx_lastblock.h"
+#include "ftx_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -193,9 +194,7 @@ __global__ __launch_bounds__(256) void aff_theta_kernel(AffSrc S, const float *_
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
-    double v = acc[q];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const double v = wave_sum_down(acc[q]);
     if (lane == 0) lds[wave * 6 + q] = v;
   }
   __syncthreads();
@@ -274,10 +273,7 @@ int aff_blocks_per_frame(int b, int64_t items, int per_block) {
 
 int aff_workspace(const char *who, int b, void *workspace, size_t workspace_bytes) {
   FTX_REQUIRE(workspace, "%s: null workspace", who);
-  if (workspace_bytes < ftx_affine_theta_workspace_bytes(b)) {
-    set_error("%s: workspace %zu < required %zu", who, workspace_bytes, ftx_affine_theta_workspace_bytes(b));
-    return FTX_EWORKSPACE;
-  }
+  if (workspace_bytes < ftx_affine_theta_workspace_bytes(b)) return workspace_short(who, workspace_bytes, ftx_affine_theta_workspace_bytes(b));
   return FTX_OK;
 }
 

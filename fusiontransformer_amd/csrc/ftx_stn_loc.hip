@@ -18,6 +18,7 @@
 // Data gradient: float32 over one pass of <= 10 output channels, float64 across the passes.
 // No float atomics anywhere; every order of summation depends on the sizes only, so every output repeats bit for bit.
 #include "ftx_common.h"
+#include "ftx_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -177,8 +178,7 @@ __global__ __launch_bounds__(64) void loc_mean_kernel(const double *__restrict__
   const double *row = part + (int64_t)blockIdx.x * tiles;
   double v = 0.0;
   for (int t = threadIdx.x; t < tiles; t += 64) v += row[t];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  v = wave_sum_down(v);
   if (threadIdx.x == 0) mean[blockIdx.x] = (float)(v * inv);
 }
 
@@ -371,10 +371,7 @@ int loc_wgrad_split(int b, int c, int ph, int pw, int k, int co) {
 
 int loc_workspace(const char *who, void *workspace, size_t have, size_t need) {
   FTX_REQUIRE(workspace, "%s: null workspace", who);
-  if (have < need) {
-    set_error("%s: workspace %zu < required %zu", who, have, need);
-    return FTX_EWORKSPACE;
-  }
+  if (have < need) return workspace_short(who, have, need);
   return FTX_OK;
 }
 
