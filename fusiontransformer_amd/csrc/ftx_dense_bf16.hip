@@ -14,12 +14,6 @@
 
 using namespace ftx;
 
-namespace {
-
-__device__ inline bf16x4 round4(float4 v) { return (bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
-
-}  // namespace
-
 struct DenseBf16 {
   static constexpr const char *gemm_name = "ftx_dense_gemm_bf16", *wgrad_name = "ftx_dense_wgrad_bf16";
   static constexpr const char *patch_name = "ftx_vit_patch_embed_bf16", *tap_name = "ftx_vit_tap_stem_bf16";

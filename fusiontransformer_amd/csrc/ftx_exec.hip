@@ -141,10 +141,11 @@ extern "C" int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const 
     switch (o.kind) {
       case FTX_SPVCNN_OP_CONV_BN: {
         const Layer &L = T.layers[o.layer];
+        const SpconvEntries E = spconv_entries(L);
         const float *res = o.src2 >= 0 ? at(o.src2) : nullptr;
         const int64_t rows_a = rows[F.level[o.src]];
         if (L.kvol == 1) {
-          RUN((L.bf16 ? ftx_rows_gemm_bf16 : ftx_rows_gemm)(src, n, L.weight, 0, nullptr, L.ca, L.co, temp, stream));
+          RUN(E.rows(src, n, L.weight, 0, nullptr, L.ca, L.co, temp, stream));
           RUN(ftx_bn_eval_fwd(temp, res, L.gamma, L.beta, L.mean, L.var, L.eps, n, L.co, o.relu, dst, stream));
           break;
         }
@@ -152,8 +153,8 @@ extern "C" int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const 
         const MapSides side = map_sides(L, M);
         switch (T.routes[i]) {
           case FTX_SPVCNN_ROUTE_DIRECT:
-            RUN((L.bf16 ? ftx_spconv_pairs_gemm_scatter_bf16 : ftx_spconv_pairs_gemm_scatter)(src, rows_a, side.gather, side.scatter, L.weight, 0, M.koff, M.n_pairs, L.ca,
-                                                                                              L.co, L.kvol, temp, n, stream));
+            RUN(E.scatter(src, rows_a, side.gather, side.scatter, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, temp, n,
+                          stream));
             RUN(ftx_bn_eval_fwd(temp, res, L.gamma, L.beta, L.mean, L.var, L.eps, n, L.co, o.relu, dst, stream));
             break;
           case FTX_SPVCNN_ROUTE_OSTAT:
@@ -161,8 +162,7 @@ extern "C" int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const 
             RUN(ftx_bn_eval_fwd(temp, res, L.gamma, L.beta, L.mean, L.var, L.eps, n, L.co, o.relu, dst, stream));
             break;
           default:   // pairs, or the empty map (no pair rows: every output row reduces to zero before the BatchNorm)
-            RUN((L.bf16 ? ftx_spconv_pairs_gemm_bf16 : ftx_spconv_pairs_gemm)(src, rows_a, side.gather, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, temp,
-                                                                              stream));
+            RUN(E.pairs(src, rows_a, side.gather, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, temp, stream));
             RUN(ftx_spconv_reduce_bn_eval(temp, side.dst_pos, n, L.co, L.kvol, res, L.gamma, L.beta, L.mean, L.var, L.eps, o.relu, dst, stream));
             break;
         }
@@ -170,7 +170,8 @@ extern "C" int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const 
       }
       case FTX_SPVCNN_OP_LINEAR_BN: {
         const Layer &L = T.layers[o.layer];
-        RUN((L.bf16 ? ftx_rows_gemm_bf16 : ftx_rows_gemm)(src, n, L.weight, 1, L.bias, L.ca, L.co, temp, stream));
+        const SpconvEntries E = spconv_entries(L);
+        RUN(E.rows(src, n, L.weight, 1, L.bias, L.ca, L.co, temp, stream));
         RUN(ftx_bn_eval_fwd(temp, nullptr, L.gamma, L.beta, L.mean, L.var, L.eps, n, L.co, o.relu, dst, stream));
         break;
       }

@@ -109,6 +109,7 @@ int Exec::fwd_op(int i, Carve &cv) const {
     case FTX_SPVCNN_OP_CONV_BN:
     case FTX_SPVCNN_OP_LINEAR_BN: {
       const Layer &L = T.layers[o.layer];
+      const SpconvEntries E = spconv_entries(L);
       const bool linear = o.kind == FTX_SPVCNN_OP_LINEAR_BN;
       const float momentum = launch ? tlayers[o.layer].momentum : 0.f;
       float *x = (float *)(base + (uintptr_t)P.x_off[i]);
@@ -121,7 +122,7 @@ int Exec::fwd_op(int i, Carve &cv) const {
       const int64_t bn_ws_bytes = (int64_t)ftx_bn_workspace_bytes(n, L.co);
       if (r == FTX_SPVCNN_ROUTE_ROWS) {
         void *ws = cv.take(bn_ws_bytes);
-        RUN((L.bf16 ? ftx_rows_gemm_bf16 : ftx_rows_gemm)(src, n, L.weight, linear ? 1 : 0, linear ? L.bias : nullptr, L.ca, L.co, x, stream));
+        RUN(E.rows(src, n, L.weight, linear ? 1 : 0, linear ? L.bias : nullptr, L.ca, L.co, x, stream));
         RUN(ftx_bn_train_fwd(x, res, L.gamma, L.beta, rm, rv, momentum, L.eps, n, L.co, o.relu, y, mean, invstd, ws, (size_t)bn_ws_bytes, stream));
         break;
       }
@@ -137,7 +138,7 @@ int Exec::fwd_op(int i, Carve &cv) const {
         if (r == FTX_SPVCNN_ROUTE_OSTAT) {
           RUN(ftx_spconv_ostat(src, rows_a, M.nbr, n, L.weight, 0, 0, L.ca, L.co, L.kvol, x, part, nb, stream));
         } else {
-          RUN((L.bf16 ? ftx_spconv_pairs_gemm_bf16 : ftx_spconv_pairs_gemm)(src, rows_a, side.gather, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, tmp, stream));
+          RUN(E.pairs(src, rows_a, side.gather, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, tmp, stream));
           RUN(ftx_spconv_reduce_stats(tmp, side.dst_pos, n, L.co, L.kvol, x, part, nb, stream));
         }
         RUN(ftx_bn_train_fwd_totals(x, res, L.gamma, L.beta, rm, rv, momentum, L.eps, n, L.co, o.relu, y, mean, invstd, totals, stream));
@@ -146,10 +147,9 @@ int Exec::fwd_op(int i, Carve &cv) const {
         float *tmp = (float *)cv.take(r == FTX_SPVCNN_ROUTE_EMPTY ? 4 * M.n_pairs * (int64_t)L.co : 0);
         void *ws = cv.take(bn_ws_bytes);
         if (r == FTX_SPVCNN_ROUTE_DIRECT) {
-          RUN((L.bf16 ? ftx_spconv_pairs_gemm_scatter_bf16 : ftx_spconv_pairs_gemm_scatter)(src, rows_a, side.gather, side.scatter, L.weight, 0, M.koff, M.n_pairs, L.ca,
-                                                                                            L.co, L.kvol, x, n, stream));
+          RUN(E.scatter(src, rows_a, side.gather, side.scatter, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, x, n, stream));
         } else {
-          RUN((L.bf16 ? ftx_spconv_pairs_gemm_bf16 : ftx_spconv_pairs_gemm)(src, rows_a, side.gather, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, tmp, stream));
+          RUN(E.pairs(src, rows_a, side.gather, L.weight, 0, M.koff, M.n_pairs, L.ca, L.co, L.kvol, tmp, stream));
           RUN(ftx_spconv_reduce(tmp, side.dst_pos, n, L.co, L.kvol, x, stream));
         }
         RUN(ftx_bn_train_fwd(x, res, L.gamma, L.beta, rm, rv, momentum, L.eps, n, L.co, o.relu, y, mean, invstd, ws, (size_t)bn_ws_bytes, stream));
@@ -193,6 +193,7 @@ int Exec::bwd_op(int i, Carve &cv) const {
     case FTX_SPVCNN_OP_CONV_BN:
     case FTX_SPVCNN_OP_LINEAR_BN: {
       const Layer &L = T.layers[o.layer];
+      const SpconvEntries E = spconv_entries(L);
       const bool linear = o.kind == FTX_SPVCNN_OP_LINEAR_BN;
       const bool has_res = !linear && o.src2 >= 0;
       const bool need_data = o.src != FTX_SPVCNN_SLOT_INPUT;
@@ -216,19 +217,17 @@ int Exec::bwd_op(int i, Carve &cv) const {
       if (T.routes[i] == FTX_SPVCNN_ROUTE_ROWS) {
         void *wg_ws = cv.take(wgrad_ws_bytes(n, L.ca, L.co, 1));
         const size_t wg_bytes = (size_t)wgrad_ws_bytes(n, L.ca, L.co, 1);
-        auto gemm = L.bf16 ? ftx_rows_gemm_bf16 : ftx_rows_gemm;
-        auto wgrad = L.bf16 ? ftx_spconv_pairs_wgrad_bf16 : ftx_spconv_pairs_wgrad;
         if (linear) {   // weight (co, ca): gx @ W, dW = gx^T x, dbias = column sums of gx
-          if (need_data) RUN(gemm(gx, n, L.weight, 0, nullptr, L.co, L.ca, tsrc.ptr, stream));
-          RUN(wgrad(gx, n, nullptr, src, n, nullptr, nullptr, n, L.co, L.ca, 1, TL.dweight, wg_ws, wg_bytes, stream));
+          if (need_data) RUN(E.rows(gx, n, L.weight, 0, nullptr, L.co, L.ca, tsrc.ptr, stream));
+          RUN(E.wgrad(gx, n, nullptr, src, n, nullptr, nullptr, n, L.co, L.ca, 1, TL.dweight, wg_ws, wg_bytes, stream));
           if (L.bias) {
             const int64_t cs_bytes = (int64_t)ftx_colsum_workspace_bytes(n, L.co);
             void *cs_ws = cv.take(cs_bytes);
             RUN(ftx_colsum(gx, n, L.co, TL.dbias, cs_ws, (size_t)cs_bytes, stream));
           }
         } else {        // kernel (ca, co): gx @ W^T, dW = x^T gx
-          if (need_data) RUN(gemm(gx, n, L.weight, 1, nullptr, L.co, L.ca, tsrc.ptr, stream));
-          RUN(wgrad(src, n, nullptr, gx, n, nullptr, nullptr, n, L.ca, L.co, 1, TL.dweight, wg_ws, wg_bytes, stream));
+          if (need_data) RUN(E.rows(gx, n, L.weight, 1, nullptr, L.co, L.ca, tsrc.ptr, stream));
+          RUN(E.wgrad(src, n, nullptr, gx, n, nullptr, nullptr, n, L.ca, L.co, 1, TL.dweight, wg_ws, wg_bytes, stream));
         }
       } else {
         const Map &M = T.maps[o.map];
@@ -241,14 +240,14 @@ int Exec::bwd_op(int i, Carve &cv) const {
           if (launch && n_src > 0 && hipMemsetAsync(tsrc.ptr, 0, sizeof(float) * n_src * L.ca, (hipStream_t)stream) != hipSuccess)
             return check_launch("ftx_spvcnn_train_bwd memset");
         } else if (gr == FTX_SPVCNN_ROUTE_DIRECT) {
-          RUN((L.bf16 ? ftx_spconv_pairs_gemm_scatter_bf16 : ftx_spconv_pairs_gemm_scatter)(gx, n, side.scatter, side.gather, L.weight, 1, M.koff, M.n_pairs, L.co, L.ca,
-                                                                                            L.kvol, tsrc.ptr, n_src, stream));
+          RUN(E.scatter(gx, n, side.scatter, side.gather, L.weight, 1, M.koff, M.n_pairs, L.co, L.ca, L.kvol, tsrc.ptr, n_src,
+                        stream));
         } else if (gr == FTX_SPVCNN_ROUTE_PAIRS) {
-          RUN((L.bf16 ? ftx_spconv_pairs_gemm_bf16 : ftx_spconv_pairs_gemm)(gx, n, side.scatter, L.weight, 1, M.koff, M.n_pairs, L.co, L.ca, L.kvol, tmp, stream));
+          RUN(E.pairs(gx, n, side.scatter, L.weight, 1, M.koff, M.n_pairs, L.co, L.ca, L.kvol, tmp, stream));
           RUN(ftx_spconv_reduce(tmp, side.src_pos, n_src, L.ca, L.kvol, tsrc.ptr, stream));
         }
-        RUN((L.bf16 ? ftx_spconv_pairs_wgrad_bf16 : ftx_spconv_pairs_wgrad)(src, n_src, side.gather, gx, n, side.scatter, M.koff, M.n_pairs, L.ca, L.co, L.kvol, TL.dweight,
-                                                                            wg_ws, (size_t)wg_bytes, stream));
+        RUN(E.wgrad(src, n_src, side.gather, gx, n, side.scatter, M.koff, M.n_pairs, L.ca, L.co, L.kvol, TL.dweight, wg_ws, (size_t)wg_bytes,
+                    stream));
       }
       if (need_data) RUN(commit(tsrc, o.src));
       break;

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include "ftx_bn_eval_op.h"
 #include "ftx_index_ops.h"
+#include "ftx_lastblock.h"
 #include "ftx_spconv_common.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -107,149 +108,8 @@ extern "C" int ftx_kernel_map_pairs(const int32_t *nbr, int64_t n_out, int64_t n
 // ---------------------------------------------------------------------------------------
 // phase 1: tmp[p,:] = A[gather[p],:] @ Wk(p)        (tiles of 128 pairs of one offset)
 // ---------------------------------------------------------------------------------------
-constexpr int AS_STRIDE = 36;  // floats
-
-// NT = 32-column tiles per wave; a wave owns one 32-pair row tile of the block's kPairTile pairs.
-// Measured on MI355X (profiles/r01_spconv_layer_micro.txt workload): 256-pair tiles (RT = 2 row tiles per wave) are 5-30 % SLOWER than
-// 128-pair tiles on every layer -- the extra accumulators cut occupancy to 1-2 waves per SIMD and the kernel is latency-, not
-// W-traffic-bound: RT = 1 everywhere, so the kernel has no such parameter.
-template <int NT>
-__global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict__ A, int64_t rows_a, const int32_t *__restrict__ gather,
-                                                         const float *__restrict__ W, int w_transposed, const int32_t *__restrict__ koff,
-                                                         int ca, int co, int kvol, float *__restrict__ tmp, const float *__restrict__ bias,
-                                                         int64_t n_dense, const int32_t *__restrict__ scatter, int64_t rows_out) {
-  // gather == nullptr: dense mode, tmp[r,:] = A[r,:] @ W (+ bias) for r < n_dense (kvol = 1)
-  // scatter != nullptr: the result row of pair p goes to row scatter[p] of `tmp` (rows_out rows) instead of row p: for maps in
-  // which every destination row receives exactly ONE pair the convolution is this one launch, with no tmp and no reduce pass
-  constexpr int BN = 32 * NT;
-  constexpr int BS_STRIDE = AS_STRIDE;         // W chunk kept as Bs[n][k]: the reduction index is contiguous for BOTH operands
-  constexpr int A_PASSES = kPairAPasses;
-  constexpr int B_PASSES = NT;                 // kPairBK * BN / 4 float4 per W chunk = NT * 256
-
-  __shared__ __attribute__((aligned(16))) float As[kPairTile * AS_STRIDE];
-  __shared__ __attribute__((aligned(16))) float Bs[BN * BS_STRIDE];
-  __shared__ int s_tile[3];
-
-  const int tid = threadIdx.x;
-  gemm_tile_scan(koff, kvol, n_dense, gather == nullptr, s_tile);
-  __syncthreads();
-  const int k = s_tile[0];
-  if (k < 0) return;  // surplus block of the upper-bound grid
-  const int p0 = s_tile[1], cnt = s_tile[2];
-
-  const int wave = tid >> 6, lane = tid & 63;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int n0 = blockIdx.y * BN;
-  const int arow = tid >> 3, acol = (tid & 7) * 4;
-
-  const bool kfull = (ca % kPairBK) == 0;
-  int32_t src[A_PASSES];
-  pair_gather_rows(gather, p0, cnt, rows_a, src);
-  const float *Wk = W + (int64_t)k * ca * co;
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[j][g] = 0.f;
-
-  float4 ra[A_PASSES], rb[B_PASSES];
-  // The chunk loader stays a lambda of each kernel, the same text in both families: as a function of ftx_spconv_common.h the compiler
-  // ordered its instructions differently and the 32 -> 32 layers ran 4-5 % slower (profiles/spconv_shared_host.txt, section 1).
-  auto load_chunk = [&](int c0) {
-    if (kfull) {
-#pragma unroll
-      for (int p = 0; p < A_PASSES; ++p) ra[p] = *(const float4 *)&A[(int64_t)src[p] * ca + c0 + acol];
-#pragma unroll
-      for (int q = 0; q < B_PASSES; ++q) {
-        if (!w_transposed) {  // W[k] stored (ca, co): 16 bytes along co; a wave covers 8 k-rows x 128 B
-          int kk = ((tid >> 6) << 3) + (tid & 7), n4 = n0 + (q * 8 + ((tid >> 3) & 7)) * 4;
-          n4 = n4 + 4 <= co ? n4 : co - 4;
-          rb[q] = *(const float4 *)&Wk[(int64_t)(c0 + kk) * co + n4];
-        } else {              // W[k] stored (co, ca): 16 bytes along ca
-          int e = q * 256 + tid;
-          int nn = n0 + (e >> 3), k4 = (e & 7) * 4;
-          nn = nn < co ? nn : co - 1;
-          rb[q] = *(const float4 *)&Wk[(int64_t)nn * ca + c0 + k4];
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int p = 0; p < A_PASSES; ++p) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c0 + acol < ca) v = *(const float4 *)&A[(int64_t)src[p] * ca + c0 + acol];
-      ra[p] = v;
-    }
-#pragma unroll
-    for (int q = 0; q < B_PASSES; ++q) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (!w_transposed) {
-        int kk = ((tid >> 6) << 3) + (tid & 7), n4 = (q * 8 + ((tid >> 3) & 7)) * 4;
-        if (c0 + kk < ca && n0 + n4 < co) v = *(const float4 *)&Wk[(int64_t)(c0 + kk) * co + n0 + n4];
-      } else {
-        int e = q * 256 + tid;
-        int nn = e >> 3, k4 = (e & 7) * 4;
-        if (n0 + nn < co && c0 + k4 < ca) v = *(const float4 *)&Wk[(int64_t)(n0 + nn) * ca + c0 + k4];
-      }
-      rb[q] = v;
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int p = 0; p < A_PASSES; ++p) *(float4 *)&As[(p * 32 + arow) * AS_STRIDE + acol] = ra[p];
-#pragma unroll
-    for (int q = 0; q < B_PASSES; ++q) {
-      if (!w_transposed) {  // transposing store; (n4i * 144 + kl) mod 64 banks: 2-way conflicts at worst
-        int kk = ((tid >> 6) << 3) + (tid & 7), n4 = (q * 8 + ((tid >> 3) & 7)) * 4;
-        Bs[(n4 + 0) * BS_STRIDE + kk] = rb[q].x;
-        Bs[(n4 + 1) * BS_STRIDE + kk] = rb[q].y;
-        Bs[(n4 + 2) * BS_STRIDE + kk] = rb[q].z;
-        Bs[(n4 + 3) * BS_STRIDE + kk] = rb[q].w;
-      } else {
-        int e = q * 256 + tid;
-        int nn = e >> 3, k4 = (e & 7) * 4;
-        *(float4 *)&Bs[nn * BS_STRIDE + k4] = rb[q];
-      }
-    }
-  };
-
-  load_chunk(0);
-  for (int c0 = 0; c0 < ca; c0 += kPairBK) {
-    store_chunk();
-    __syncthreads();
-    if (c0 + kPairBK < ca) load_chunk(c0 + kPairBK);  // next chunk's global loads fly under the MFMAs
-    // lane (l31, half) owns k = 8t + 4*half + s of both operands: one ds_read_b128 per operand row feeds 4 MFMAs.
-    // The fragments of step t+1 are in flight while the MFMAs of step t issue.
-    const float *arow_p = &As[(wave * 32 + l31) * AS_STRIDE + 4 * half];
-    const float *brow_p = &Bs[l31 * BS_STRIDE + 4 * half];
-    float af[2][4], bf[2][NT][4];
-    auto load_frag = [&](int buf, int t) {
-      float4 a = *(const float4 *)(arow_p + 8 * t);
-      af[buf][0] = a.x; af[buf][1] = a.y; af[buf][2] = a.z; af[buf][3] = a.w;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        float4 b = *(const float4 *)(brow_p + j * 32 * BS_STRIDE + 8 * t);
-        bf[buf][j][0] = b.x; bf[buf][j][1] = b.y; bf[buf][j][2] = b.z; bf[buf][j][3] = b.w;
-      }
-    };
-    load_frag(0, 0);
-#pragma unroll
-    for (int t = 0; t < kPairBK / 8; ++t) {
-      if (t + 1 < kPairBK / 8) load_frag((t + 1) & 1, t + 1);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[t & 1][j][s], af[t & 1][s], acc[j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  pair_gemm_epilogue<NT>(acc, p0, cnt, n0, gather, rows_a, scatter, rows_out, bias, co, tmp);
-}
-
-#include "ftx_lastblock.h"
-
-// One pair-GEMM kernel ships.  The LDS-DMA, producer / consumer and bf16x3 variants of rounds 1-2 each tied or lost against it
+// pairs_gemm_kernel<SpconvF32, NT> of ftx_spconv_common.h, the body that both families instantiate.  One pair-GEMM kernel ships: the
+// LDS-DMA, producer / consumer and bf16x3 variants of rounds 1-2 each tied or lost against it
 // (DESIGN.md section 8); their sources live under tools/probes/spconv_variants/ and are not part of libftx.so.
 
 // ---------------------------------------------------------------------------------------
@@ -604,10 +464,13 @@ struct SpconvF32 {
   // .vgpr_count 60 / 96-104 / 128-136 / 156 / 184-236 / 316
   static constexpr int wgrad_blocks[4][4] = {{8, 4, 3, 3}, {5, 3, 2, 2}, {4, 2, 1, 2}, {3, 2, 2, 2}};
   static constexpr int wgrad_step = 2 * WG_BR;
+  using gemm_lds_t = float;
+  static constexpr int gemm_stride = 36;   // floats per LDS row: a lane's four-MFMA fragment is ONE ds_read_b128, conflict-free
+  static constexpr bool gemm_frag_ptrs_first = false;
   template <int NT>
   static void gemm(dim3 grid, hipStream_t st, const PairsGemmArgs &a) {
-    pairs_gemm_kernel<NT><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.gather, a.W, a.w_transposed, a.koff, a.ca, a.co, a.kvol, a.out, a.bias, a.n_dense,
-                                                a.scatter, a.rows_out);
+    pairs_gemm_kernel<SpconvF32, NT><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.gather, a.W, a.w_transposed, a.koff, a.ca, a.co, a.kvol, a.out, a.bias,
+                                                           a.n_dense, a.scatter, a.rows_out);
   }
   template <int MI, int NI, int WMG, int WNG>
   static void wgrad(dim3 grid, hipStream_t st, const PairsWgradArgs &a) {

@@ -11,137 +11,17 @@
 //
 // Operand maps of v_mfma_f32_32x32x16_bf16 (cdna_hip_programming.md section 3): lane (r = lane & 31, h = lane >> 5) holds A[row r][k]
 // and B[k][col r] for k = 8h + j, j = 0..7, of each 16-wide k-step; accumulator register g of the lane is C[(g&3) + 8(g>>2) + 4h][r],
-// the same layout as the f32 MFMA, so the pair GEMM shares its epilogue with the fp32 kernel (ftx_spconv_common.h, with everything
-// else the two families have in common).  Both operands are staged as bf16 LDS images in which the reduction index is contiguous: one
+// the same layout as the f32 MFMA, so the pair GEMM is one kernel body and one epilogue for both families (ftx_spconv_common.h, with
+// everything else the two families have in common).  Both operands are staged as bf16 LDS images in which the reduction index is contiguous: one
 // ds_read_b128 per operand and k-step.
 #include "ftx_spconv_common.h"
 
 using namespace ftx;
 
-__device__ inline bf16x4 round4(float4 v) { return (bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
-
 // ---------------------------------------------------------------------------------------
-// tmp[p,:] = bf16(A[gather[p],:]) @ bf16(Wk(p))      (tiles of 128 pairs of one offset; the forms of pairs_gemm_kernel)
+// tmp[p,:] = bf16(A[gather[p],:]) @ bf16(Wk(p))      (tiles of 128 pairs of one offset; the forms of the fp32 family):
+// pairs_gemm_kernel<SpconvBf16, NT> of ftx_spconv_common.h, the body that both families instantiate
 // ---------------------------------------------------------------------------------------
-constexpr int GB_STRIDE = 40;   // bf16 per LDS row (80 B): the 16 lanes of one ds_read_b128 phase cover 16 disjoint bank quads
-
-// NT = 32-column tiles per block.  W is the MFMA's row operand (rows = output channels, columns = pairs), as in the fp32 kernel.
-template <int NT>
-__global__ __launch_bounds__(256) void pairs_gemm_bf16_kernel(const float *__restrict__ A, int64_t rows_a, const int32_t *__restrict__ gather,
-                                                              const float *__restrict__ W, int w_transposed, const int32_t *__restrict__ koff,
-                                                              int ca, int co, int kvol, float *__restrict__ tmp, const float *__restrict__ bias,
-                                                              int64_t n_dense, const int32_t *__restrict__ scatter, int64_t rows_out) {
-  constexpr int BN = 32 * NT;
-  constexpr int A_PASSES = kPairAPasses;
-  constexpr int B_PASSES = NT;     // kPairBK * BN / 4 float4 = NT * 256; a step of kPairBK channels is two k-steps of 16
-  __shared__ __attribute__((aligned(16))) __bf16 As[kPairTile * GB_STRIDE];   // [pair][k]
-  __shared__ __attribute__((aligned(16))) __bf16 Bs[BN * GB_STRIDE];        // [n][k]
-  __shared__ int s_tile[3];
-
-  const int tid = threadIdx.x;
-  gemm_tile_scan(koff, kvol, n_dense, gather == nullptr, s_tile);
-  __syncthreads();
-  const int k = s_tile[0];
-  if (k < 0) return;  // surplus block of the upper-bound grid
-  const int p0 = s_tile[1], cnt = s_tile[2];
-
-  const int wave = tid >> 6, lane = tid & 63;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int n0 = blockIdx.y * BN;
-  const int arow = tid >> 3, acol = (tid & 7) * 4;
-
-  const bool kfull = (ca % kPairBK) == 0;
-  int32_t src[A_PASSES];
-  pair_gather_rows(gather, p0, cnt, rows_a, src);
-  const float *Wk = W + (int64_t)k * ca * co;
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[j][g] = 0.f;
-
-  float4 ra[A_PASSES], rb[B_PASSES];
-  // The chunk loader stays a lambda of each kernel, the same text in both families: as a function of ftx_spconv_common.h the compiler
-  // ordered its instructions differently and the 32 -> 32 layers ran 4-5 % slower (profiles/spconv_shared_host.txt, section 1).
-  auto load_chunk = [&](int c0) {
-    if (kfull) {
-#pragma unroll
-      for (int p = 0; p < A_PASSES; ++p) ra[p] = *(const float4 *)&A[(int64_t)src[p] * ca + c0 + acol];
-#pragma unroll
-      for (int q = 0; q < B_PASSES; ++q) {
-        if (!w_transposed) {  // W[k] stored (ca, co): 16 bytes along co
-          int kk = ((tid >> 6) << 3) + (tid & 7), n4 = n0 + (q * 8 + ((tid >> 3) & 7)) * 4;
-          n4 = n4 + 4 <= co ? n4 : co - 4;
-          rb[q] = *(const float4 *)&Wk[(int64_t)(c0 + kk) * co + n4];
-        } else {              // W[k] stored (co, ca): 16 bytes along ca
-          int e = q * 256 + tid;
-          int nn = n0 + (e >> 3), k4 = (e & 7) * 4;
-          nn = nn < co ? nn : co - 1;
-          rb[q] = *(const float4 *)&Wk[(int64_t)nn * ca + c0 + k4];
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int p = 0; p < A_PASSES; ++p) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c0 + acol < ca) v = *(const float4 *)&A[(int64_t)src[p] * ca + c0 + acol];
-      ra[p] = v;
-    }
-#pragma unroll
-    for (int q = 0; q < B_PASSES; ++q) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (!w_transposed) {
-        int kk = ((tid >> 6) << 3) + (tid & 7), n4 = (q * 8 + ((tid >> 3) & 7)) * 4;
-        if (c0 + kk < ca && n0 + n4 < co) v = *(const float4 *)&Wk[(int64_t)(c0 + kk) * co + n0 + n4];
-      } else {
-        int e = q * 256 + tid;
-        int nn = e >> 3, k4 = (e & 7) * 4;
-        if (n0 + nn < co && c0 + k4 < ca) v = *(const float4 *)&Wk[(int64_t)(n0 + nn) * ca + c0 + k4];
-      }
-      rb[q] = v;
-    }
-  };
-  // the ONE place the operands are rounded: fp32 registers -> bf16 LDS images
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int p = 0; p < A_PASSES; ++p) *(bf16x4 *)&As[(p * 32 + arow) * GB_STRIDE + acol] = round4(ra[p]);
-#pragma unroll
-    for (int q = 0; q < B_PASSES; ++q) {
-      if (!w_transposed) {  // transposing store
-        int kk = ((tid >> 6) << 3) + (tid & 7), n4 = (q * 8 + ((tid >> 3) & 7)) * 4;
-        const bf16x4 v = round4(rb[q]);
-        Bs[(n4 + 0) * GB_STRIDE + kk] = v[0];
-        Bs[(n4 + 1) * GB_STRIDE + kk] = v[1];
-        Bs[(n4 + 2) * GB_STRIDE + kk] = v[2];
-        Bs[(n4 + 3) * GB_STRIDE + kk] = v[3];
-      } else {
-        int e = q * 256 + tid;
-        int nn = e >> 3, k4 = (e & 7) * 4;
-        *(bf16x4 *)&Bs[nn * GB_STRIDE + k4] = round4(rb[q]);
-      }
-    }
-  };
-
-  const __bf16 *ap = &As[(wave * 32 + l31) * GB_STRIDE + 8 * half];
-  const __bf16 *bp = &Bs[l31 * GB_STRIDE + 8 * half];
-  load_chunk(0);
-  for (int c0 = 0; c0 < ca; c0 += kPairBK) {
-    store_chunk();
-    __syncthreads();
-    if (c0 + kPairBK < ca) load_chunk(c0 + kPairBK);  // next chunk's global loads fly under the MFMAs
-#pragma unroll
-    for (int s = 0; s < kPairBK / 16; ++s) {
-      const bf16x8 a = *(const bf16x8 *)(ap + 16 * s);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) acc[j] = mfma_bf16(*(const bf16x8 *)(bp + j * 32 * GB_STRIDE + 16 * s), a, acc[j]);
-    }
-    __syncthreads();
-  }
-
-  pair_gemm_epilogue<NT>(acc, p0, cnt, n0, gather, rows_a, scatter, rows_out, bias, co, tmp);
-}
 
 // ---------------------------------------------------------------------------------------
 // weight gradient: dW[k] = sum_{p in k} bf16(A[idx_a[p],:])^T @ bf16(G[idx_g[p],:])
@@ -322,10 +202,13 @@ struct SpconvBf16 {
   // .vgpr_count 64 / 100-104 / 136-152 / 188-244 / 312
   static constexpr int wgrad_blocks[4][4] = {{8, 4, 3, 3}, {4, 3, 2, 2}, {3, 2, 1, 2}, {3, 2, 2, 2}};
   static constexpr int wgrad_step = 2 * WB_BR;
+  using gemm_lds_t = __bf16;
+  static constexpr int gemm_stride = 40;   // bf16 per LDS row (80 B): the 16 lanes of one ds_read_b128 phase cover 16 disjoint bank quads
+  static constexpr bool gemm_frag_ptrs_first = true;
   template <int NT>
   static void gemm(dim3 grid, hipStream_t st, const PairsGemmArgs &a) {
-    pairs_gemm_bf16_kernel<NT><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.gather, a.W, a.w_transposed, a.koff, a.ca, a.co, a.kvol, a.out, a.bias, a.n_dense,
-                                                     a.scatter, a.rows_out);
+    pairs_gemm_kernel<SpconvBf16, NT><<<grid, 256, 0, st>>>(a.A, a.rows_a, a.gather, a.W, a.w_transposed, a.koff, a.ca, a.co, a.kvol, a.out, a.bias,
+                                                            a.n_dense, a.scatter, a.rows_out);
   }
   template <int MI, int NI, int WMG, int WNG>
   static void wgrad(dim3 grid, hipStream_t st, const PairsWgradArgs &a) {

@@ -1,9 +1,12 @@
 // What the two sparse-convolution families share (ftx_spconv.hip: exact fp32 MFMA; ftx_spconv_bf16.hip: bf16 operands): the tile scan,
-// the gather clamp and the row epilogue of the pair GEMM, the index staging and wave-group reduce of the weight gradient, its ordered second
-// pass, and the host layer behind the extern "C" entries.  A family brings its LDS images, its MFMA loops, its weight-gradient
-// epilogue and a small description (SpconvF32, SpconvBf16): the entry names that front its messages, its occupancy table, its
-// tile-length step and two launch hooks.  Nothing here is selected by process-wide mutable state or by a device query: tile shapes,
-// workspace sizes and summation trees are functions of the arguments alone.
+// the whole pair-GEMM kernel (one body, the family's few lines in place under `if constexpr`), the index staging and wave-group reduce of
+// the weight gradient, its ordered second pass, and the host layer behind the extern "C" entries.  The weight-gradient kernels stay two:
+// their staging differs by design (fp32: row-major rows, interleaved sub-tiles, two register stages; bf16: transposed k-contiguous
+// images, one stage), and one body would be two kernels under one name.  A family brings exactly: its weight-gradient kernel, and a
+// description (SpconvF32, SpconvBf16) with the entry names that front its messages, the pair GEMM's LDS element type, row stride and
+// fragment-pointer placement, the weight gradient's occupancy table and tile-length step, and two launch hooks.  Nothing here is
+// selected by process-wide mutable state or by a device query: tile shapes, workspace sizes and summation trees are functions of the
+// arguments alone.
 #pragma once
 #include "ftx_common.h"
 #include "ftx_mfma.h"
@@ -69,7 +72,7 @@ __device__ __forceinline__ void gemm_tile_scan(const int32_t *__restrict__ koff,
 
 // ---------------------------------------------------------------------------------------
 // device: the gathered rows of the pair GEMM.  Thread tid holds float4 (row p * 32 + (tid >> 3), channels (tid & 7) * 4) of the A
-// chunk; the chunk loader that uses these rows is a lambda of each kernel (see there).
+// chunk; the chunk loader that uses these rows is a lambda of the kernel (see there).
 //
 // Gathers are unconditional loads from addresses that are always valid: rows past the end of the tile (and malformed indices) read
 // row 0 -- what they produce lands in accumulator columns the epilogue never stores (or zeroes) -- and a column tile that sticks out
@@ -130,6 +133,193 @@ __device__ __forceinline__ void pair_gemm_epilogue(const f32x16 (&acc)[NT], int 
       }
     }
 }
+
+}  // namespace ftx
+
+// ---------------------------------------------------------------------------------------
+// device: the pair GEMM of both families.  tmp[p,:] = A[gather[p],:] @ Wk(p) over tiles of kPairTile pairs of one offset; the fp32
+// family multiplies the stored values on v_mfma_f32_32x32x2_f32, the bf16 family rounds both operands to bf16 on their way into LDS
+// and multiplies on v_mfma_f32_32x32x16_bf16.  The lines that differ sit in place under `if constexpr`.  F brings
+//   F::gemm_lds_t           element type of the two LDS images (float / __bf16)
+//   F::gemm_stride          elements per LDS row of kPairBK channels
+//   F::gemm_frag_ptrs_first whether a lane's fragment pointers are formed before the first chunk load or inside the chunk loop: the
+//                           same values either way, but the placement decides how the compiler orders the stream, and each family
+//                           keeps the one its kernel was measured with (profiles/spconv_one_gemm_body.txt)
+// NT = 32-column tiles per wave; a wave owns one 32-pair row tile of the block's kPairTile pairs.  W is the MFMA's row operand (rows =
+// output channels, columns = pairs) in both families.
+// Measured on MI355X (profiles/r01_spconv_layer_micro.txt workload): 256-pair tiles (RT = 2 row tiles per wave) are 5-30 % SLOWER than
+// 128-pair tiles on every layer -- the extra accumulators cut occupancy to 1-2 waves per SIMD and the kernel is latency-, not
+// W-traffic-bound: RT = 1 everywhere, so the kernel has no such parameter.
+// ---------------------------------------------------------------------------------------
+template <class F, int NT>
+__global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict__ A, int64_t rows_a, const int32_t *__restrict__ gather,
+                                                         const float *__restrict__ W, int w_transposed, const int32_t *__restrict__ koff,
+                                                         int ca, int co, int kvol, float *__restrict__ tmp, const float *__restrict__ bias,
+                                                         int64_t n_dense, const int32_t *__restrict__ scatter, int64_t rows_out) {
+  using namespace ftx;
+  // gather == nullptr: dense mode, tmp[r,:] = A[r,:] @ W (+ bias) for r < n_dense (kvol = 1)
+  // scatter != nullptr: the result row of pair p goes to row scatter[p] of `tmp` (rows_out rows) instead of row p: for maps in
+  // which every destination row receives exactly ONE pair the convolution is this one launch, with no tmp and no reduce pass
+  using T = typename F::gemm_lds_t;
+  constexpr bool BF16 = std::is_same<T, __bf16>::value;
+  constexpr int BN = 32 * NT;
+  constexpr int STRIDE = F::gemm_stride;       // both images: the W chunk is kept as Bs[n][k], the reduction index is contiguous for BOTH operands
+  constexpr int FRAG = 16 / sizeof(T);         // elements of one ds_read_b128
+  constexpr int A_PASSES = kPairAPasses;
+  constexpr int B_PASSES = NT;                 // kPairBK * BN / 4 float4 per W chunk = NT * 256
+
+  __shared__ __attribute__((aligned(16))) T As[kPairTile * STRIDE];   // [pair][k]
+  __shared__ __attribute__((aligned(16))) T Bs[BN * STRIDE];          // [n][k]
+  __shared__ int s_tile[3];
+
+  const int tid = threadIdx.x;
+  gemm_tile_scan(koff, kvol, n_dense, gather == nullptr, s_tile);
+  __syncthreads();
+  const int k = s_tile[0];
+  if (k < 0) return;  // surplus block of the upper-bound grid
+  const int p0 = s_tile[1], cnt = s_tile[2];
+
+  const int wave = tid >> 6, lane = tid & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int n0 = blockIdx.y * BN;
+  const int arow = tid >> 3, acol = (tid & 7) * 4;
+
+  const bool kfull = (ca % kPairBK) == 0;
+  int32_t src[A_PASSES];
+  pair_gather_rows(gather, p0, cnt, rows_a, src);
+  const float *Wk = W + (int64_t)k * ca * co;
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[j][g] = 0.f;
+
+  float4 ra[A_PASSES], rb[B_PASSES];
+  // The chunk loader is a lambda of the kernel and must stay one: as a function of this header the compiler ordered its instructions
+  // differently and the 32 -> 32 layers ran 4-5 % slower (profiles/spconv_shared_host.txt, section 1).
+  auto load_chunk = [&](int c0) {
+    if (kfull) {
+#pragma unroll
+      for (int p = 0; p < A_PASSES; ++p) ra[p] = *(const float4 *)&A[(int64_t)src[p] * ca + c0 + acol];
+#pragma unroll
+      for (int q = 0; q < B_PASSES; ++q) {
+        if (!w_transposed) {  // W[k] stored (ca, co): 16 bytes along co; a wave covers 8 k-rows x 128 B
+          int kk = ((tid >> 6) << 3) + (tid & 7), n4 = n0 + (q * 8 + ((tid >> 3) & 7)) * 4;
+          n4 = n4 + 4 <= co ? n4 : co - 4;
+          rb[q] = *(const float4 *)&Wk[(int64_t)(c0 + kk) * co + n4];
+        } else {              // W[k] stored (co, ca): 16 bytes along ca
+          int e = q * 256 + tid;
+          int nn = n0 + (e >> 3), k4 = (e & 7) * 4;
+          nn = nn < co ? nn : co - 1;
+          rb[q] = *(const float4 *)&Wk[(int64_t)nn * ca + c0 + k4];
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int p = 0; p < A_PASSES; ++p) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c0 + acol < ca) v = *(const float4 *)&A[(int64_t)src[p] * ca + c0 + acol];
+      ra[p] = v;
+    }
+#pragma unroll
+    for (int q = 0; q < B_PASSES; ++q) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!w_transposed) {
+        int kk = ((tid >> 6) << 3) + (tid & 7), n4 = (q * 8 + ((tid >> 3) & 7)) * 4;
+        if (c0 + kk < ca && n0 + n4 < co) v = *(const float4 *)&Wk[(int64_t)(c0 + kk) * co + n0 + n4];
+      } else {
+        int e = q * 256 + tid;
+        int nn = e >> 3, k4 = (e & 7) * 4;
+        if (n0 + nn < co && c0 + k4 < ca) v = *(const float4 *)&Wk[(int64_t)(n0 + nn) * ca + c0 + k4];
+      }
+      rb[q] = v;
+    }
+  };
+  // registers -> LDS images; in the bf16 family the ONE place the operands are rounded
+  auto store_chunk = [&]() {
+#pragma unroll
+    for (int p = 0; p < A_PASSES; ++p) {
+      if constexpr (BF16) *(bf16x4 *)&As[(p * 32 + arow) * STRIDE + acol] = round4(ra[p]);
+      else *(float4 *)&As[(p * 32 + arow) * STRIDE + acol] = ra[p];
+    }
+#pragma unroll
+    for (int q = 0; q < B_PASSES; ++q) {
+      if (!w_transposed) {  // transposing store; fp32: (n4i * 144 + kl) mod 64 banks: 2-way conflicts at worst
+        int kk = ((tid >> 6) << 3) + (tid & 7), n4 = (q * 8 + ((tid >> 3) & 7)) * 4;
+        if constexpr (BF16) {
+          const bf16x4 v = round4(rb[q]);
+          Bs[(n4 + 0) * STRIDE + kk] = v[0];
+          Bs[(n4 + 1) * STRIDE + kk] = v[1];
+          Bs[(n4 + 2) * STRIDE + kk] = v[2];
+          Bs[(n4 + 3) * STRIDE + kk] = v[3];
+        } else {
+          Bs[(n4 + 0) * STRIDE + kk] = rb[q].x;
+          Bs[(n4 + 1) * STRIDE + kk] = rb[q].y;
+          Bs[(n4 + 2) * STRIDE + kk] = rb[q].z;
+          Bs[(n4 + 3) * STRIDE + kk] = rb[q].w;
+        }
+      } else {
+        int e = q * 256 + tid;
+        int nn = e >> 3, k4 = (e & 7) * 4;
+        if constexpr (BF16) *(bf16x4 *)&Bs[nn * STRIDE + k4] = round4(rb[q]);
+        else *(float4 *)&Bs[nn * STRIDE + k4] = rb[q];
+      }
+    }
+  };
+
+  // a lane's fragment rows: pair row wave * 32 + l31 of As, W row l31 of every 32-column tile of Bs, from its half's FRAG elements on
+  const T *ap = nullptr, *bp = nullptr;
+  if constexpr (F::gemm_frag_ptrs_first) {
+    ap = &As[(wave * 32 + l31) * STRIDE + FRAG * half];
+    bp = &Bs[l31 * STRIDE + FRAG * half];
+  }
+  load_chunk(0);
+  for (int c0 = 0; c0 < ca; c0 += kPairBK) {
+    store_chunk();
+    __syncthreads();
+    if (c0 + kPairBK < ca) load_chunk(c0 + kPairBK);  // next chunk's global loads fly under the MFMAs
+    if constexpr (!F::gemm_frag_ptrs_first) {
+      ap = &As[(wave * 32 + l31) * STRIDE + FRAG * half];
+      bp = &Bs[l31 * STRIDE + FRAG * half];
+    }
+    if constexpr (BF16) {   // a chunk of kPairBK channels is two k-steps of 16: one ds_read_b128 per operand and k-step
+#pragma unroll
+      for (int s = 0; s < kPairBK / 16; ++s) {
+        const bf16x8 a = *(const bf16x8 *)(ap + 16 * s);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[j] = mfma_bf16(*(const bf16x8 *)(bp + j * 32 * STRIDE + 16 * s), a, acc[j]);
+      }
+    } else {
+      // lane (l31, half) owns k = 8t + 4*half + s of both operands: one ds_read_b128 per operand row feeds 4 MFMAs.
+      // The fragments of step t+1 are in flight while the MFMAs of step t issue.
+      float af[2][4], bf[2][NT][4];
+      auto load_frag = [&](int buf, int t) {
+        float4 a = *(const float4 *)(ap + 8 * t);
+        af[buf][0] = a.x; af[buf][1] = a.y; af[buf][2] = a.z; af[buf][3] = a.w;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          float4 b = *(const float4 *)(bp + j * 32 * STRIDE + 8 * t);
+          bf[buf][j][0] = b.x; bf[buf][j][1] = b.y; bf[buf][j][2] = b.z; bf[buf][j][3] = b.w;
+        }
+      };
+      load_frag(0, 0);
+#pragma unroll
+      for (int t = 0; t < kPairBK / 8; ++t) {
+        if (t + 1 < kPairBK / 8) load_frag((t + 1) & 1, t + 1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[t & 1][j][s], af[t & 1][s], acc[j], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  pair_gemm_epilogue<NT>(acc, p0, cnt, n0, gather, rows_a, scatter, rows_out, bias, co, tmp);
+}
+
+namespace ftx {
 
 // ---------------------------------------------------------------------------------------
 // device: weight gradient
@@ -270,7 +460,8 @@ inline void launch_wgrad_reduce(const float *part, const int32_t *koff, int kvol
 // ---------------------------------------------------------------------------------------
 // host: the pair GEMM's entries, generic over a family F:
 //   F::pairs_name, F::scatter_name, F::rows_name, F::wgrad_name   the entries' names, as they front every message
-//   F::gemm<NT>(grid, st, args)                 launches the pair-GEMM kernel with NT 32-column tiles per block
+//   F::gemm_lds_t, F::gemm_stride, F::gemm_frag_ptrs_first       what pairs_gemm_kernel<F, NT> takes from the family (see there)
+//   F::gemm<NT>(grid, st, args)                 launches pairs_gemm_kernel<F, NT>: NT 32-column tiles per block
 //   F::wgrad<MI, NI, WMG, WNG>(grid, st, args)  launches the weight-gradient kernel of that tile shape
 //   F::wgrad_blocks, F::wgrad_step              the weight gradient's occupancy table and tile-length step (below)
 // ---------------------------------------------------------------------------------------

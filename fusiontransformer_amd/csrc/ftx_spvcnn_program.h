@@ -1,5 +1,5 @@
 // What the two SPVCNN executors (ftx_exec.hip: eval, ftx_exec_train.hip: training) share on the host: the view of the tables of one
-// call, the rule for the two sides of a kernel map, and the ONE checker of the op program against the model and batch tables.
+// call, the rule for the two sides of a kernel map, the table of a precision family's sparse-convolution entries, and the ONE checker of the op program against the model and batch tables.
 // Nothing here places memory or launches; each executor places its own arena from the facts the checker leaves.  Where the two
 // executors ask different things of the same program the checker says so in a `train` / eval branch at that point.
 #pragma once
@@ -49,6 +49,19 @@ struct MapSides {
 inline MapSides map_sides(const Layer &L, const Map &M) {
   if (L.transposed) return {M.pair_out, M.pair_in, M.pos_t, M.pos};
   return {M.pair_in, M.pair_out, M.pos, M.pos_t};
+}
+
+// The four sparse-convolution entries of a layer's precision family (include/ftx.h): the ONE place the executors pick between the
+// fp32 entries and their bf16 twins.
+struct SpconvEntries {
+  decltype(&ftx_spconv_pairs_gemm) pairs;
+  decltype(&ftx_spconv_pairs_gemm_scatter) scatter;
+  decltype(&ftx_rows_gemm) rows;
+  decltype(&ftx_spconv_pairs_wgrad) wgrad;
+};
+inline SpconvEntries spconv_entries(const Layer &L) {
+  if (L.bf16) return {ftx_spconv_pairs_gemm_bf16, ftx_spconv_pairs_gemm_scatter_bf16, ftx_rows_gemm_bf16, ftx_spconv_pairs_wgrad_bf16};
+  return {ftx_spconv_pairs_gemm, ftx_spconv_pairs_gemm_scatter, ftx_rows_gemm, ftx_spconv_pairs_wgrad};
 }
 
 // What the checker found out about the program, for the placement of either executor.

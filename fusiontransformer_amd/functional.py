@@ -481,13 +481,20 @@ _ROWS_GEMM = {False: "ftx_rows_gemm", True: "ftx_rows_gemm_bf16"}
 # The launchers: the ONE call site of each convolution / BatchNorm entry point and of its launch-log metadata.  Pointers are raw device
 # addresses; results and temporaries go where the caller says (sparse_conv and batch_norm allocate tensors, so they can be captured
 # into a HIP graph; conv_bn_train carves its temporaries from the stream's scratch buffer).
-def _launch_pairs(a, rows_a, gather, w, w_transposed, pos, koff, n_pairs, ca, co, kvol, tmp, out, n_out, st, bf16, part=0, nb=0):
-    """tmp[p] = A[gather[p]] @ W[k(p)], then out = the reduce of tmp over the offsets through `pos`.  part != 0: the reduce also leaves
-    the BatchNorm statistics of `out` there (nb partial rows + the totals row, float64; `st` then has its tickets attached)."""
+def _launch_pairs_gemm(a, rows_a, gather, w, w_transposed, koff, n_pairs, ca, co, kvol, tmp, n_out, st, bf16):
+    """tmp[p] = A[gather[p]] @ W[k(p)]; n_out (the rows of the reduce that follows) is for the log only.  Returns the log metadata."""
     L = _lib.load()
     gemm, kind = _PAIRS_GEMM[bf16]
     meta = dict(pairs=n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol)
     _log_launch(kind, meta, lambda: check(getattr(L, gemm)(a, rows_a, gather, w, w_transposed, koff, n_pairs, ca, co, kvol, tmp, st), gemm))
+    return meta
+
+
+def _launch_pairs(a, rows_a, gather, w, w_transposed, pos, koff, n_pairs, ca, co, kvol, tmp, out, n_out, st, bf16, part=0, nb=0):
+    """tmp[p] = A[gather[p]] @ W[k(p)], then out = the reduce of tmp over the offsets through `pos`.  part != 0: the reduce also leaves
+    the BatchNorm statistics of `out` there (nb partial rows + the totals row, float64; `st` then has its tickets attached)."""
+    L = _lib.load()
+    meta = _launch_pairs_gemm(a, rows_a, gather, w, w_transposed, koff, n_pairs, ca, co, kvol, tmp, n_out, st, bf16)
     if part:
         _log_launch("spconv_reduce", meta, lambda: check(L.ftx_spconv_reduce_stats(tmp, pos, n_out, co, kvol, out, part, nb, st), "ftx_spconv_reduce_stats"))
     else:
@@ -1060,11 +1067,8 @@ def conv_bn_eval(feats, kernel, km, transposed, gamma, beta, running_mean, runni
     route = _conv_route(km, transposed, ca, co, kvol, n_out, bf16)
     if route in (_PAIRS, _EMPTY) and kvol in (8, 27):
         src, _, _, dst_pos = _map_sides(km, transposed)
-        L = _lib.load()
         tmp = _empty((km.n_pairs, co), F32, feats)
-        gemm, kind = _PAIRS_GEMM[bool(bf16)]
-        _log_launch(kind, dict(pairs=km.n_pairs, n_out=n_out, ca=ca, co=co, kvol=kvol), lambda: check(getattr(L, gemm)(
-            ptr(feats), n_in, ptr(src), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(tmp), stream()), gemm))
+        _launch_pairs_gemm(ptr(feats), n_in, ptr(src), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(tmp), n_out, stream(), bool(bf16))
         return spconv_reduce_bn_eval(tmp, dst_pos, n_out, gamma, beta, running_mean, running_var, eps, residual=residual, relu=relu)
     with torch.no_grad():
         return batch_norm(_conv_forward(feats, kernel, km, transposed, bool(bf16)), gamma, beta, running_mean, running_var, False, eps=eps,

@@ -4,6 +4,8 @@ import collections, csv, sys
 
 def cat(name):
     if 'naive_conv' in name or 'miopenSp3' in name or 'igemm' in name or 'Im2d2Col' in name or 'Col2Im' in name: return 'MIOpen conv'
+    # one kernel template for both families: the family is its first template argument (needs untruncated kernel names)
+    if 'pairs_gemm_kernel<SpconvBf16' in name: return 'ftx spconv pairs_gemm (bf16)'
     if 'pairs_gemm_kernel' in name: return 'ftx spconv pairs_gemm'
     if 'spconv_reduce' in name: return 'ftx spconv reduce'
     if 'spconv_ostat' in name: return 'ftx spconv ostat (one-launch thin layers)'
