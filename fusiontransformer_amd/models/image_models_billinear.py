@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as spf
+from .spvcnn import bump_step_counter
 from .transformers import image_2d_distilled_transformer
 
 __all__ = ["BilinearModule", "Net2DBillinear", "pack_img_indices"]
@@ -60,8 +61,7 @@ class BilinearModule(nn.Module):
         # every pixel), then the nearest pick
         conv, bn = self.stem[0], self.stem[2]
         if conv.in_channels == 3 and conv.out_channels == 3 and (bn.training or not torch.is_grad_enabled() or not conv.weight.requires_grad):
-            if bn.training and bn.track_running_stats and not getattr(bn, "_nbt_external", False):
-                bn.num_batches_tracked.add_(1)
+            bump_step_counter(bn)
             conv_w = conv.weight.view(3, 3)
             if x.requires_grad:
                 raise RuntimeError("sample_down: the fused kernel does not produce a gradient for the image")
@@ -71,8 +71,7 @@ class BilinearModule(nn.Module):
         x = torch.einsum("oc,bchw->bohw", w, x) + conv.bias.view(1, -1, 1, 1)
         x = F.relu(x)
         x = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.training, bn.momentum, bn.eps)
-        if bn.training and bn.track_running_stats:
-            bn.num_batches_tracked.add_(1)
+        bump_step_counter(bn)
         return spf.resample_nearest(x, self.size)
 
     def forward_tokens(self, tokens, grid_hw):
@@ -80,8 +79,7 @@ class BilinearModule(nn.Module):
         B, T, E = tokens.shape
         conv, bn = self.stem[0], self.stem[2]
         rows = F.relu(F.linear(tokens.reshape(B * T, E), conv.weight.view(conv.out_channels, E), conv.bias))
-        if bn.training and bn.track_running_stats and not getattr(bn, "_nbt_external", False):
-            bn.num_batches_tracked.add_(1)
+        bump_step_counter(bn)
         rows = spf.batch_norm(rows, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps)
         return rows.view(B, grid_hw[0], grid_hw[1], conv.out_channels)
 
@@ -119,13 +117,7 @@ class Net2DBillinear(nn.Module):
             ckpt = torch.load(kw["IMAGE_PRETRAINED_PATH"], map_location="cpu", weights_only=True)["state_dict"]
             new_state_dict = OrderedDict((k.replace("backbone.", ""), v) for k, v in ckpt.items() if "backbone" in k)
             self.backbone.load_state_dict(new_state_dict)
-        self.backbone.set_attention_impl(kw.get("attn_impl", "ftx"))
-        if kw.get("vit_bf16", False):
-            self.backbone.set_bf16(True)   # BASELINE configs[4] "bf16 forward"; default is fp32 like the reference
-        # how those bf16 GEMMs run: "library" (default) or "ftx" (libftx's bf16 kernels, fp32 results, fused bias / GELU).  Inert
-        # while the GEMMs are fp32.  "ftx_split": the fp32 model's own kernels (three bf16 pieces per fp32 operand, six products
-        # summed in fp32: fp32-class results with the fused bias / GELU epilogues); routes with vit_bf16 off or on.
-        self.backbone.set_linear_impl(kw.get("vit_linear_impl", "library"))
+        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl
         # Training on the GPU runs the trunk as HIP graphs, one per tapped segment (transformers.py): ~500 kernel launches
         # per step become 4 graph launches, which takes 7 ms off the host side of a step (batch 4: the host issue time
         # drops from ~24 to ~17 ms, so the step stays GPU-bound on a slow host; +26-30 % frames/s at batch 1-2).

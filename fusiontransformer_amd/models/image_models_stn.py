@@ -55,10 +55,7 @@ class Net2DSeg(nn.Module):
             ckpt = torch.load(kw["IMAGE_PRETRAINED_PATH"], map_location="cpu", weights_only=True)["state_dict"]
             new_state_dict = OrderedDict((k.replace("backbone.", ""), v) for k, v in ckpt.items() if "backbone" in k)
             self.backbone.load_state_dict(new_state_dict)
-        self.backbone.set_attention_impl(kw.get("attn_impl", "ftx"))
-        if kw.get("vit_bf16", False):
-            self.backbone.set_bf16(True)
-        self.backbone.set_linear_impl(kw.get("vit_linear_impl", "library"))
+        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl
         # parameters that can never receive a gradient: the final `norm` (forward_blocks never applies it) and blocks past the last tap
         for p in self.backbone.norm.parameters():
             p.requires_grad_(False)

@@ -41,33 +41,39 @@ class Conv3d(nn.Module):
         self.kernel.data.uniform_(-std, std)
 
     def forward(self, x: SparseTensor) -> SparseTensor:
-        ks, s = self.kernel_size, self.stride
-        bf16 = getattr(self, "ftx_bf16", False)   # SPVCNN.set_bf16: bf16-operand kernels
-        if ks == 1 and s == 1:
-            out = x.derive(spf.rows_matmul(x.F, self.kernel, bf16=bf16))
-            out.check()
-            return out
-        if not self.t:
-            km = x.cm.kernel_map(ks, x.s, s)
-            feats = spf.sparse_conv(x.F, self.kernel, km, False, bf16=bf16)
-            out = x.derive(feats, km.out_coords, x.s * s)
+        if self.kernel_size == 1 and self.stride == 1:
+            out = x.derive(spf.rows_matmul(x.F, self.kernel, bf16=bf16_operands(self)))
         else:
-            original_stride = x.s // s
-            km = x.cm.kernel_maps.get((ks, original_stride, s))
-            if km is None:
-                raise RuntimeError("transposed Conv3d needs the kernel map of the paired strided Conv3d")
-            feats = spf.sparse_conv(x.F, self.kernel, km, True, bf16=bf16)
-            out = x.derive(feats, x.cm.coords[original_stride], original_stride)
+            km, coords, stride = _conv_map(self, x)
+            out = x.derive(spf.sparse_conv(x.F, self.kernel, km, self.t, bf16=bf16_operands(self)), coords, stride)
         out.check()
         return out
+
+
+def bf16_operands(module):
+    """SPVCNN.set_bf16 as it stands on a Conv3d or a point-branch nn.Linear: the one reader of `ftx_bf16` for the LiDAR branch."""
+    return bool(getattr(module, "ftx_bf16", False))
+
+
+def step_counter(bn):
+    """The `num_batches_tracked` a BatchNorm (any nn.BatchNorm*) bumps itself in this forward, or None: not in training mode, no
+    running statistics, or _fusion_common.bump_batchnorm_counters counts for it (it marks the module `_nbt_external`)."""
+    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None and not getattr(bn, "_nbt_external", False):
+        return bn.num_batches_tracked
+    return None
+
+
+def bump_step_counter(bn):
+    counter = step_counter(bn)
+    if counter is not None:
+        counter.add_(1)
 
 
 class BatchNorm(nn.BatchNorm1d):
     """spnn.BatchNorm: BatchNorm1d over the voxel rows; `fused` adds the residual and ReLU in the same pass."""
 
     def fused(self, feats, residual=None, relu=False):
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None and not getattr(self, "_nbt_external", False):
-            self.num_batches_tracked.add_(1)
+        bump_step_counter(self)
         return spf.batch_norm(feats, self.weight, self.bias, self.running_mean, self.running_var, self.training,
                               self.momentum, self.eps, residual=residual, relu=relu)
 
@@ -87,7 +93,7 @@ class ReLU(nn.ReLU):
 
 
 def _conv_map(conv, x):
-    """(kernel map, output coordinates, output stride) of a k > 1 Conv3d on x, as Conv3d.forward finds them."""
+    """(kernel map, output coordinates, output stride) of a k > 1 Conv3d on x."""
     ks, s = conv.kernel_size, conv.stride
     if not conv.t:
         km = x.cm.kernel_map(ks, x.s, s)
@@ -102,39 +108,36 @@ def _conv_map(conv, x):
 def _conv_bn(conv, bn, x, residual=None, relu=True):
     """Conv3d -> BatchNorm (-> + residual) (-> ReLU).  In training a k>1 convolution and its BatchNorm run as one autograd node whose
     reduce pass also produces the batch statistics (functional.conv_bn_train); eval and 1x1x1 layers run the two separately."""
-    ks, s = conv.kernel_size, conv.stride
-    if bn.training and not (ks == 1 and s == 1) and x.F.is_cuda:
-        if not conv.t:
-            km = x.cm.kernel_map(ks, x.s, s)
-            coords, stride = km.out_coords, x.s * s
-        else:
-            original_stride = x.s // s
-            km = x.cm.kernel_maps.get((ks, original_stride, s))
-            if km is None:
-                raise RuntimeError("transposed Conv3d needs the kernel map of the paired strided Conv3d")
-            coords, stride = x.cm.coords[original_stride], original_stride
-        if bn.track_running_stats and bn.num_batches_tracked is not None and not getattr(bn, "_nbt_external", False):
-            bn.num_batches_tracked.add_(1)
+    fused_eval = getattr(conv, "ftx_native_eval", False) and not bn.training and not torch.is_grad_enabled()
+    if (conv.kernel_size == 1 and conv.stride == 1) or not x.F.is_cuda or not (bn.training or fused_eval):
+        y = conv(x)
+        return y.derive(bn.fused(y.F, residual=residual, relu=relu))
+    km, coords, stride = _conv_map(conv, x)
+    if bn.training:
+        bump_step_counter(bn)
         feats = spf.conv_bn_train(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                  residual=residual, relu=relu, bf16=getattr(conv, "ftx_bf16", False))
-        out = x.derive(feats, coords, stride)
-        out.check()
-        return out
-    if getattr(conv, "ftx_native_eval", False) and not bn.training and not torch.is_grad_enabled() and not (ks == 1 and s == 1) and x.F.is_cuda:
+                                  residual=residual, relu=relu, bf16=bf16_operands(conv))
+    else:
         # SPVCNN.set_native_eval where the executor does not run (a layer option it refuses): the reduce carries the eval BatchNorm
-        km, coords, stride = _conv_map(conv, x)
         feats = spf.conv_bn_eval(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, residual=residual,
-                                 relu=relu, bf16=getattr(conv, "ftx_bf16", False))
-        out = x.derive(feats, coords, stride)
-        out.check()
-        return out
-    y = conv(x)
-    return y.derive(bn.fused(y.F, residual=residual, relu=relu))
+                                 relu=relu, bf16=bf16_operands(conv))
+    out = x.derive(feats, coords, stride)
+    out.check()
+    return out
+
+
+def _addend_steps(f, token):
+    """A fusion addend `f` (the image features, or the call that waits for them: _fusion_common._Lazy.get) after yielding `token`
+    where they are first touched; None without a yield where nothing is fused."""
+    if f is None:
+        return None
+    yield token
+    return f() if callable(f) else f
 
 
 def _linear_bn_relu(seq, feats):
     """nn.Sequential(Linear, BatchNorm1d, ReLU) on point rows (spvcnn.py:164-180)."""
-    return seq[1].fused(spf.linear(feats, seq[0].weight, seq[0].bias, bf16=getattr(seq[0], "ftx_bf16", False)), relu=True)
+    return seq[1].fused(spf.linear(feats, seq[0].weight, seq[0].bias, bf16=bf16_operands(seq[0])), relu=True)
 
 
 class BasicConvolutionBlock(nn.Module):
@@ -309,24 +312,17 @@ class SPVCNN(nn.Module):
     def _native_train_steps(self, run, z, x0, fuse_early, fuse_middle):
         """_backbone_steps from "voxelized" on through the training executor: one autograd node per segment, Dropout between them."""
         z0 = run.segment(0, x0.F)
-        early = middle = None
-        if fuse_early is not None:
-            yield "need_early"
-            early = fuse_early() if callable(fuse_early) else fuse_early
+        early = yield from _addend_steps(fuse_early, "need_early")
         yield "stem"
         z1 = run.segment(1, z0, early)
-        if fuse_middle is not None:
-            yield "need_middle"
-            middle = fuse_middle() if callable(fuse_middle) else fuse_middle
+        middle = yield from _addend_steps(fuse_middle, "need_middle")
         yield "stage4"
         y1 = self._drop(run.segment(2, z1, middle), "y1")
         y3 = self._drop(run.segment(3, y1), "y3")
         yield "up2"
         feats = run.segment(4, y3)
         yield "up4"
-        cm = x0.cm
-        levels = {"x%d" % l: SparseTensor(None, cm.coords[s], s) for l, s in enumerate((1, 2, 4, 8, 16)) if l}
-        self.last_index = dict(x0=x0, z=z, **levels)
+        self._keep_index(z, x0)
         return feats
 
     def _native_executor(self, x):
@@ -344,35 +340,18 @@ class SPVCNN(nn.Module):
     def _native_steps(self, ex, x, fuse_early, fuse_middle):
         """_backbone_steps through the executor: the same index build, then one call per segment; "need_early" / "need_middle" are
         yielded where the image features are first touched, the stage tokens are the segment boundaries."""
-        prepared = getattr(x, "prepared", None)
-        if isinstance(prepared, PendingIndex):
-            while prepared.done is None:
-                yield "sync"
-                prepared.step()
-            prepared = prepared.done
-        if prepared is not None:
-            z, x0 = prepared.take(torch.cuda.current_stream())
-            x.prepared = None
-        else:
-            z, x0 = yield from self._index_steps(x, ahead=True)
+        z, x0 = yield from self._batch_index_steps(x, ahead=True)
         yield "voxelized"
         run = ex.begin(z, x0)
         run.segments(0, 0)
-        early = middle = None
-        if fuse_early is not None:
-            yield "need_early"
-            early = fuse_early() if callable(fuse_early) else fuse_early
+        early = yield from _addend_steps(fuse_early, "need_early")
         yield "stem"
         run.segments(1, 1, add_early=early)
-        if fuse_middle is not None:
-            yield "need_middle"
-            middle = fuse_middle() if callable(fuse_middle) else fuse_middle
+        middle = yield from _addend_steps(fuse_middle, "need_middle")
         yield "stage4"
         feats = run.segments(2, 2, add_middle=middle)
         yield "up4"
-        cm = x0.cm
-        levels = {"x%d" % l: SparseTensor(None, cm.coords[s], s) for l, s in enumerate((1, 2, 4, 8, 16)) if l}
-        self.last_index = dict(x0=x0, z=z, **levels)
+        self._keep_index(z, x0)
         return feats
 
     def weight_initialization(self):
@@ -392,12 +371,7 @@ class SPVCNN(nn.Module):
 
     def _backbone(self, x, fuse_early=None, fuse_middle=None):
         """spvcnn.py:191-233 with the fusion adds of early_fusion.py:39 / middle_fusion.py:48."""
-        steps = self._backbone_steps(x, fuse_early, fuse_middle)
-        while True:
-            try:
-                next(steps)
-            except StopIteration as done:
-                return done.value
+        return drain(self._backbone_steps(x, fuse_early, fuse_middle))
 
     def _backbone_steps(self, x, fuse_early=None, fuse_middle=None):
         """The same forward as a generator that yields at stage boundaries, so a scheduler can interleave
@@ -407,19 +381,7 @@ class SPVCNN(nn.Module):
         if ex is not None:
             return (yield from self._native_steps(ex, x, fuse_early, fuse_middle))
         trainer = self._native_trainer(x)
-        prepared = getattr(x, "prepared", None)
-        if isinstance(prepared, PendingIndex):
-            # started ahead of this forward (prepare(wait=False)) and parked at a host read: finish it here, on its own stream
-            while prepared.done is None:
-                yield "sync"
-                prepared.step()
-            prepared = prepared.done
-        if prepared is not None:
-            # built ahead of this forward on the index stream (prepare()): wait for it, and tell the allocator this stream uses it
-            z, x0 = prepared.take(torch.cuda.current_stream() if x.F.is_cuda else None)
-            x.prepared = None
-        else:
-            z, x0 = yield from self._index_steps(x, ahead=trainer is not None)
+        z, x0 = yield from self._batch_index_steps(x, ahead=trainer is not None)
         yield "voxelized"
         if trainer is not None:
             from ..native_train import Refused
@@ -431,9 +393,9 @@ class SPVCNN(nn.Module):
                 return (yield from self._native_train_steps(run, z, x0, fuse_early, fuse_middle))
         x0 = self._stem(x0)
         z0 = voxel_to_point(x0, z, nearest=False)
-        if fuse_early is not None:
-            yield "need_early"
-            z0.F = z0.F + (fuse_early() if callable(fuse_early) else fuse_early)
+        early = yield from _addend_steps(fuse_early, "need_early")
+        if early is not None:
+            z0.F = z0.F + early
         yield "stem"
 
         x1 = point_to_voxel(x0, z0)
@@ -446,9 +408,9 @@ class SPVCNN(nn.Module):
         x4 = self.stage4(x3)
         z1 = voxel_to_point(x4, z0)
         z1.F = z1.F + _linear_bn_relu(self.point_transforms[0], z0.F)
-        if fuse_middle is not None:
-            yield "need_middle"
-            z1.F = z1.F + (fuse_middle() if callable(fuse_middle) else fuse_middle)
+        middle = yield from _addend_steps(fuse_middle, "need_middle")
+        if middle is not None:
+            z1.F = z1.F + middle
         yield "stage4"
 
         y1 = point_to_voxel(x4, z1)
@@ -480,6 +442,28 @@ class SPVCNN(nn.Module):
         z3.F = z3.F + _linear_bn_relu(self.point_transforms[2], z2.F)
         self.last_index = dict(x0=x0, x1=x1, x2=x2, x3=x3, x4=x4, z=z)
         return z3.F
+
+    def _batch_index_steps(self, x, ahead):
+        """(z, x0) of batch `x` at the start of a forward: what prepare() hung on it, else built here (_index_steps)."""
+        prepared = getattr(x, "prepared", None)
+        if isinstance(prepared, PendingIndex):
+            # started ahead of this forward (prepare(wait=False)) and parked at a host read: finish it here, on its own stream
+            while prepared.done is None:
+                yield "sync"
+                prepared.step()
+            prepared = prepared.done
+        if prepared is None:
+            return (yield from self._index_steps(x, ahead=ahead))
+        # built ahead of this forward on the index stream (prepare()): wait for it, and tell the allocator this stream uses it
+        z, x0 = prepared.take(torch.cuda.current_stream() if x.F.is_cuda else None)
+        x.prepared = None
+        return z, x0
+
+    def _keep_index(self, z, x0):
+        """`last_index` of a forward through an executor: the levels' coordinates without features (those stay in the arena)."""
+        cm = x0.cm
+        levels = {"x%d" % l: SparseTensor(None, cm.coords[s], s) for l, s in enumerate((1, 2, 4, 8, 16)) if l}
+        self.last_index = dict(x0=x0, z=z, **levels)
 
     def _index_steps(self, x, ahead=False):
         """Everything of a batch that depends on its coordinates only: the voxelisation of the points, the voxel hash, the

@@ -101,18 +101,46 @@ def _over_batch(p, b):
     return _BatchBroadcast.apply(p, b) if p.is_cuda else p.expand(b, *p.shape[1:])
 
 
+def linear_switches(lin):
+    """(impl, bf16) of a trunk Linear as set_linear_impl / set_bf16 left them: the one reader of the two attributes and their defaults."""
+    return getattr(lin, "ftx_linear_impl", "library"), bool(getattr(lin, "ftx_bf16", False))
+
+
+# What linear_route answers.  The two own-kernel routes are spelled as the `mode` of functional.vit_linear / vit_mlp.
+LIBRARY_FP32, LIBRARY_BF16, OWN_BF16, OWN_SPLIT = "library_fp32", "library_bf16", "bf16", "split"
+OWN_ROUTES = (OWN_BF16, OWN_SPLIT)
+
+
+def linear_route(lin):
+    """Which GEMMs a trunk Linear runs on, from its two switches: "ftx_split" is the more specific request and routes to the split
+    kernels whatever set_bf16 says; "ftx" routes to the bf16 kernels only with set_bf16 on; everything else is the library path, in
+    bf16 or fp32."""
+    impl, bf16 = linear_switches(lin)
+    if impl == "ftx_split":
+        return OWN_SPLIT
+    if impl == "ftx" and bf16:
+        return OWN_BF16
+    return LIBRARY_BF16 if bf16 else LIBRARY_FP32
+
+
+def block_linears(blk):
+    return blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2
+
+
+def block_switches(blk):
+    """(attn_impl, (linear_switches of qkv, proj, fc1, fc2)): every switch of a Block, raw, as graph keys and table signatures record it."""
+    return blk.attn.attn_impl, tuple(linear_switches(lin) for lin in block_linears(blk))
+
+
 def _linear(x, lin, with_bias=True):
+    bias = lin.bias if with_bias else None
     if lin.bias is None or not x.is_cuda:
-        return F.linear(x, lin.weight, lin.bias if with_bias else None)
-    bf16 = getattr(lin, "ftx_bf16", False)
-    impl = getattr(lin, "ftx_linear_impl", "library")
-    if impl == "ftx_split":   # the more specific request: routes whether or not set_bf16 is on
+        return F.linear(x, lin.weight, bias)
+    route = linear_route(lin)
+    if route in OWN_ROUTES:
         from .. import functional as spf
-        return spf.vit_linear(x, lin.weight, lin.bias if with_bias else None, mode="split")   # fp32 library path for shapes the kernels do not take
-    if bf16 and impl == "ftx":
-        from .. import functional as spf
-        return spf.vit_linear(x, lin.weight, lin.bias if with_bias else None)   # library path for shapes the kernels do not take
-    return _LinearFn.apply(x, lin.weight, lin.bias if with_bias else None, bf16)
+        return spf.vit_linear(x, lin.weight, bias, mode=route)   # the library path (fp32 for "split") for shapes the kernels do not take
+    return _LinearFn.apply(x, lin.weight, bias, route == LIBRARY_BF16)
 
 
 class Mlp(nn.Module):
@@ -128,17 +156,15 @@ class Mlp(nn.Module):
             # vit_linear_impl "ftx" / "ftx_split": fc1 + GELU + fc2 as one node on the bf16 / three-piece split kernels (GELU in fc1's
             # epilogue, its derivative in fc2's dX)
             from .. import functional as spf
-            mode = "split" if getattr(self.fc1, "ftx_linear_impl", "library") == "ftx_split" else "bf16"
-            return spf.vit_mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias if with_fc2_bias else None, mode=mode)
+            return spf.vit_mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias if with_fc2_bias else None,
+                               mode=linear_route(self.fc1))
         return self.drop(_linear(self.drop(self.act(_linear(x, self.fc1))), self.fc2, with_fc2_bias))
 
     def _fused_ftx(self, x):
-        fc1, fc2 = self.fc1, self.fc2
-        impls = (getattr(fc1, "ftx_linear_impl", "library"), getattr(fc2, "ftx_linear_impl", "library"))
-        bf16 = getattr(fc1, "ftx_bf16", False) and getattr(fc2, "ftx_bf16", False)
-        return (x.is_cuda and (impls == ("ftx_split", "ftx_split") or (bool(bf16) and impls == ("ftx", "ftx")))
+        route = linear_route(self.fc1)
+        return (x.is_cuda and route in OWN_ROUTES and linear_route(self.fc2) == route
                 and type(self.act) is nn.GELU and self.act.approximate == "none" and self.drop.p == 0.0
-                and fc1.bias is not None and fc2.bias is not None)
+                and self.fc1.bias is not None and self.fc2.bias is not None)
 
 
 class Attention(nn.Module):
@@ -298,7 +324,7 @@ class Image2DTransformer(nn.Module):
         bar for this mode is stated in tests/test_model_gpu.py.  The attention kernel gets bf16 operands separately:
         set_attention_impl("ftx_bf16")."""
         for blk in self.blocks:
-            for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
+            for lin in block_linears(blk):
                 lin.ftx_bf16 = bool(on)
 
     def set_linear_impl(self, impl: str):
@@ -311,12 +337,19 @@ class Image2DTransformer(nn.Module):
         if impl not in ("library", "ftx", "ftx_split"):
             raise ValueError(f"vit_linear_impl must be 'library', 'ftx' or 'ftx_split', got {impl!r}")
         for blk in self.blocks:
-            for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
+            for lin in block_linears(blk):
                 lin.ftx_linear_impl = impl
 
     def set_attention_impl(self, impl: str):
         for blk in self.blocks:
             blk.attn.attn_impl = impl
+
+    def set_switches(self, kw):
+        """The three switches above from an image model's backbone_2d_kwargs (cfg.MODEL.attn_impl / vit_bf16 / vit_linear_impl)."""
+        self.set_attention_impl(kw.get("attn_impl", "ftx"))
+        if kw.get("vit_bf16", False):
+            self.set_bf16(True)   # BASELINE configs[4] "bf16 forward"; default is fp32 like the reference
+        self.set_linear_impl(kw.get("vit_linear_impl", "library"))
 
     def _embed(self, x):
         x = self.patch_embed(x)
@@ -403,12 +436,10 @@ class Image2DTransformer(nn.Module):
 
     def _graph_key(self, x):
         """Everything a captured graph bakes in: input shape / dtype / requires_grad, the tap set and segment length, the
-        per-block execution flags and the parameters' requires_grad pattern.  Changing any of them selects another graph."""
-        flags = tuple((blk.attn.attn_impl, bool(getattr(blk.attn.qkv, "ftx_bf16", False)), bool(getattr(blk.mlp.fc1, "ftx_bf16", False)),
-                       _linear_impls(blk)) for blk in self.blocks)
+        per-block execution switches and the parameters' requires_grad pattern.  Changing any of them selects another graph."""
         grads = tuple(p.requires_grad for p in self.parameters())
         return (tuple(x.shape), x.dtype, bool(x.requires_grad), tuple(self.graph_taps), self.last_block, self.graph_segment_blocks,
-                flags, grads, torch.cuda.current_device())
+                tuple(block_switches(blk) for blk in self.blocks), grads, torch.cuda.current_device())
 
     def _graphed_segments(self, x):
         if not self.graph_taps or not self.use_graphs or not x.is_cuda or not self.training or not torch.is_grad_enabled():
@@ -437,6 +468,11 @@ class Image2DTransformer(nn.Module):
     # ---- forward-only graph for evaluation -----------------------------------------------------------------------------------
     eval_graphs = True
 
+    def _infer_key(self, x):
+        """The forward-only graph's counterpart of _graph_key (no gradients, so no requires_grad patterns)."""
+        return (tuple(x.shape), x.dtype, tuple(self.graph_taps), self.last_block, tuple(block_switches(blk) for blk in self.blocks),
+                torch.cuda.current_device())
+
     def _inference_graph(self, x):
         """Replay function of the forward-only HIP graph for this input shape, or None (not on the GPU, gradients enabled, training
         mode, taps unknown, or the capture was refused).  No autograd node is created under no_grad, so the restriction of the
@@ -445,9 +481,7 @@ class Image2DTransformer(nn.Module):
                 or torch.cuda.is_current_stream_capturing()):
             return None
         cache = self.__dict__.setdefault("_infer_cache", {})
-        flags = tuple((blk.attn.attn_impl, bool(getattr(blk.attn.qkv, "ftx_bf16", False)), bool(getattr(blk.mlp.fc1, "ftx_bf16", False)),
-                       _linear_impls(blk)) for blk in self.blocks)
-        key = (tuple(x.shape), x.dtype, tuple(self.graph_taps), self.last_block, flags, torch.cuda.current_device())
+        key = self._infer_key(x)
         if key not in cache:
             try:
                 cache[key] = self._capture_inference(x)
@@ -549,11 +583,6 @@ def _no_gc():
     finally:
         if was:
             gc.enable()
-
-
-def _linear_impls(blk):
-    """The vit_linear_impl of a block's four Linears (part of the graph keys: it selects other kernels)."""
-    return tuple(getattr(lin, "ftx_linear_impl", "library") for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2))
 
 
 class _TrunkSegment(nn.Module):

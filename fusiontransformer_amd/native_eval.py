@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from . import functional as spf
+from .models.spvcnn import BatchNorm, Conv3d, bf16_operands
 
 _P = "<i8"   # a device pointer in a table
 LAYER = np.dtype([("weight", _P), ("bias", _P), ("gamma", _P), ("beta", _P), ("mean", _P), ("var", _P), ("ca", "<i4"), ("co", "<i4"),
@@ -82,7 +83,6 @@ class Program:
 
     def conv_bn(self, seg, conv, bn, src, level, residual=-1, relu=True):
         """-> (slot, level) of Conv3d -> BatchNorm (-> + residual) (-> ReLU), as models/spvcnn._conv_bn."""
-        from .models.spvcnn import BatchNorm, Conv3d
         if not isinstance(conv, Conv3d) or not isinstance(bn, BatchNorm) or not bn.track_running_stats or not bn.affine:
             raise Unsupported("Conv3d -> BatchNorm with running statistics expected")
         ks, s = conv.kernel_size, conv.stride
@@ -106,7 +106,6 @@ class Program:
 
     def linear_bn_relu(self, seg, seq, src, dst=None):
         """nn.Sequential(Linear, BatchNorm, ReLU) on point rows, as models/spvcnn._linear_bn_relu."""
-        from .models.spvcnn import BatchNorm
         lin, bn = seq[0], seq[1]
         if not isinstance(lin, torch.nn.Linear) or not isinstance(bn, BatchNorm) or not bn.track_running_stats or not bn.affine:
             raise Unsupported("Linear -> BatchNorm with running statistics expected")
@@ -195,7 +194,7 @@ def layer_table(program: Program) -> np.ndarray:
                 raise Unsupported("parameters must be contiguous float32")
         r["weight"], r["bias"], r["gamma"], r["beta"], r["mean"], r["var"] = (0 if t is None else t.data_ptr() for t in (w, b, g, be, m, v))
         r["ca"], r["co"], r["kvol"], r["stride"], r["transposed"], r["eps"], r["kind"] = l["ca"], l["co"], l["kvol"], l["stride"], l["transposed"], l["eps"], l["kind"]
-        r["bf16"] = int(bool(getattr(l["module"], "ftx_bf16", False)))
+        r["bf16"] = int(bf16_operands(l["module"]))
     return rec
 
 
@@ -258,7 +257,7 @@ class _Host:
         self.layers = None
 
     def model_table(self):
-        key = tuple([d[n].data_ptr() for d, n in self.refs] + [getattr(m, "ftx_bf16", False) for m in self.modules])
+        key = tuple([d[n].data_ptr() for d, n in self.refs] + [bf16_operands(m) for m in self.modules])
         if key != self.key:
             self.layers = layer_table(self.program)
             self.key = key

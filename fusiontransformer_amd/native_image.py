@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from . import functional as spf
+from .models.transformers import OWN_BF16, OWN_SPLIT, block_linears, block_switches, linear_route, linear_switches
 
 _P = "<i8"   # a device pointer in a table
 MODEL = np.dtype([("patch_w", _P), ("patch_b", _P), ("cls", _P), ("dist", _P), ("pos", _P), ("dim", "<i4"), ("heads", "<i4"), ("hidden", "<i4"),
@@ -23,6 +24,7 @@ TAP = np.dtype([("stem_w", _P), ("stem_b", _P), ("gamma", _P), ("beta", _P), ("m
                 ("eps", "<f4"), ("reserved", "<i4")])
 LINEAR_SPLIT, LINEAR_BF16 = 0, 1
 ATTN_FP32, ATTN_BF16 = 0, 1
+_LINEAR_MODE = {OWN_SPLIT: LINEAR_SPLIT, OWN_BF16: LINEAR_BF16}      # of the routes the executor runs (transformers.linear_route)
 
 _vp = ctypes.c_void_p
 
@@ -59,15 +61,13 @@ def modes(net):
     live = [b for i, b in enumerate(bb.blocks) if bb.last_block is None or i <= bb.last_block]
     lin, att = set(), set()
     for blk in live:
-        for l in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
-            impl = getattr(l, "ftx_linear_impl", "library")
-            if impl == "ftx_split":
-                lin.add(LINEAR_SPLIT)
-            elif impl == "ftx" and getattr(l, "ftx_bf16", False):
-                lin.add(LINEAR_BF16)
-            else:
+        for l in block_linears(blk):
+            route = linear_route(l)
+            if route not in _LINEAR_MODE:
+                impl = linear_switches(l)[0]
                 raise Unsupported("vit_linear_impl=%r%s: the library has no GEMM of its own for these Linears" % (
                     impl, "" if impl != "ftx" else " without set_bf16"))
+            lin.add(_LINEAR_MODE[route])
         att.add(blk.attn.attn_impl)
     if len(lin) != 1:
         raise Unsupported("the blocks do not share one linear mode")
@@ -185,12 +185,9 @@ class NativeImage:
         n_live = len(bb.blocks) if bb.last_block is None else bb.last_block + 1
         sig = [bb.patch_embed.proj.weight.data_ptr(), bb.patch_embed.proj.bias.data_ptr(), bb.cls_token.data_ptr(),
                0 if bb.dist_token is None else bb.dist_token.data_ptr(), bb.pos_embed.data_ptr(), net.middle_feat_block_number, net.late_feat_block_number]
-        for i in range(n_live):
-            blk = bb.blocks[i]
+        for blk in bb.blocks[:n_live]:
             sig.extend(t.data_ptr() for t in block_tensors(blk))
-            sig.append(blk.attn.attn_impl)
-            for l in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
-                sig.append((getattr(l, "ftx_linear_impl", "library"), bool(getattr(l, "ftx_bf16", False))))
+            sig.append(block_switches(blk))
         for up in net.up.values():
             sig.extend(t.data_ptr() for t in tap_tensors(up))
         return tuple(sig)

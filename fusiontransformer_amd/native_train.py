@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from . import functional as spf
 from . import native_eval as ne
+from .models.spvcnn import step_counter
 from .native_eval import Unsupported, _P, _ptr
 
 TRAIN_LAYER = np.dtype([("dweight", _P), ("dbias", _P), ("dgamma", _P), ("dbeta", _P), ("momentum", "<f4"), ("reserved", "<i4")])
@@ -233,7 +234,7 @@ class _Run:
             addend = _lib.req(addend.contiguous(), torch.float32, "native train fusion addend", 2)
             if tuple(addend.shape) != (n_pts, tp.in_channels[seg]) or seg not in (1, 2):
                 raise ValueError("native train: the fusion addend does not match the point features")
-        live = [bn.num_batches_tracked for bn in tp.seg_bns[seg] if bn.num_batches_tracked is not None and not getattr(bn, "_nbt_external", False)]
+        live = [c for c in map(step_counter, tp.seg_bns[seg]) if c is not None]
         if live:
             torch._foreach_add_(live, 1)
         last = seg == tp.n_segments - 1

@@ -290,3 +290,37 @@ def test_switch_is_off_by_default_and_reaches_every_model(net):
     assert net.lidar_native_train is True
     net.set_native_eval(False).set_native_index(False).set_bf16(False).set_native_train(False)
     assert net.lidar_native_train is False and net._native_tr is None
+
+
+def test_step_counter_names_exactly_the_counters_a_training_forward_bumps():
+    """models/spvcnn.step_counter is the one rule every site that bumps num_batches_tracked asks (BatchNorm.fused, _conv_bn, this
+    executor's _Run._forward, the image branch's stems): the module's own counter in training mode with running statistics, None in eval
+    mode, without running statistics, and once _fusion_common.bump_batchnorm_counters counts for the module."""
+    from fusiontransformer_amd.models._fusion_common import bump_batchnorm_counters
+    from fusiontransformer_amd.models.image_models_billinear import Net2DBillinear
+    from fusiontransformer_amd.models.spvcnn import step_counter
+    torch.manual_seed(0)
+    lidar = SPVCNN(cr=0.25)
+    image = Net2DBillinear(num_classes=4, dual_head=False, backbone_2d_kwargs=dict(vit_depth=2, middle_feat_block_number=0, late_feat_block_number=1))
+    for model, n_bns in ((lidar, 52), (image, 3)):      # 2 stem + 23 encoder + 24 decoder + 3 point transforms; sample_down + two taps
+        bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+        assert len(bns) == n_bns
+        model.train()
+        assert all(step_counter(m) is m.num_batches_tracked for m in bns)
+        model.eval()
+        assert all(step_counter(m) is None for m in bns)
+        model.train()
+        bns[1].eval()      # a module frozen on its own keeps its counter
+        assert [step_counter(m) is None for m in bns] == [i == 1 for i in range(n_bns)]
+        before = [int(m.num_batches_tracked) for m in bns]
+        bump_batchnorm_counters(model)      # counts once for every training module and marks them all
+        assert [int(m.num_batches_tracked) - b for m, b in zip(bns, before)] == [i != 1 for i in range(n_bns)]
+        bns[1].train()
+        assert all(step_counter(m) is None for m in bns), "the model's one launch counts for them from here on"
+        model.eval()
+        assert all(step_counter(m) is None for m in bns)
+    for bn in (BatchNorm(8, track_running_stats=False), torch.nn.BatchNorm2d(8, track_running_stats=False)):
+        bn.train()
+        assert bn.num_batches_tracked is None and step_counter(bn) is None
+    bn = BatchNorm(8).train()
+    assert step_counter(bn) is bn.num_batches_tracked

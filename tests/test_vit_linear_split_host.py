@@ -232,7 +232,7 @@ def test_graph_keys_distinguish_the_three_impls(monkeypatch):
             assert t.graph_taps
             keys[impl] = t._graph_key(x)
         assert len(set(keys.values())) == 3, on
-        assert all(blk[3] == ("ftx_split",) * 4 for blk in keys["ftx_split"][6])
+        assert all([impl for impl, _ in blk[1]] == ["ftx_split"] * 4 for blk in keys["ftx_split"][6])
     trunks["ftx_split"].set_linear_impl("library")
     assert trunks["ftx_split"]._graph_key(x) == trunks["library"]._graph_key(x)
 
@@ -294,3 +294,91 @@ def test_g2_passes_six_products_and_fails_five_and_three(k):
     # all nine products in float64 are the float64 GEMM itself: the pieces lose nothing
     s = a.double() @ b.double()
     assert R.rms(R.gemm(a, b, R.NINE) - s) / R.rms(s) < 1e-12
+
+
+# ---------------------------------------------------------------- one reader of the switches: the route table and the keys
+# (set_linear_impl, set_bf16) -> the constant of models/transformers.py that linear_route answers
+ROUTE_TABLE = {("library", False): "LIBRARY_FP32", ("library", True): "LIBRARY_BF16", ("ftx", False): "LIBRARY_FP32", ("ftx", True): "OWN_BF16",
+               ("ftx_split", False): "OWN_SPLIT", ("ftx_split", True): "OWN_SPLIT"}
+
+
+def _image_branch():
+    from fusiontransformer_amd.models.build import build_model
+    from tests.helpers import small_cfg
+    torch.manual_seed(0)
+    net = build_model(small_cfg("middle"))[0].image_backbone
+    assert len(net.backbone.blocks) == 2
+    return net
+
+
+def test_route_table_and_every_consumer_of_it(monkeypatch):
+    """All six setter states on a depth-2 trunk: linear_route of the eight Linears is the documented table, and _linear, Mlp._fused_ftx,
+    Mlp.forward's mode and native_image.modes each do what the route names."""
+    from fusiontransformer_amd import functional as spf
+    from fusiontransformer_amd import native_image as ni
+    from fusiontransformer_amd.models import transformers as T
+    net = _image_branch()
+    b = net.backbone
+    xc = torch.zeros(1, 5, 768).as_subclass(_Cuda)
+    routed = []
+
+    def stub(name, what):
+        def call(*a, **k):
+            routed.append((name, what(a, k)))
+            return a[0].new_zeros(*a[0].shape[:-1], (a[3] if name == "vit_mlp" else a[1]).shape[0])
+        return call
+    monkeypatch.setattr(spf, "vit_linear", stub("vit_linear", lambda a, k: k["mode"]))
+    monkeypatch.setattr(spf, "vit_mlp", stub("vit_mlp", lambda a, k: k["mode"]))
+    monkeypatch.setattr(T._LinearFn, "apply", staticmethod(stub("library", lambda a, k: a[3])))
+    callee = {T.LIBRARY_FP32: ("library", False), T.LIBRARY_BF16: ("library", True), T.OWN_BF16: ("vit_linear", "bf16"), T.OWN_SPLIT: ("vit_linear", "split")}
+    native = {T.OWN_BF16: ni.LINEAR_BF16, T.OWN_SPLIT: ni.LINEAR_SPLIT}
+    assert len(set(callee)) == 4
+    for (impl, on), name in ROUTE_TABLE.items():
+        b.set_linear_impl(impl)
+        b.set_bf16(on)
+        want = getattr(T, name)
+        assert [T.linear_route(lin) for lin in _lins(b)] == [want] * 8, (impl, on)
+        for blk in b.blocks:
+            for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1):
+                del routed[:]
+                T._linear(xc, lin)
+                assert routed == [callee[want]], (impl, on, routed)
+            del routed[:]
+            T._linear(torch.zeros(1, 5, 3072).as_subclass(_Cuda), blk.mlp.fc2, with_bias=False)
+            assert routed == [callee[want]], (impl, on, routed)
+            own = want in native
+            assert bool(blk.mlp._fused_ftx(xc)) is own, (impl, on)
+            del routed[:]
+            blk.mlp(xc)
+            assert routed == ([("vit_mlp", callee[want][1])] if own else [callee[want]] * 2), (impl, on, routed)
+        if own:
+            assert ni.modes(net) == (native[want], ni.ATTN_FP32), (impl, on)
+        else:
+            with pytest.raises(ni.Unsupported, match="set_bf16" if impl == "ftx" else "library"):
+                ni.modes(net)
+
+
+def test_every_linears_switches_reach_both_graph_keys_and_the_table_signature(monkeypatch):
+    """Flipping ftx_bf16 or ftx_linear_impl of ONE Linear of a block changes _graph_key, _infer_key and NativeImage._signature, and
+    restoring it restores them.  Before the keys were built from block_switches this failed for ftx_bf16 of attn.proj and of mlp.fc2 on
+    both graph keys: they recorded ftx_bf16 of attn.qkv and mlp.fc1 only, so a captured graph would have replayed the old kernels."""
+    from fusiontransformer_amd import native_image as ni
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)   # the keys record the device; no GPU is touched here
+    net = _image_branch()
+    b = net.backbone
+    b.set_bf16(False)
+    ex = ni.NativeImage(net)
+    x = torch.zeros(1, 3, 384, 384)
+
+    def keys():
+        return b._graph_key(x), b._infer_key(x), ex._signature()
+    base = keys()
+    blk = b.blocks[0]
+    for name, lin in (("qkv", blk.attn.qkv), ("proj", blk.attn.proj), ("fc1", blk.mlp.fc1), ("fc2", blk.mlp.fc2)):
+        for attr, other in (("ftx_bf16", True), ("ftx_linear_impl", "ftx_split")):
+            was = getattr(lin, attr)
+            assert was != other
+            setattr(lin, attr, other)
+            assert [new != old for new, old in zip(keys(), base)] == [True] * 3, (name, attr)
+            setattr(lin, attr, was)
+            assert keys() == base, (name, attr)
