@@ -97,6 +97,13 @@ SIGNATURES = {
     "ftx_spconv_pairs_wgrad_bf16": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "ftx_spconv_gemm_bf16_block_cols": (_i32, [_i32, _i64, _i32]),
     "ftx_spconv_wgrad_bf16_table_blocks": (_i32, [_i32, _i32, _i32, _i32]),
+    "ftx_spconv_pairs_gemm_split": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_spconv_pairs_gemm_scatter_split": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "ftx_rows_gemm_split": (C.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "ftx_spconv_pairs_wgrad_split_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "ftx_spconv_pairs_wgrad_split": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ftx_spconv_gemm_split_block_cols": (_i32, [_i32, _i64, _i32]),
+    "ftx_spconv_wgrad_split_table_blocks": (_i32, [_i32, _i32, _i32, _i32]),
     "ftx_bn_workspace_bytes": (_sz, [_i64, _i32]),
     "ftx_bn_train_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ftx_bn_eval_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _i32, _vp, _vp]),

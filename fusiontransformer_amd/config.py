@@ -61,6 +61,9 @@ def get_cfg_defaults() -> CfgNode:
             "USE_IMAGE": False, "USE_LIDAR": False, "USE_FUSION": False, "IMAGE_PRETRAINED_PATH": "",
             "middle_feat_block_number": None, "late_feat_block_number": None,
             "image_stn": False,      # build_model builds TYPE="ImageSeg" only when this is set (image_stn_cfg())
+            # the LiDAR branch's GEMM operands (SPVCNN.set_bf16 / set_split; at most one of the two): rounded to bf16, or split into
+            # three bf16 pieces for fp32-class results on the bf16 MFMA.  Both off: the exact fp32 MFMA.
+            "lidar_bf16": False, "lidar_split": False,
         },
         "OPTIMIZER": {"TYPE": "", "BASE_LR": 0.001, "WEIGHT_DECAY": 0.0, "Adam": {"betas": (0.9, 0.999)}},
         "TRAIN": {"BATCH_SIZE": 0, "CLASS_WEIGHTS": [], "FusionTransformer": {"lambda_xm": 0.0}},

@@ -15,22 +15,9 @@
 // The kernels (dense_gemm_kernel, dense_wgrad_kernel), the epilogue, the tile and split rules and the host layer are shared with
 // ftx_dense_bf16.hip: ftx_dense_common.h.  This file says what is the split family's own, the description DenseSplit, and holds its entries.
 #include "ftx_dense_common.h"
+#include "ftx_split.h"   // split1: the ONE definition of the split, shared with ftx_spconv_split.hip
 
 using namespace ftx;
-
-namespace {
-
-// the ONE definition of the split: h + m + l == x for finite x in range; h = inf / NaN keeps m = l = 0
-__device__ inline void split1(float x, __bf16 &h, __bf16 &m, __bf16 &l) {
-  h = (__bf16)x;
-  const float hf = (float)h;
-  const bool finite = (__float_as_uint(hf) & 0x7f800000u) != 0x7f800000u;
-  const float r = finite ? x - hf : 0.f;
-  m = (__bf16)r;
-  l = (__bf16)(r - (float)m);
-}
-
-}  // namespace
 
 struct DenseSplit {
   static constexpr const char *gemm_name = "ftx_dense_gemm_split", *wgrad_name = "ftx_dense_wgrad_split";

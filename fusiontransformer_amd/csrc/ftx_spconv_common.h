@@ -4,7 +4,9 @@
 // their staging differs by design (fp32: row-major rows, interleaved sub-tiles, two register stages; bf16: transposed k-contiguous
 // images, one stage), and one body would be two kernels under one name.  A family brings exactly: its weight-gradient kernel, and a
 // description (SpconvF32, SpconvBf16) with the entry names that front its messages, the pair GEMM's LDS element type, row stride and
-// fragment-pointer placement, the weight gradient's occupancy table and tile-length step, and two launch hooks.  Nothing here is
+// fragment-pointer placement, the weight gradient's occupancy table and tile-length step, and two launch hooks.  The third family
+// (ftx_spconv_split.hip, SpconvSplit: three bf16 pieces per operand, fp32-class results) takes everything here but the pair-GEMM body:
+// its `gemm` hook launches a kernel of its own, so it brings no GEMM LDS type, stride or pointer placement.  Nothing here is
 // selected by process-wide mutable state or by a device query: tile shapes, workspace sizes and summation trees are functions of the
 // arguments alone.
 #pragma once
@@ -198,6 +200,8 @@ __global__ __launch_bounds__(256) void pairs_gemm_kernel(const float *__restrict
   float4 ra[A_PASSES], rb[B_PASSES];
   // The chunk loader is a lambda of the kernel and must stay one: as a function of this header the compiler ordered its instructions
   // differently and the 32 -> 32 layers ran 4-5 % slower (profiles/spconv_shared_host.txt, section 1).
+  // pairs_gemm_split_kernel (ftx_spconv_split.hip) holds a copy of it for the same reason: the clamping and zero-fill rules below are
+  // what keeps every load inside its operand, so the two copies change together.
   auto load_chunk = [&](int c0) {
     if (kfull) {
 #pragma unroll
@@ -324,15 +328,16 @@ namespace ftx {
 // ---------------------------------------------------------------------------------------
 // device: weight gradient
 // ---------------------------------------------------------------------------------------
-// One round of a tile: the indices of pairs [rbase, rend), rend - rbase <= kWgradRound, into LDS (idx_a == nullptr: pair p joins row p
+// One round of a tile: the indices of pairs [rbase, rend), rend - rbase <= ROUND, into LDS (idx_a == nullptr: pair p joins row p
 // of A and G).  Every slot gets a loadable row: slots past the end repeat row 0, malformed pairs are flagged in s_ok and s_bad and
-// zeroed at store time.
+// zeroed at store time.  ROUND is kWgradRound unless a family's LDS budget asks for less (ftx_spconv_split.hip).
+template <int ROUND = kWgradRound>
 __device__ __forceinline__ void wgrad_stage_indices(const int32_t *__restrict__ idx_a, int64_t rows_a, const int32_t *__restrict__ idx_g, int64_t rows_g,
                                            int rbase, int rend, int32_t *s_ia, int32_t *s_ig, uint8_t *s_ok, int *s_bad) {
   __syncthreads();  // previous round's gathers are done with s_ia / s_ig
   if (threadIdx.x == 0) *s_bad = 0;
   __syncthreads();
-  for (int t = threadIdx.x; t < kWgradRound; t += 256) {
+  for (int t = threadIdx.x; t < ROUND; t += 256) {
     int32_t ia = 0, ig = 0;
     uint8_t ok = 0;
     if (t < rend - rbase) {

@@ -52,7 +52,7 @@ inline MapSides map_sides(const Layer &L, const Map &M) {
 }
 
 // The four sparse-convolution entries of a layer's precision family (include/ftx.h): the ONE place the executors pick between the
-// fp32 entries and their bf16 twins.
+// fp32 entries (operand mode 0), their bf16 twins (1) and their three-piece split twins (2); check_program admits no other mode.
 struct SpconvEntries {
   decltype(&ftx_spconv_pairs_gemm) pairs;
   decltype(&ftx_spconv_pairs_gemm_scatter) scatter;
@@ -60,6 +60,7 @@ struct SpconvEntries {
   decltype(&ftx_spconv_pairs_wgrad) wgrad;
 };
 inline SpconvEntries spconv_entries(const Layer &L) {
+  if (L.bf16 == 2) return {ftx_spconv_pairs_gemm_split, ftx_spconv_pairs_gemm_scatter_split, ftx_rows_gemm_split, ftx_spconv_pairs_wgrad_split};
   if (L.bf16) return {ftx_spconv_pairs_gemm_bf16, ftx_spconv_pairs_gemm_scatter_bf16, ftx_rows_gemm_bf16, ftx_spconv_pairs_wgrad_bf16};
   return {ftx_spconv_pairs_gemm, ftx_spconv_pairs_gemm_scatter, ftx_rows_gemm, ftx_spconv_pairs_wgrad};
 }
@@ -152,6 +153,7 @@ static inline int check_program(const SpvcnnTables &T, bool train, SlotFacts &F)
                     "%s: op %d (%s) layer %d: channels must be multiples of 4 (ca=%d co=%d)", who, i, kn, o.layer, L.ca, L.co);
         FTX_REQUIRE(L.co == o.channels && need_src(o.src, L.ca), "%s: op %d (%s) layer %d: channel counts do not match the slots", who, i, kn, o.layer);
         FTX_REQUIRE(L.weight && L.gamma && L.beta && L.mean && L.var, "%s: op %d (%s) layer %d: null parameter", who, i, kn, o.layer);
+        FTX_REQUIRE(L.bf16 >= 0 && L.bf16 <= 2, "%s: op %d (%s) layer %d: operand mode %d is not 0 (fp32), 1 (bf16) or 2 (split)", who, i, kn, o.layer, L.bf16);
         const int r = T.routes[i];
         F.op[i].temp_rows = n_dst;
         if (o.src != FTX_SPVCNN_SLOT_INPUT) grad_to[0] = o.src;
@@ -180,7 +182,8 @@ static inline int check_program(const SpvcnnTables &T, bool train, SlotFacts &F)
             if (!train) FTX_REQUIRE(!M.n_pairs || (M.pair_in && M.pair_out && M.koff), "%s: op %d (%s): null pair list in map %d", who, i, kn, o.map);
           } else if (r == FTX_SPVCNN_ROUTE_OSTAT) {
             // eval: the kernel needs a row on either side; train (no empty level): the route's statistics epilogue needs a pair
-            FTX_REQUIRE(!L.bf16 && !L.transposed && ftx_spconv_ostat_supported(L.ca, L.co, L.kvol, 0) && n_dst <= kOstatMaxRows &&
+            // the kernel is exact fp32: that is mode 0, and it meets mode 2's fp32-class contract; a bf16 layer never takes it
+            FTX_REQUIRE(L.bf16 != 1 && !L.transposed && ftx_spconv_ostat_supported(L.ca, L.co, L.kvol, 0) && n_dst <= kOstatMaxRows &&
                             (train ? M.n_pairs > 0 : n_dst >= 1 && m_in >= 1),
                         "%s: op %d (%s) layer %d: the output-stationary route does not take this layer", who, i, kn, o.layer);
             FTX_REQUIRE(M.nbr, "%s: op %d (%s): null neighbour table in map %d", who, i, kn, o.map);

@@ -469,13 +469,39 @@ def _log_launch(kind, meta, launch):
     return out
 
 
-# bf16=True: the bf16-operand twins of the pair GEMM and the weight gradient (csrc/ftx_spconv_bf16.hip; the operands are rounded to bf16,
-# accumulation and storage stay fp32, include/ftx.h).  (C entry, launch-log kind) per precision.
-_PAIRS_GEMM = {False: ("ftx_spconv_pairs_gemm", "spconv_pairs_gemm"), True: ("ftx_spconv_pairs_gemm_bf16", "spconv_pairs_gemm_bf16")}
-_PAIRS_GEMM_SCATTER = {False: "ftx_spconv_pairs_gemm_scatter", True: "ftx_spconv_pairs_gemm_scatter_bf16"}
-_PAIRS_WGRAD = {False: ("ftx_spconv_pairs_wgrad", "ftx_spconv_pairs_wgrad_workspace_bytes", "spconv_pairs_wgrad"),
-                True: ("ftx_spconv_pairs_wgrad_bf16", "ftx_spconv_pairs_wgrad_bf16_workspace_bytes", "spconv_pairs_wgrad_bf16")}
-_ROWS_GEMM = {False: "ftx_rows_gemm", True: "ftx_rows_gemm_bf16"}
+# The operand modes of the pair GEMM, the dense rows and the weight gradient, as the layer record of the executors numbers them
+# (include/ftx.h).  "fp32": the exact fp32 MFMA (csrc/ftx_spconv.hip).  "bf16": the operands rounded to bf16 (csrc/ftx_spconv_bf16.hip).
+# "split": every operand split into three bf16 pieces, six piece products summed in fp32 -- fp32-class results on the bf16 MFMA
+# (csrc/ftx_spconv_split.hip).  Accumulation and storage are fp32 in all three.  False == 0 and True == 1, so bf16=False / bf16=True
+# index the tables below as they always did.
+FP32, BF16, SPLIT = 0, 1, 2
+OPERANDS = {"fp32": FP32, "bf16": BF16, "split": SPLIT}
+
+
+def operand_mode(bf16=False, operands=None):
+    """The mode (FP32, BF16 or SPLIT) that the public pair `bf16=`, `operands=` names.  operands=None: bf16=False / True mean what
+    they always meant.  operands="fp32" | "bf16" | "split" names the mode itself; bf16=True next to another mode is a contradiction
+    and refused.  `bf16` is a flag, not a mode number: anything but False / True (0 / 1) is refused, so `bf16=2` never means split.
+    Inside this module a resolved mode travels in the launchers' and autograd nodes' `bf16` argument and is never resolved again."""
+    if operands is None:
+        if bf16 not in (False, True):
+            raise ValueError(f"bf16 must be False or True, got {bf16!r}")
+        return int(bf16)
+    if operands not in OPERANDS:
+        raise ValueError(f"operands must be 'fp32', 'bf16' or 'split', got {operands!r}")
+    if bf16 and OPERANDS[operands] != BF16:
+        raise ValueError(f"bf16=True contradicts operands={operands!r}")
+    return OPERANDS[operands]
+
+
+# (C entry, launch-log kind) per mode
+_PAIRS_GEMM = {FP32: ("ftx_spconv_pairs_gemm", "spconv_pairs_gemm"), BF16: ("ftx_spconv_pairs_gemm_bf16", "spconv_pairs_gemm_bf16"),
+               SPLIT: ("ftx_spconv_pairs_gemm_split", "spconv_pairs_gemm_split")}
+_PAIRS_GEMM_SCATTER = {FP32: "ftx_spconv_pairs_gemm_scatter", BF16: "ftx_spconv_pairs_gemm_scatter_bf16", SPLIT: "ftx_spconv_pairs_gemm_scatter_split"}
+_PAIRS_WGRAD = {FP32: ("ftx_spconv_pairs_wgrad", "ftx_spconv_pairs_wgrad_workspace_bytes", "spconv_pairs_wgrad"),
+                BF16: ("ftx_spconv_pairs_wgrad_bf16", "ftx_spconv_pairs_wgrad_bf16_workspace_bytes", "spconv_pairs_wgrad_bf16"),
+                SPLIT: ("ftx_spconv_pairs_wgrad_split", "ftx_spconv_pairs_wgrad_split_workspace_bytes", "spconv_pairs_wgrad_split")}
+_ROWS_GEMM = {FP32: "ftx_rows_gemm", BF16: "ftx_rows_gemm_bf16", SPLIT: "ftx_rows_gemm_split"}
 
 
 # The launchers: the ONE call site of each convolution / BatchNorm entry point and of its launch-log metadata.  Pointers are raw device
@@ -544,24 +570,24 @@ def _launch_bn_bwd(gy, x, y, gamma, beta, mean, invstd, n, c, relu, gx, gres, gg
         L.ftx_bn_train_bwd(gy, x, y, gamma, beta, mean, invstd, n, c, int(relu), gx, gres, ggamma, gbeta, ws, ws_bytes, st), "ftx_bn_train_bwd"))
 
 
-def _spconv_apply(A, W, gather, pos, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False):
+def _spconv_apply(A, W, gather, pos, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False, operands=None, mode=None):
     """reduce(pairs_gemm(A[gather] @ W[k]), pos) -> (n_rows_out, co)."""
     rows_a, ca = A.shape
     tmp = _empty((n_pairs, co), F32, A)
     out = _empty((n_rows_out, co), F32, A)
     _launch_pairs(ptr(A), rows_a, ptr(gather), ptr(W), int(w_transposed), ptr(pos), ptr(koff), n_pairs, ca, co, koff.shape[0] - 1, ptr(tmp), ptr(out),
-                  n_rows_out, stream(), bool(bf16))
+                  n_rows_out, stream(), operand_mode(bf16, operands) if mode is None else mode)
     return out
 
 
-def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False):
+def _spconv_direct(A, W, gather, scatter, koff, n_pairs, n_rows_out, co, w_transposed, bf16=False, operands=None, mode=None):
     """out[scatter[p]] = A[gather[p]] @ W[k(p)] in ONE launch, for maps whose destination side is a bijection of the pair list."""
     rows_a, ca = A.shape
     if n_pairs != n_rows_out:
         raise ValueError("direct sparse conv: the pair list must cover every destination row exactly once")
     out = _empty((n_rows_out, co), F32, A)
     _launch_direct(ptr(A), rows_a, ptr(gather), ptr(scatter), ptr(W), int(w_transposed), ptr(koff), n_pairs, ca, co, koff.shape[0] - 1, ptr(out),
-                   n_rows_out, stream(), bool(bf16))
+                   n_rows_out, stream(), operand_mode(bf16, operands) if mode is None else mode)
     return out
 
 
@@ -600,14 +626,15 @@ def _spconv_ostat(A, W, nbr, n_rows_out, co, w_transposed, flip, part=0, nb=0, p
     return out
 
 
-def _spconv_wgrad(A, idx_a, G, idx_g, koff, n_pairs, bf16=False):
+def _spconv_wgrad(A, idx_a, G, idx_g, koff, n_pairs, bf16=False, operands=None, mode=None):
+    mode = operand_mode(bf16, operands) if mode is None else mode      # mode: already resolved (the autograd nodes)
     rows_a, ca = A.shape
     rows_g, cg = G.shape
     kvol = koff.shape[0] - 1
     dW = _empty((kvol, ca, cg), F32, A)
-    ws_bytes = _ws_bytes(_PAIRS_WGRAD[bool(bf16)][1], n_pairs, ca, cg, kvol)
+    ws_bytes = _ws_bytes(_PAIRS_WGRAD[mode][1], n_pairs, ca, cg, kvol)
     ws = _scratch(ws_bytes, A)
-    _launch_wgrad(ptr(A), rows_a, ptr(idx_a), ptr(G), rows_g, ptr(idx_g), ptr(koff), n_pairs, ca, cg, kvol, ptr(dW), ptr(ws), ws_bytes, stream(), bool(bf16))
+    _launch_wgrad(ptr(A), rows_a, ptr(idx_a), ptr(G), rows_g, ptr(idx_g), ptr(koff), n_pairs, ca, cg, kvol, ptr(dW), ptr(ws), ws_bytes, stream(), mode)
     return dW
 
 
@@ -635,7 +662,8 @@ def _conv_route(km, transposed, ca, co, kvol, rows, bf16, grad=False):
     """How sparse_conv and conv_bn_train compute the (rows, co) result of a ca -> co GEMM over the map's pairs: a layer's forward, or
     (grad=True) its data gradient.  _DIRECT: one launch with the scatter epilogue, where every row written is the destination of
     exactly one pair (the strided 2^3 map seen from its fine side: forward of the transposed conv, data gradient of the strided one).
-    _OSTAT: the output-stationary kernel on the neighbour table, for the thin fp32 forward layers.  _PAIRS: pair GEMM + reduce.
+    _OSTAT: the output-stationary kernel on the neighbour table, for the thin forward layers of the fp32 and the split mode (the kernel
+    is exact fp32, which meets the split mode's fp32-class contract; `bf16` is the operand mode).  _PAIRS: pair GEMM + reduce.
     _EMPTY: no pair or no row -- the forward takes the pair list without the statistics-producing forms, the gradient is a zero fill."""
     if grad:
         if rows == 0 or km.n_pairs == 0:
@@ -645,21 +673,21 @@ def _conv_route(km, transposed, ca, co, kvol, rows, bf16, grad=False):
         return _DIRECT
     if rows == 0 or km.n_pairs == 0:
         return _EMPTY
-    if not bf16 and not transposed and ostat_preferred(ca, co, kvol, rows=rows):
+    if bf16 != BF16 and not transposed and ostat_preferred(ca, co, kvol, rows=rows):
         return _OSTAT
     return _PAIRS
 
 
 def _conv_forward(feats, kernel, km, transposed, bf16=False):
-    """bf16=True: the bf16-operand kernels; the output-stationary kernel is exact fp32 only, so every layer takes the pair list."""
+    """`bf16`: the operand mode.  BF16: the output-stationary kernel is exact fp32 only, so every layer takes the pair list."""
     kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
     route = _conv_route(km, transposed, ca, co, kvol, n_out, bf16)
     src, _, dst, dst_pos = _map_sides(km, transposed)
     if route == _DIRECT:
-        return _spconv_direct(feats, kernel, src, dst, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
+        return _spconv_direct(feats, kernel, src, dst, km.koff, km.n_pairs, n_out, co, 0, mode=bf16)
     if route == _OSTAT:
         return _spconv_ostat(feats, kernel, km.nbr, n_out, co, 0, 0, pairs=km.n_pairs)
-    return _spconv_apply(feats, kernel, src, dst_pos, km.koff, km.n_pairs, n_out, co, 0, bf16=bf16)
+    return _spconv_apply(feats, kernel, src, dst_pos, km.koff, km.n_pairs, n_out, co, 0, mode=bf16)
 
 
 def _conv_backward(feats, kernel, km, transposed, grad_out, need_feats, need_kernel, bf16=False):
@@ -672,11 +700,11 @@ def _conv_backward(feats, kernel, km, transposed, grad_out, need_feats, need_ker
         if route == _EMPTY:
             g_feats = torch.zeros((n_feats, ca), dtype=F32, device=feats.device)
         elif route == _DIRECT:
-            g_feats = _spconv_direct(grad_out, kernel, dst, src, km.koff, km.n_pairs, n_feats, ca, 1, bf16=bf16)
+            g_feats = _spconv_direct(grad_out, kernel, dst, src, km.koff, km.n_pairs, n_feats, ca, 1, mode=bf16)
         else:
-            g_feats = _spconv_apply(grad_out, kernel, dst, src_pos, km.koff, km.n_pairs, n_feats, ca, 1, bf16=bf16)
+            g_feats = _spconv_apply(grad_out, kernel, dst, src_pos, km.koff, km.n_pairs, n_feats, ca, 1, mode=bf16)
     if need_kernel:
-        g_kernel = _spconv_wgrad(feats, src, grad_out, dst, km.koff, km.n_pairs, bf16=bf16)
+        g_kernel = _spconv_wgrad(feats, src, grad_out, dst, km.koff, km.n_pairs, mode=bf16)
     return g_feats, g_kernel
 
 
@@ -703,9 +731,11 @@ class _SparseConv(torch.autograd.Function):
         return g_feats, g_kernel, None, None, None
 
 
-def sparse_conv(feats, kernel, km, transposed=False, bf16=False):
-    """bf16=True: forward, data gradient and weight gradient on bf16-rounded operands with fp32 accumulation (include/ftx.h)."""
-    return _SparseConv.apply(feats, kernel, km, transposed, bool(bf16))
+def sparse_conv(feats, kernel, km, transposed=False, bf16=False, operands=None):
+    """bf16=True (operands="bf16"): forward, data gradient and weight gradient on bf16-rounded operands with fp32 accumulation.
+    operands="split": the three on three-piece split operands, fp32-class results on the bf16 MFMA; layers the output-stationary kernel
+    takes in fp32 mode keep it (it is exact fp32).  The contracts are stated in include/ftx.h."""
+    return _SparseConv.apply(feats, kernel, km, transposed, operand_mode(bf16, operands))
 
 
 # ---------------------------------------------------------------- dense rows (skinny GEMMs)
@@ -713,7 +743,7 @@ def _rows_gemm(A, W, w_transposed, bias, co, bf16=False):
     L = _lib.load()
     n, ca = A.shape
     out = _empty((n, co), F32, A)
-    fn = _ROWS_GEMM[bool(bf16)]
+    fn = _ROWS_GEMM[bf16]                      # a resolved mode, as in the launchers above
     check(getattr(L, fn)(ptr(A), n, ptr(W), int(w_transposed), ptr(bias), ca, co, ptr(out), stream()), fn)
     return out
 
@@ -721,7 +751,7 @@ def _rows_gemm(A, W, w_transposed, bias, co, bf16=False):
 def _rows_wgrad(A, G, bf16=False):
     """A (n, ca)^T @ G (n, cg) -> (ca, cg)."""
     L = _lib.load()
-    fn, ws_fn, _ = _PAIRS_WGRAD[bool(bf16)]
+    fn, ws_fn, _ = _PAIRS_WGRAD[bf16]
     n, ca = A.shape
     cg = G.shape[1]
     dW = _empty((1, ca, cg), F32, A)
@@ -813,21 +843,25 @@ class _LibraryMatmulBf16(torch.autograd.Function):
         return gx, gw, gb
 
 
-def linear(x, weight, bias=None, bf16=False):
+def linear(x, weight, bias=None, bf16=False, operands=None):
     """nn.Linear on point / voxel rows.  Skinny shapes (tens of thousands of rows, <= 384 channels)
-    run on libftx's tile kernel; anything else is a plain library GEMM.  bf16=True: x, weight (and in the backward the output
-    gradient) rounded to bf16 as GEMM operands, fp32 accumulation, on every shape."""
+    run on libftx's tile kernel; anything else is a plain library GEMM.  bf16=True (operands="bf16"): x, weight (and in the backward
+    the output gradient) rounded to bf16 as GEMM operands, fp32 accumulation, on every shape.  operands="split": the tile kernel on
+    three-piece split operands (fp32-class results); a shape the tile kernel does not take runs the plain fp32 library GEMM."""
+    mode = operand_mode(bf16, operands)
     if x.dim() == 2 and _rows_ok(x.shape[1], weight.shape[0]) and max(weight.shape) <= 512:
-        return _RowsLinear.apply(x, weight, bias, bool(bf16))
-    if bf16:
+        return _RowsLinear.apply(x, weight, bias, mode)
+    if mode == BF16:
         return _LibraryMatmulBf16.apply(x, weight.t(), bias)
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def rows_matmul(x, kernel, bf16=False):
+def rows_matmul(x, kernel, bf16=False, operands=None):
+    """x (N, ca) @ kernel (ca, co); `bf16` / `operands` as in linear()."""
+    mode = operand_mode(bf16, operands)
     if x.dim() == 2 and _rows_ok(*kernel.shape) and max(kernel.shape) <= 512:
-        return _RowsMatmul.apply(x, kernel, bool(bf16))
-    if bf16:
+        return _RowsMatmul.apply(x, kernel, mode)
+    if mode == BF16:
         return _LibraryMatmulBf16.apply(x, kernel, None)
     return torch.matmul(x, kernel)
 
@@ -1016,12 +1050,12 @@ class _ConvBNTrain(torch.autograd.Function):
 
 
 def conv_bn_train(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, residual=None, relu=False,
-                  bf16=False, remask=True):
-    """Conv3d -> BatchNorm(training) (+ residual) (+ ReLU) in one autograd node; see _ConvBNTrain.  bf16=True: the convolution's
-    forward, data gradient and weight gradient on bf16-rounded operands (as sparse_conv(bf16=True)); BatchNorm stays fp32.
-    remask: as in batch_norm."""
-    return _ConvBNTrain.apply(feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, bool(bf16),
-                              bool(remask))
+                  bf16=False, remask=True, operands=None):
+    """Conv3d -> BatchNorm(training) (+ residual) (+ ReLU) in one autograd node; see _ConvBNTrain.  bf16=True (operands="bf16"): the
+    convolution's forward, data gradient and weight gradient on bf16-rounded operands (as sparse_conv(bf16=True)); operands="split":
+    on three-piece split operands (as sparse_conv(operands="split")).  BatchNorm stays fp32.  remask: as in batch_norm."""
+    return _ConvBNTrain.apply(feats, kernel, km, transposed, residual, gamma, beta, running_mean, running_var, momentum, eps, relu,
+                              operand_mode(bf16, operands), bool(remask))
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, residual=None, relu=False, remask=True):
@@ -1057,21 +1091,24 @@ def spconv_reduce_bn_eval(tmp, pos, n_out, gamma, beta, running_mean, running_va
     return out
 
 
-def conv_bn_eval(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, eps=1e-5, residual=None, relu=False, bf16=False):
+def conv_bn_eval(feats, kernel, km, transposed, gamma, beta, running_mean, running_var, eps=1e-5, residual=None, relu=False, bf16=False,
+                 operands=None):
     """Conv3d -> BatchNorm(eval) (+ residual) (+ ReLU) without autograd.  On the pair-list route (and for an empty map) the reduce carries
     the BatchNorm in its epilogue: pair GEMM + ftx_spconv_reduce_bn_eval, two launches instead of three and one (n_out, co) round trip
-    less; the other routes run sparse_conv's launch and the eval BatchNorm pass.  Bit-identical to sparse_conv + batch_norm(training=False)."""
+    less; the other routes run sparse_conv's launch and the eval BatchNorm pass.  Bit-identical to sparse_conv + batch_norm(training=False)
+    in the same operand mode (`bf16` / `operands` as in sparse_conv)."""
+    mode = operand_mode(bf16, operands)
     feats = req(feats.contiguous(), F32, "conv3d feats", 2)
     kernel = req(kernel.contiguous(), F32, "conv3d kernel", 3)
     kvol, ca, co, n_in, n_out = _conv_shapes(feats, kernel, km, transposed)
-    route = _conv_route(km, transposed, ca, co, kvol, n_out, bf16)
+    route = _conv_route(km, transposed, ca, co, kvol, n_out, mode)
     if route in (_PAIRS, _EMPTY) and kvol in (8, 27):
         src, _, _, dst_pos = _map_sides(km, transposed)
         tmp = _empty((km.n_pairs, co), F32, feats)
-        _launch_pairs_gemm(ptr(feats), n_in, ptr(src), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(tmp), n_out, stream(), bool(bf16))
+        _launch_pairs_gemm(ptr(feats), n_in, ptr(src), ptr(kernel), 0, ptr(km.koff), km.n_pairs, ca, co, kvol, ptr(tmp), n_out, stream(), mode)
         return spconv_reduce_bn_eval(tmp, dst_pos, n_out, gamma, beta, running_mean, running_var, eps, residual=residual, relu=relu)
     with torch.no_grad():
-        return batch_norm(_conv_forward(feats, kernel, km, transposed, bool(bf16)), gamma, beta, running_mean, running_var, False, eps=eps,
+        return batch_norm(_conv_forward(feats, kernel, km, transposed, mode), gamma, beta, running_mean, running_var, False, eps=eps,
                           residual=residual, relu=relu)
 
 

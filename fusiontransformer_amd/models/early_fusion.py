@@ -13,6 +13,7 @@ class Net3DSeg(SPVCNN):
         self.early_fusion_transform = nn.Sequential(nn.Linear(96, 32), BatchNorm(32), nn.ReLU(True))
         heads(self, self.cs[-1], num_classes, dual_head)
         self.set_bf16(self.lidar_bf16)   # now early_fusion_transform exists too
+        self.set_split(self.lidar_split)
 
     def _fuse(self, img_early_feats):
         # z0.F = z0.F + early_fusion_transform(img_early_feats)  (early_fusion.py:39)

@@ -13,6 +13,7 @@ class Net3DSeg(SPVCNN):
         self.middle_fusion_transform = nn.Sequential(nn.Linear(96, self.cs[4]), BatchNorm(self.cs[4]), nn.ReLU(True))
         heads(self, self.cs[-1], num_classes, dual_head)
         self.set_bf16(self.lidar_bf16)   # now middle_fusion_transform exists too
+        self.set_split(self.lidar_split)
 
     def _fuse(self, img_middle_feats):
         # z1.F = z1.F + point_transforms[0](z0.F) + middle_fusion_transform(img_middle_feats)  (middle_fusion.py:48)

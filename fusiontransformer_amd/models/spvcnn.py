@@ -42,17 +42,26 @@ class Conv3d(nn.Module):
 
     def forward(self, x: SparseTensor) -> SparseTensor:
         if self.kernel_size == 1 and self.stride == 1:
-            out = x.derive(spf.rows_matmul(x.F, self.kernel, bf16=bf16_operands(self)))
+            out = x.derive(spf.rows_matmul(x.F, self.kernel, operands=operand_mode(self)))
         else:
             km, coords, stride = _conv_map(self, x)
-            out = x.derive(spf.sparse_conv(x.F, self.kernel, km, self.t, bf16=bf16_operands(self)), coords, stride)
+            out = x.derive(spf.sparse_conv(x.F, self.kernel, km, self.t, operands=operand_mode(self)), coords, stride)
         out.check()
         return out
 
 
+def operand_mode(module):
+    """SPVCNN.set_bf16 / set_split as they stand on a Conv3d or a point-branch nn.Linear: "fp32", "bf16" or "split", the `operands=`
+    of the functional layer (functional.OPERANDS numbers them for the executors' layer records).  The one reader of `ftx_bf16` and
+    `ftx_split` for the LiDAR branch."""
+    if getattr(module, "ftx_split", False):
+        return "split"
+    return "bf16" if getattr(module, "ftx_bf16", False) else "fp32"
+
+
 def bf16_operands(module):
-    """SPVCNN.set_bf16 as it stands on a Conv3d or a point-branch nn.Linear: the one reader of `ftx_bf16` for the LiDAR branch."""
-    return bool(getattr(module, "ftx_bf16", False))
+    """Whether the module's GEMM operands are rounded to bf16 (SPVCNN.set_bf16), through operand_mode."""
+    return operand_mode(module) == "bf16"
 
 
 def step_counter(bn):
@@ -116,11 +125,11 @@ def _conv_bn(conv, bn, x, residual=None, relu=True):
     if bn.training:
         bump_step_counter(bn)
         feats = spf.conv_bn_train(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                  residual=residual, relu=relu, bf16=bf16_operands(conv))
+                                  residual=residual, relu=relu, operands=operand_mode(conv))
     else:
         # SPVCNN.set_native_eval where the executor does not run (a layer option it refuses): the reduce carries the eval BatchNorm
         feats = spf.conv_bn_eval(x.F, conv.kernel, km, conv.t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, residual=residual,
-                                 relu=relu, bf16=bf16_operands(conv))
+                                 relu=relu, operands=operand_mode(conv))
     out = x.derive(feats, coords, stride)
     out.check()
     return out
@@ -137,7 +146,7 @@ def _addend_steps(f, token):
 
 def _linear_bn_relu(seq, feats):
     """nn.Sequential(Linear, BatchNorm1d, ReLU) on point rows (spvcnn.py:164-180)."""
-    return seq[1].fused(spf.linear(feats, seq[0].weight, seq[0].bias, bf16=bf16_operands(seq[0])), relu=True)
+    return seq[1].fused(spf.linear(feats, seq[0].weight, seq[0].bias, operands=operand_mode(seq[0])), relu=True)
 
 
 class BasicConvolutionBlock(nn.Module):
@@ -225,7 +234,12 @@ class SPVCNN(nn.Module):
         self.dropout = nn.Dropout(0.3, True)
         # cfg.MODEL.lidar_bf16: the LiDAR branch on bf16-operand kernels, see set_bf16
         self.lidar_bf16 = bool(kwargs.get("lidar_bf16", False))
+        # cfg.MODEL.lidar_split: the LiDAR branch fp32-accurate on the bf16 MFMA (three-piece operand split), see set_split
+        self.lidar_split = bool(kwargs.get("lidar_split", False))
+        if self.lidar_bf16 and self.lidar_split:
+            raise ValueError("lidar_bf16 and lidar_split are two operand modes of the same GEMMs: set at most one")
         self.set_bf16(self.lidar_bf16)
+        self.set_split(self.lidar_split)
         # cfg.MODEL.lidar_native_eval: the eval-mode, no-gradient forward through the native executor, see set_native_eval
         self._native = None
         self.set_native_eval(bool(kwargs.get("lidar_native_eval", False)))
@@ -246,14 +260,32 @@ class SPVCNN(nn.Module):
         point_transforms and of the early / middle fusion transform run their forward, data gradient and weight gradient with the GEMM
         operands rounded to bf16 and fp32 accumulation (include/ftx.h).  BatchNorm, the reduce over offsets and all storage stay fp32.
         The segmentation heads (`linear`, `linear2`) stay fp32.  Subclasses that add a fusion transform call this again after adding it."""
+        if on and getattr(self, "lidar_split", False):
+            raise ValueError("lidar_bf16 and lidar_split are two operand modes of the same GEMMs: set at most one")
         self.lidar_bf16 = bool(on)
-        for m in self.modules():
-            if isinstance(m, Conv3d):
-                m.ftx_bf16 = bool(on)
-        seqs = list(self.point_transforms) + [getattr(self, n) for n in self._FUSION_TRANSFORMS if hasattr(self, n)]
-        for seq in seqs:
-            seq[0].ftx_bf16 = bool(on)
+        for m in self._operand_modules():
+            m.ftx_bf16 = bool(on)
         return self
+
+    def set_split(self, on=True):
+        """fp32-accurate mode of the LiDAR branch on the bf16 matrix cores: exactly the modules set_bf16 flags -- every Conv3d and the
+        nn.Linear of point_transforms and of the early / middle fusion transform, no head -- run their forward, data gradient and weight
+        gradient with every fp32 GEMM operand split into three bf16 pieces and six piece products summed in fp32 (include/ftx.h:
+        ftx_spconv_pairs_gemm_split).  Results are fp32-class: the model meets the gates of the default path, not those of set_bf16.
+        The thin forward layers that the default path sends to the output-stationary kernel keep it (it is exact fp32).  Not both
+        this and set_bf16: ValueError.  Subclasses that add a fusion transform call this again after adding it."""
+        if on and getattr(self, "lidar_bf16", False):
+            raise ValueError("lidar_bf16 and lidar_split are two operand modes of the same GEMMs: set at most one")
+        self.lidar_split = bool(on)
+        for m in self._operand_modules():
+            m.ftx_split = bool(on)
+        return self
+
+    def _operand_modules(self):
+        """The modules whose GEMM operands set_bf16 / set_split switch: every Conv3d and the first module of each point / fusion transform."""
+        convs = [m for m in self.modules() if isinstance(m, Conv3d)]
+        seqs = list(self.point_transforms) + [getattr(self, n) for n in self._FUSION_TRANSFORMS if hasattr(self, n)]
+        return convs + [seq[0] for seq in seqs]
 
     def set_native_eval(self, on=True):
         """Opt-in native executor for the eval-mode forward (include/ftx.h: ftx_spvcnn_eval).  With it on, a forward in eval mode, with

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from . import functional as spf
-from .models.spvcnn import BatchNorm, Conv3d, bf16_operands
+from .models.spvcnn import BatchNorm, Conv3d, operand_mode
 
 _P = "<i8"   # a device pointer in a table
 LAYER = np.dtype([("weight", _P), ("bias", _P), ("gamma", _P), ("beta", _P), ("mean", _P), ("var", _P), ("ca", "<i4"), ("co", "<i4"),
@@ -194,7 +194,7 @@ def layer_table(program: Program) -> np.ndarray:
                 raise Unsupported("parameters must be contiguous float32")
         r["weight"], r["bias"], r["gamma"], r["beta"], r["mean"], r["var"] = (0 if t is None else t.data_ptr() for t in (w, b, g, be, m, v))
         r["ca"], r["co"], r["kvol"], r["stride"], r["transposed"], r["eps"], r["kind"] = l["ca"], l["co"], l["kvol"], l["stride"], l["transposed"], l["eps"], l["kind"]
-        r["bf16"] = int(bf16_operands(l["module"]))
+        r["bf16"] = spf.OPERANDS[operand_mode(l["module"])]     # the record's operand mode: 0 fp32, 1 bf16, 2 split
     return rec
 
 
@@ -227,7 +227,7 @@ def batch_tables(program: Program, layers: np.ndarray, z, x0):
             routes[i] = ROUTE_ROWS
         elif kind == OP_CONV_BN:
             l = layers[layer]
-            routes[i] = ROUTES[spf._conv_route(kms[map_], bool(l["transposed"]), int(l["ca"]), int(l["co"]), int(l["kvol"]), int(rows[level]), bool(l["bf16"]))]
+            routes[i] = ROUTES[spf._conv_route(kms[map_], bool(l["transposed"]), int(l["ca"]), int(l["co"]), int(l["kvol"]), int(rows[level]), int(l["bf16"]))]
     return rows, maps, pvs, routes, kms
 
 
@@ -245,8 +245,8 @@ def arena_bytes(layers, ops, rows, maps, pvs, routes) -> int:
 
 
 class _Host:
-    """What both executors keep per module: the program, its op table and the model table (rebuilt when a parameter moved or the bf16
-    switch changed)."""
+    """What both executors keep per module: the program, its op table and the model table (rebuilt when a parameter moved or a layer's
+    operand mode -- set_bf16 / set_split -- changed)."""
 
     def __init__(self, program):
         self.program = program
@@ -257,7 +257,7 @@ class _Host:
         self.layers = None
 
     def model_table(self):
-        key = tuple([d[n].data_ptr() for d, n in self.refs] + [bf16_operands(m) for m in self.modules])
+        key = tuple([d[n].data_ptr() for d, n in self.refs] + [operand_mode(m) for m in self.modules])
         if key != self.key:
             self.layers = layer_table(self.program)
             self.key = key

@@ -134,7 +134,7 @@ def grad_routes(tp: TrainProgram, layers, rows, kms):
         if op[_K] == ne.OP_CONV_BN and op[_MAP] >= 0 and op[_SRC] != ne.SLOT_INPUT:
             l = layers[op[_LAYER]]
             out[i] = ne.ROUTES[spf._conv_route(kms[op[_MAP]], bool(l["transposed"]), int(l["co"]), int(l["ca"]), int(l["kvol"]),
-                                               int(rows[tp.src_level[i]]), bool(l["bf16"]), grad=True)]
+                                               int(rows[tp.src_level[i]]), int(l["bf16"]), grad=True)]
     return out
 
 

@@ -321,6 +321,37 @@ int ftx_spconv_pairs_wgrad_bf16(const float *A, int64_t rows_a, const int32_t *i
 int32_t ftx_spconv_gemm_bf16_block_cols(int32_t co, int64_t n_pairs, int32_t kvol);
 int32_t ftx_spconv_wgrad_bf16_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng);
 
+/* fp32-accurate sparse convolution on the bf16 MFMA (csrc/ftx_spconv_split.hip): the same calls, with the same arguments, argument
+ * rules and error texts, from a three-piece split of every operand; opt-in (cfg.MODEL.lidar_split), the default stays the exact fp32
+ * entries above.  No operand bit is discarded below the stated range and the result is fp32-class (measured: DESIGN section 5).
+ * Precision contract, the one of the dense split entries (ftx_dense_gemm_split below; csrc/ftx_split.h is the one definition of the
+ * split for both):
+ *   split     every fp32 operand element x -- A and W of the pair GEMM and of the dense rows, A and G of the weight gradient -- is split
+ *             as it is staged, round-to-nearest-even, both subtractions in fp32 (they are exact):
+ *             h = bf16(x),  m = bf16(x - h),  l = bf16((x - h) - m).  If h is not finite, m = l = 0.
+ *   products  six of the nine piece products are summed, fp32 accumulation on v_mfma_f32_32x32x16_bf16: hh, hm, mh, hl, lh, mm (first
+ *             letter: the piece of A).  Each bf16 x bf16 product is exact in fp32.  The dropped ml, lm, ll are each below
+ *             2.01 * 2^-24 * |a b|.
+ *   order     fixed: two fp32 accumulators per output element.  One takes the hh products alone, reduction index ascending.  The other
+ *             takes, per 16-wide reduction step, mm, hl, lh, hm, mh in that order (smallest first).  They are added once, after the
+ *             last step: sum = hh + corrections; the bias is added to that in fp32.  In the weight gradient the waves that share an
+ *             output element each take a subset of the steps (on the smallest tiles: of a step's products, in the order above), add
+ *             their two accumulators once, and their sums are added in wave order; partial tiles are added by wgrad_reduce_kernel in
+ *             tile order.  No atomics: results are deterministic and a function of the arguments alone.  They are not bit-identical to
+ *             the fp32 entries (another summation tree).
+ *   storage   A, W, G, bias, out, dW and the pair rows `tmp` stay fp32; `tmp` keeps the layout of ftx_spconv_pairs_gemm, so
+ *             ftx_spconv_reduce, ftx_spconv_reduce_stats and ftx_spconv_reduce_bn_eval consume it unchanged.
+ * Gather rules as above: an out-of-range source index gives a zero row.  Tile shapes and workspace sizes are functions of the arguments
+ * alone; the column rule is the fp32 entries' (ftx_spconv_gemm_split_block_cols == ftx_spconv_gemm_block_cols). */
+int ftx_spconv_pairs_gemm_split(const float *A, int64_t rows_a, const int32_t *gather, const float *W, int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *tmp, void *stream);
+int ftx_spconv_pairs_gemm_scatter_split(const float *A, int64_t rows_a, const int32_t *gather, const int32_t *scatter, const float *W, int32_t w_transposed, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t co, int32_t kvol, float *out, int64_t rows_out, void *stream);
+int ftx_rows_gemm_split(const float *A, int64_t n, const float *W, int32_t w_transposed, const float *bias, int32_t ca, int32_t co, float *out, void *stream);
+size_t ftx_spconv_pairs_wgrad_split_workspace_bytes(int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol);
+int ftx_spconv_pairs_wgrad_split(const float *A, int64_t rows_a, const int32_t *idx_a, const float *G, int64_t rows_g, const int32_t *idx_g, const int32_t *koff, int64_t n_pairs, int32_t ca, int32_t cg, int32_t kvol, float *dW, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only queries, as ftx_spconv_gemm_block_cols / ftx_spconv_wgrad_table_blocks, for the split kernels' own tilings. */
+int32_t ftx_spconv_gemm_split_block_cols(int32_t co, int64_t n_pairs, int32_t kvol);
+int32_t ftx_spconv_wgrad_split_table_blocks(int32_t mi, int32_t wmg, int32_t ni, int32_t wng);
+
 /* ---- BatchNorm1d over rows (+residual, +ReLU): spnn.BatchNorm / nn.BatchNorm1d
  *      models/spvcnn.py:30-31,71-79,100-102,164-180; models/middle_fusion.py:18-22 */
 
@@ -566,8 +597,12 @@ int ftx_resize_bilinear_u8(const uint8_t *src, int64_t frame_stride, int64_t pit
  *     const float *bias    nn.Linear bias (co) or NULL; NULL for a convolution
  *     const float *gamma, *beta, *running_mean, *running_var   the BatchNorm behind the layer, (co) each
  *     int32 ca, co, kvol (1, 8 or 27; 0 for a Linear), stride, transposed, bf16;  float eps;  int32 kind (FTX_SPVCNN_LAYER_*)
- *     bf16 != 0: the layer's GEMM runs on the bf16-operand entry points (ftx_spconv_pairs_gemm_bf16 / _scatter_bf16, ftx_rows_gemm_bf16),
- *     as SPVCNN.set_bf16 makes the Python path do; the flag is honoured here, nothing falls back.
+ *     bf16 is the layer's operand mode, 0, 1 or 2 (anything else is FTX_EINVAL with the layer named).  1: the layer's GEMM runs on the
+ *     bf16-operand entry points (ftx_spconv_pairs_gemm_bf16 / _scatter_bf16, ftx_rows_gemm_bf16), as SPVCNN.set_bf16 makes the Python
+ *     path do.  2: on the three-piece split entry points (ftx_spconv_pairs_gemm_split / _scatter_split, ftx_rows_gemm_split, in
+ *     training ftx_spconv_pairs_wgrad_split), as SPVCNN.set_split does; the output-stationary route is exact fp32, which meets the
+ *     split mode's fp32-class contract, so a mode-2 layer may take it wherever a mode-0 layer may (a mode-1 layer never).  The mode is
+ *     honoured here, nothing falls back.
  *   op (the static program of the network, emitted once per model by the host; fusiontransformer_amd/native_eval.py emits SPVCNN's):
  *     int32 kind (FTX_SPVCNN_OP_*), segment (0 stem, 1 encoder, 2 decoder; ascending), layer (index into the model table; for ADD_EXT
  *     0 = the early-fusion addend, 1 = the middle-fusion addend), map (index into the kernel maps for CONV_BN with kvol > 1, into the

@@ -5,6 +5,7 @@ usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/s
        python tools/bench_single.py --native-index-ab [--steps 20]     # LidarSeg steps, native index build off / on, alternating windows
        python tools/bench_single.py --native-train-ab [--steps 20] [--ab-model LidarSeg|middle]   # the same for the training executor
        python tools/bench_single.py --native-train-steps on|off --steps N     # N untimed batch-1 steps, to count launches under a kernel trace
+       python tools/bench_single.py --lidar-split [--steps 20] [--out profiles/spconv_split_steps.json]   # LidarSeg steps, default against lidar_split
 
 * Steps: TrainStep on synthetic KITTI-shaped frames (data/synth.make_batch), two alternating resident batches as bench.py
   uses, batch 4 and batch 1, HIP events around the timed loop after the warm-up, profiler off.  LidarSeg runs with the index
@@ -188,6 +189,12 @@ def native_train_ab(batch, steps, warmup, windows=5, model_kind="LidarSeg"):
     return _switch_ab("native_train", batch, steps, warmup, windows, model_kind)
 
 
+def lidar_split_ab(batch, steps, warmup, windows=5):
+    """LidarSeg step time with the default exact-fp32 sparse convolution and with SPVCNN.set_split (the three-piece split kernels): two
+    models from one seed in one process, `windows` windows of `steps` steps each, alternating."""
+    return _switch_ab("split", batch, steps, warmup, windows, "LidarSeg")
+
+
 def native_train_steps(mode, steps):
     """`steps` untimed LidarSeg steps at batch 1 with the training executor on / off: run under a kernel trace with two step counts, the
     difference of the two launch counts is the launches of the extra steps."""
@@ -284,6 +291,7 @@ def main():
     ap.add_argument("--native-train-ab", action="store_true", help="only: step time with SPVCNN.set_native_train off / on, batch 1 and 4")
     ap.add_argument("--ab-model", default="LidarSeg", choices=["LidarSeg", "middle"], help="the model of --native-train-ab")
     ap.add_argument("--native-train-steps", choices=["on", "off"], help="only: --steps untimed LidarSeg batch-1 steps with the switch on / off")
+    ap.add_argument("--lidar-split", action="store_true", help="only: LidarSeg step time with SPVCNN.set_split off / on, batch 4 and 1; --out writes the JSON")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_single: needs a GPU (there is no fallback)")
@@ -293,6 +301,21 @@ def main():
         return
     if args.native_train_steps:
         print(json.dumps(native_train_steps(args.native_train_steps, args.steps)), flush=True)
+        return
+    if args.lidar_split:
+        result = {"what": "LidarSeg train steps on synthetic KITTI-shaped frames (two alternating resident batches, HIP events, profiler off): the "
+                          "default exact-fp32 sparse convolution (off) against lidar_split (on), two models from one seed in one process, five "
+                          "windows each, alternating; median and min..max ms per step over the windows",
+                  "device": torch.cuda.get_device_name(0), "ab": []}
+        for batch in (4, 1):
+            r = lidar_split_ab(batch, args.steps, args.warmup)
+            print(json.dumps(r), flush=True)
+            result["ab"].append(r)
+        if args.out != ap.get_default("out"):
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+            print("wrote", args.out)
         return
     if args.native_index_ab:
         for batch in (1, 4):
