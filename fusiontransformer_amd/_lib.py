@@ -122,6 +122,9 @@ SIGNATURES = {
     "ftx_attn_bwd_tiled": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _i32, _i32, _vp]),
     "ftx_attn_fwd_bf16": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp]),
     "ftx_attn_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "ftx_attn_split_tiling_built": (_i32, [_i32, _i32, _i32]),
+    "ftx_attn_fwd_split": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp]),
+    "ftx_attn_bwd_split": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _i32, _i32, _vp]),
     "ftx_dense_gemm_bf16": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ftx_dense_wgrad_bf16_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ftx_dense_wgrad_bf16": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),

@@ -3,6 +3,7 @@
 // Flash-style: the T x T score matrix is never written.  Two precisions of the products, one set of kernel bodies:
 //   AttnF32   exact-fp32 MFMA (v_mfma_f32_32x32x2_f32)                          ftx_attn_fwd / ftx_attn_bwd [_tiled]
 //   AttnBf16  bf16 operands, fp32 accumulation (v_mfma_f32_32x32x16_bf16)       ftx_attn_fwd_bf16 / ftx_attn_bwd_bf16
+//   AttnSplit every operand in three bf16 pieces, six piece products, fp32-class ftx_attn_fwd_split / ftx_attn_bwd_split
 // A precision is an operand description (below): the lane fragment and its loader, the staging registers with prefetch and store, the
 // LDS images of a staged tile, the two products, and where scale * log2(e) enters.  The forward, dK/dV, dQ and delta bodies
 // (attn_*_body) are written once over that description and <QW, SPLIT>; the __global__ kernels are wrappers that keep their names, and
@@ -21,6 +22,7 @@
 // fragments are one ds_read_b128 / one 16-byte global load per 4 MFMAs.
 #include "ftx_common.h"
 #include "ftx_mfma.h"
+#include "ftx_split.h"   // split1: the ONE definition of the split
 
 using namespace ftx;
 
@@ -257,6 +259,197 @@ struct AttnBf16 {
       const __bf16 *p = colimg + (col_off + l31) * CS + 16 * s + 4 * h;
       out = mfma_bf16(__builtin_shufflevector(*(const bf16x4 *)p, *(const bf16x4 *)(p + 8), 0, 1, 2, 3, 4, 5, 6, 7), x.s[s], out);
     }
+  }
+};
+
+// =======================================================================================
+// fp32-accurate attention on the bf16 MFMA (ftx_attn_fwd_split / ftx_attn_bwd_split): the same bodies once more, every product from
+// three bf16 pieces per operand (ftx_split.h: x = h + m + l) and the six piece products of tests/split_ref.py.
+//
+// Precision contract (include/ftx.h states it for callers):
+//   storage   qkv, out, lse, grad_out and grad_qkv stay fp32 in HBM.
+//   operands  every MFMA operand is split by ftx::split1: Q, K, V, dO from their stored fp32 values (a staged tile when it is stored to
+//             LDS, a lane's own fragment when it is loaded), and the accumulator tiles P (forward, dK/dV) and dS (dK/dV, dQ) from their
+//             fp32 registers (operand).  Nothing is rounded to one bf16.
+//   products  a product is mm, hl, lh, hm, mh, hh (first letter: the staged tile's piece) on v_mfma_f32_32x32x16_bf16, per 16-wide
+//             k-step in that order.  Grouping: within one call of first / second the five corrections run in an accumulator of their
+//             own that starts at zero, hh runs in the caller's accumulator, and the corrections are added to it once at the end of the
+//             call -- once per 32 x 32 x 64 (first) or 32 x 32 x 32 (second) product, i.e. once per staged tile.
+//   scale     scale * log2(e) multiplies the fp32 score (as in AttnBf16), it is not folded into an operand.
+//   dO        exact: P::dO(g) = g, so attn_delta_split_kernel is the fp32 delta kernel in arithmetic.
+//   softmax   running max, row sum, lse, rescale and the P rebuilt from lse are fp32, as in the other families.
+//   order     no atomics; merge_sum's fixed tree: deterministic for a given tiling.
+//
+// LDS: the bf16 family's two images per staged tile (row image, col image: see AttnBf16), three times -- one per piece -- split once
+// when the tile is stored, so the QW waves of a block share the split's VALU work as they share the tile (one fp32 image split at
+// fragment-read time was built first: every wave then splits every tile it reads, and at (4,2) the kernels only matched the fp32
+// family's time).  The images' layout and the fragment order are AttnBf16's; the staging is the family's own (prefetch_rows below).  A
+// key group costs 27 KB in the forward, 55 KB in dK/dV and
+// 41 KB in dQ, so on a 160 KB CU the forward fits every tiling but (1,8) and the backward those with two groups: built() below.  The
+// lane's own fragments are split once, when loaded, and held as pieces in registers (48 VGPRs each).
+// =======================================================================================
+struct Pieces8 { bf16x8 h, m, l; };
+struct Pieces4 { bf16x4 h, m, l; };
+__device__ inline void split8(const float (&v)[8], Pieces8 &p) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    __bf16 h, m, l;
+    split1(v[j], h, m, l);
+    p.h[j] = h; p.m[j] = m; p.l[j] = l;
+  }
+}
+__device__ inline Pieces4 split4(float a, float b, float c, float d) {
+  const float v[4] = {a, b, c, d};
+  Pieces4 p;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    __bf16 h, m, l;
+    split1(v[j], h, m, l);
+    p.h[j] = h; p.m[j] = m; p.l[j] = l;
+  }
+  return p;
+}
+// one k-step of a product: the five corrections, smallest first, into `corr`, hh into `main`.  a = the staged tile's pieces
+__device__ inline void six_products(const Pieces8 &a, const Pieces8 &b, f32x16 &corr, f32x16 &main) {
+  corr = mfma_bf16(a.m, b.m, corr);
+  corr = mfma_bf16(a.h, b.l, corr);
+  corr = mfma_bf16(a.l, b.h, corr);
+  corr = mfma_bf16(a.h, b.m, corr);
+  corr = mfma_bf16(a.m, b.h, corr);
+  main = mfma_bf16(a.h, b.h, main);
+}
+
+struct AttnSplit : AttnBf16 {
+  using Frag = Pieces8[4];
+  struct X { Pieces8 s[2]; };
+  // the row images of h, m, l, then the col images of h, m, l, of those the tile's products read
+  static constexpr int tile_floats(bool row, bool col) { return 3 * (row + col) * IMG / 2; }
+  // What fits a 160 KB CU (LDS of a block: forward 27 KB x SPLIT, dK/dV 55 KB x SPLIT, dQ 41 KB x SPLIT); the kernels of the other
+  // tilings are empty and never launched.
+  static constexpr bool built(int qw, int split, bool backward) { return backward ? split == 2 : split <= 4; }
+
+  // The lane's fragment of a 64-float global row, split: f[s] piece [j] = piece of row[16s + 8h + j].
+  __device__ static void load_frag(const float *row, int h, bool valid, Frag &f) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+      if (valid) {
+        a = *(const float4 *)(row + 16 * s + 8 * h);
+        b = *(const float4 *)(row + 16 * s + 8 * h + 4);
+      }
+      const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      split8(v, f[s]);
+    }
+  }
+  __device__ static void fold(Frag &, float) {}
+  __device__ static float dO(float g) { return g; }
+
+  // Staging in units of TOK tokens x 4 floats, 16 units across a token row: 4 x 4 micro-blocks as AttnBf16 up to 128 threads, 2 x 4 with
+  // 256, so that every thread of the group stages -- and splits -- its share (with micro-blocks half of them would do it all) and a
+  // lane holds 2 float4 per tile in flight, not 4.
+  template <int NT> static constexpr int tok() { return NT > 128 ? 2 : 4; }
+  template <int NT> static constexpr int units() { return (32 / tok<NT>()) * 16 / NT; }
+  template <int NT> using Stage = float4[tok<NT>() * units<NT>()];
+  template <int NT>
+  __device__ static void prefetch(const float *qkv, int b, int hd, int which, int t0, int T, int nh, int tid, Stage<NT> &r) {
+    prefetch_rows<NT>(qkv_row(qkv, b, 0, which, hd, T, nh), 3 * nh * HD, t0, T, tid, r);
+  }
+  template <int NT>
+  __device__ static void prefetch_o(const float *o, int b, int hd, int t0, int T, int nh, int tid, Stage<NT> &r) {
+    prefetch_rows<NT>(o + ((int64_t)b * T * nh + hd) * HD, nh * HD, t0, T, tid, r);
+  }
+  template <int NT>
+  __device__ static void prefetch_rows(const float *src, int64_t rstride, int t0, int T, int tid, Stage<NT> &r) {
+    constexpr int TOK = tok<NT>();
+#pragma unroll
+    for (int q = 0; q < units<NT>(); ++q) {
+      const int e = q * NT + tid, tq = e >> 4, c4 = (e & 15) * 4;
+#pragma unroll
+      for (int i = 0; i < TOK; ++i) {
+        const int t = t0 + TOK * tq + i;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < T) v = *(const float4 *)(src + t * rstride + c4);
+        r[TOK * q + i] = v;
+      }
+    }
+  }
+  // the ONE place a staged tile is split: each unit once, its pieces written to the row and / or col images
+  template <int NT, bool ROW, bool COL>
+  __device__ static void store(float *tile, int tid, const Stage<NT> &r) {
+    constexpr int TOK = tok<NT>();
+    __bf16 *rowimg = (__bf16 *)tile, *colimg = rowimg + (ROW ? 3 * IMG : 0);
+#pragma unroll
+    for (int q = 0; q < units<NT>(); ++q) {
+      const int e = q * NT + tid, tq = e >> 4, c4 = (e & 15) * 4;
+      Pieces4 p[TOK];   // p[i]: token TOK tq + i, columns c4 .. c4 + 3
+#pragma unroll
+      for (int i = 0; i < TOK; ++i) p[i] = split4(r[TOK * q + i].x, r[TOK * q + i].y, r[TOK * q + i].z, r[TOK * q + i].w);
+      if (ROW) {
+#pragma unroll
+        for (int i = 0; i < TOK; ++i) {
+          __bf16 *d = rowimg + (TOK * tq + i) * RS + c4;
+          *(bf16x4 *)d = p[i].h;
+          *(bf16x4 *)(d + IMG) = p[i].m;
+          *(bf16x4 *)(d + 2 * IMG) = p[i].l;
+        }
+      }
+      if (COL) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          __bf16 *d = colimg + (c4 + c) * CS + TOK * tq;
+          if constexpr (TOK == 4) {
+            *(bf16x4 *)d = (bf16x4){p[0].h[c], p[1].h[c], p[2].h[c], p[3].h[c]};
+            *(bf16x4 *)(d + IMG) = (bf16x4){p[0].m[c], p[1].m[c], p[2].m[c], p[3].m[c]};
+            *(bf16x4 *)(d + 2 * IMG) = (bf16x4){p[0].l[c], p[1].l[c], p[2].l[c], p[3].l[c]};
+          } else {
+            *(bf16x2 *)d = (bf16x2){p[0].h[c], p[1].h[c]};
+            *(bf16x2 *)(d + IMG) = (bf16x2){p[0].m[c], p[1].m[c]};
+            *(bf16x2 *)(d + 2 * IMG) = (bf16x2){p[0].l[c], p[1].l[c]};
+          }
+        }
+      }
+    }
+  }
+  __device__ static void first(const float *tile, int l31, int h, const Frag &frag, f32x16 &acc) {
+    const __bf16 *rp = (const __bf16 *)tile + l31 * RS + 8 * h;
+    f32x16 corr;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) corr[g] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const Pieces8 t = {*(const bf16x8 *)(rp + 16 * s), *(const bf16x8 *)(rp + 16 * s + IMG), *(const bf16x8 *)(rp + 16 * s + 2 * IMG)};
+      six_products(t, frag[s], corr, acc);
+    }
+    acc += corr;
+  }
+  // an accumulator tile as a B operand: k-step s = registers 8s..8s+7, split here, and only here
+  __device__ static X operand(const f32x16 &x) {
+    X r;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = x[8 * s + j];
+      split8(v, r.s[s]);
+    }
+    return r;
+  }
+  template <bool ROW>
+  __device__ static void second(const float *tile, int col_off, int l31, int h, const X &x, f32x16 &out) {
+    const __bf16 *cp = (const __bf16 *)tile + (ROW ? 3 * IMG : 0) + (col_off + l31) * CS + 4 * h;
+    f32x16 corr;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) corr[g] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      Pieces8 t;
+      const __bf16 *p = cp + 16 * s;
+      t.h = __builtin_shufflevector(*(const bf16x4 *)p, *(const bf16x4 *)(p + 8), 0, 1, 2, 3, 4, 5, 6, 7);
+      t.m = __builtin_shufflevector(*(const bf16x4 *)(p + IMG), *(const bf16x4 *)(p + IMG + 8), 0, 1, 2, 3, 4, 5, 6, 7);
+      t.l = __builtin_shufflevector(*(const bf16x4 *)(p + 2 * IMG), *(const bf16x4 *)(p + 2 * IMG + 8), 0, 1, 2, 3, 4, 5, 6, 7);
+      six_products(t, x.s[s], corr, out);
+    }
+    out += corr;
   }
 };
 
@@ -662,6 +855,24 @@ __global__ __launch_bounds__(64 * QW * SPLIT) void attn_bwd_q_bf16_kernel(const 
 __global__ void attn_delta_bf16_kernel(const float *__restrict__ o, const float *__restrict__ go, int64_t rows, int T, int nh, float *__restrict__ delta) {
   attn_delta_body<AttnBf16>(o, go, rows, T, nh, delta);
 }
+template <int QW, int SPLIT>
+__global__ __launch_bounds__(64 * QW * SPLIT) void attn_fwd_split_kernel(const float *__restrict__ qkv, int T, int nh, float scale, float *__restrict__ out,
+    float *__restrict__ lse) {
+  if constexpr (AttnSplit::built(QW, SPLIT, false)) attn_fwd_body<AttnSplit, QW, SPLIT>(qkv, T, nh, scale, out, lse);
+}
+template <int QW, int SPLIT>
+__global__ __launch_bounds__(64 * QW * SPLIT) void attn_bwd_kv_split_kernel(const float *__restrict__ qkv, const float *__restrict__ go,
+    const float *__restrict__ lse, const float *__restrict__ delta, int T, int nh, float scale, float *__restrict__ gqkv) {
+  if constexpr (AttnSplit::built(QW, SPLIT, true)) attn_bwd_kv_body<AttnSplit, QW, SPLIT>(qkv, go, lse, delta, T, nh, scale, gqkv);
+}
+template <int QW, int SPLIT>
+__global__ __launch_bounds__(64 * QW * SPLIT) void attn_bwd_q_split_kernel(const float *__restrict__ qkv, const float *__restrict__ go,
+    const float *__restrict__ lse, const float *__restrict__ delta, int T, int nh, float scale, float *__restrict__ gqkv) {
+  if constexpr (AttnSplit::built(QW, SPLIT, true)) attn_bwd_q_body<AttnSplit, QW, SPLIT>(qkv, go, lse, delta, T, nh, scale, gqkv);
+}
+__global__ void attn_delta_split_kernel(const float *__restrict__ o, const float *__restrict__ go, int64_t rows, int T, int nh, float *__restrict__ delta) {
+  attn_delta_body<AttnSplit>(o, go, rows, T, nh, delta);
+}
 
 // ---------------------------------------------------------------------------------------
 // host: a family = the entry names that front its messages, its three kernels and its delta kernel
@@ -672,6 +883,8 @@ struct AttnF32Family {
   template <int QW, int SPLIT> static constexpr auto bwd_kv = attn_bwd_kv_kernel<QW, SPLIT>;
   template <int QW, int SPLIT> static constexpr auto bwd_q = attn_bwd_q_kernel<QW, SPLIT>;
   static constexpr auto delta = attn_delta_kernel;
+  static bool built(int qw, int split, bool backward);
+  static void config(int b, int t, int h, bool backward, int &qw, int &split);
 };
 struct AttnBf16Family {
   static constexpr const char *fwd_name = "ftx_attn_fwd_bf16", *bwd_name = "ftx_attn_bwd_bf16", *tiled = "";
@@ -679,6 +892,17 @@ struct AttnBf16Family {
   template <int QW, int SPLIT> static constexpr auto bwd_kv = attn_bwd_kv_bf16_kernel<QW, SPLIT>;
   template <int QW, int SPLIT> static constexpr auto bwd_q = attn_bwd_q_bf16_kernel<QW, SPLIT>;
   static constexpr auto delta = attn_delta_bf16_kernel;
+  static bool built(int qw, int split, bool backward);
+  static void config(int b, int t, int h, bool backward, int &qw, int &split);
+};
+struct AttnSplitFamily {
+  static constexpr const char *fwd_name = "ftx_attn_fwd_split", *bwd_name = "ftx_attn_bwd_split", *tiled = "";
+  template <int QW, int SPLIT> static constexpr auto fwd = attn_fwd_split_kernel<QW, SPLIT>;
+  template <int QW, int SPLIT> static constexpr auto bwd_kv = attn_bwd_kv_split_kernel<QW, SPLIT>;
+  template <int QW, int SPLIT> static constexpr auto bwd_q = attn_bwd_q_split_kernel<QW, SPLIT>;
+  static constexpr auto delta = attn_delta_split_kernel;
+  static bool built(int qw, int split, bool backward);
+  static void config(int b, int t, int h, bool backward, int &qw, int &split);
 };
 
 static int attn_check(const char *who, int b, int t, int h, int d) {
@@ -707,6 +931,32 @@ static void attn_config(int b, int t, int h, bool backward, int &qw, int &split)
   else { qw = 4; split = 2; }
 }
 
+bool AttnF32Family::built(int qw, int split, bool) { return attn_tiling_built(qw, split); }
+bool AttnBf16Family::built(int qw, int split, bool) { return attn_tiling_built(qw, split); }
+void AttnF32Family::config(int b, int t, int h, bool backward, int &qw, int &split) { attn_config(b, t, h, backward, qw, split); }
+void AttnBf16Family::config(int b, int t, int h, bool backward, int &qw, int &split) { attn_config(b, t, h, backward, qw, split); }
+
+// The split family's own set and choice: the tilings whose blocks fit the LDS (AttnSplit::built).  Forward: attn_config's thresholds
+// with the nearest built tiling -- one wave per group up to a quarter of the SIMDs, two up to half, four above.  Backward: (2,2) at every
+// size.  (4,2) is built and is the faster backward from batch 4 up at 578 tokens x 12 heads (154 us against 184), but
+// its dK/dV kernel keeps 80 bytes of scratch per lane (two fragments in pieces, four gradient tiles and two split accumulator tiles
+// are 256 registers before anything else), and the automatic choice keeps to kernels without scratch; (1,2) runs one block of two
+// waves per CU (111 KB of LDS) and loses to (2,2) at every size measured.
+bool AttnSplitFamily::built(int qw, int split, bool backward) {
+  return attn_tiling_built(qw, split) && ((qw == 0 && split == 0) || AttnSplit::built(qw, split, backward));
+}
+void AttnSplitFamily::config(int b, int t, int h, bool backward, int &qw, int &split) {
+  if (qw != 0) return;   // explicit
+  if (backward) { qw = 2; split = 2; return; }
+  const int64_t wave_tiles = (int64_t)ceil_div(t, 32) * h * b;
+  const int64_t simds = 4 * 256;
+  qw = wave_tiles * 4 <= simds ? 1 : wave_tiles * 2 <= simds ? 2 : 4;
+  split = qw == 4 ? 2 : 4;
+}
+extern "C" int32_t ftx_attn_split_tiling_built(int32_t qw, int32_t split, int32_t backward) {
+  return (qw != 0 || split != 0) && AttnSplitFamily::built(qw, split, backward != 0);
+}
+
 #define ATTN_DISPATCH(KERNEL, ...)                                                                               \
   do {                                                                                                           \
     dim3 grid((unsigned)ceil_div(t, 32 * qw), (unsigned)h, (unsigned)b);                                         \
@@ -725,9 +975,9 @@ static int attn_fwd_entry(const float *qkv, int32_t b, int32_t t, int32_t h, int
   int rc = attn_check(me, b, t, h, d);
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE(qkv && out && lse, "%s: null pointer", me);
-  FTX_REQUIRE(attn_tiling_built(qw, split), "%s%s: (%d, %d) is not a built tiling", me, F::tiled, qw, split);
+  FTX_REQUIRE(F::built(qw, split, false), "%s%s: (%d, %d) is not a built tiling", me, F::tiled, qw, split);
   hipStream_t st = (hipStream_t)stream;
-  attn_config(b, t, h, false, qw, split);
+  F::config(b, t, h, false, qw, split);
   ATTN_DISPATCH(F::template fwd, qkv, t, h, scale, out, lse);
   return check_launch(me);
 }
@@ -744,13 +994,13 @@ static int attn_bwd_entry(const float *qkv, const float *out, const float *grad_
   int rc = attn_check(me, b, t, h, d);
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE(qkv && out && grad_out && lse && grad_qkv && workspace, "%s: null pointer", me);
-  FTX_REQUIRE(attn_tiling_built(qw, split), "%s%s: (%d, %d) is not a built tiling", me, F::tiled, qw, split);
+  FTX_REQUIRE(F::built(qw, split, true), "%s%s: (%d, %d) is not a built tiling", me, F::tiled, qw, split);
   if (workspace_bytes < ftx_attn_bwd_workspace_bytes(b, t, h)) return workspace_short(me, workspace_bytes, ftx_attn_bwd_workspace_bytes(b, t, h));
   hipStream_t st = (hipStream_t)stream;
   float *delta = (float *)workspace;
   const int64_t rows = (int64_t)b * t * h;
   F::delta<<<(unsigned)ceil_div(rows * 16, 256), 256, 0, st>>>(out, grad_out, rows, t, h, delta);
-  attn_config(b, t, h, true, qw, split);
+  F::config(b, t, h, true, qw, split);
   ATTN_DISPATCH(F::template bwd_kv, qkv, grad_out, lse, delta, t, h, scale, grad_qkv);
   ATTN_DISPATCH(F::template bwd_q, qkv, grad_out, lse, delta, t, h, scale, grad_qkv);
   return check_launch(me);
@@ -780,4 +1030,13 @@ extern "C" int ftx_attn_bwd_bf16(const float *qkv, const float *out, const float
                                  int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split,
                                  void *stream) {
   return attn_bwd_entry<AttnBf16Family>(qkv, out, grad_out, lse, b, t, h, d, scale, grad_qkv, workspace, workspace_bytes, qw, split, stream);
+}
+extern "C" int ftx_attn_fwd_split(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw,
+                                  int32_t split, void *stream) {
+  return attn_fwd_entry<AttnSplitFamily>(qkv, b, t, h, d, scale, out, lse, qw, split, stream);
+}
+extern "C" int ftx_attn_bwd_split(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h,
+                                  int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split,
+                                  void *stream) {
+  return attn_bwd_entry<AttnSplitFamily>(qkv, out, grad_out, lse, b, t, h, d, scale, grad_qkv, workspace, workspace_bytes, qw, split, stream);
 }

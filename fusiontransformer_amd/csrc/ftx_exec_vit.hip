@@ -131,7 +131,7 @@ extern "C" int ftx_vit_eval(const void *model_host, const void *blocks_host, int
   FTX_REQUIRE(block_first >= 0 && block_first <= block_last && block_last < n_blocks, "%s: blocks [%d, %d] outside 0..%d", who, block_first, block_last,
               n_blocks - 1);
   FTX_REQUIRE(linear_mode == 0 || linear_mode == 1, "%s: linear_mode must be 0 (split) or 1 (bf16)", who);
-  FTX_REQUIRE(attn_mode == 0 || attn_mode == 1, "%s: attn_mode must be 0 (fp32) or 1 (bf16)", who);
+  FTX_REQUIRE(attn_mode >= 0 && attn_mode <= 2, "%s: attn_mode must be 0 (fp32), 1 (bf16) or 2 (split)", who);
   FTX_REQUIRE(n_taps >= 0 && n_taps <= kMaxBlocks && (taps || !n_taps) && (tap_out_host || !n_taps), "%s: null tap table or tap count outside [0, %d]", who,
               kMaxBlocks);
   for (int i = 0; i < n_taps; ++i) {
@@ -227,7 +227,8 @@ extern "C" int ftx_vit_eval(const void *model_host, const void *blocks_host, int
       RUN("norm1", ftx_add_layernorm_fwd(r, nullptr, nullptr, B.norm1_w, B.norm1_b, M.eps, rows, dim, nullptr, h, mean, rstd, stream));
     }
     RUN("qkv", gemm(h, B.qkv_w, 0, B.qkv_b, nullptr, rows, 3 * dim, dim, FTX_EPI_BIAS, qkv, nullptr, stream));
-    if (attn_mode) RUN("attention", ftx_attn_fwd_bf16(qkv, b, T, M.heads, 64, 0.125f, att, lse, 0, 0, stream));
+    if (attn_mode == 2) RUN("attention", ftx_attn_fwd_split(qkv, b, T, M.heads, 64, 0.125f, att, lse, 0, 0, stream));
+    else if (attn_mode == 1) RUN("attention", ftx_attn_fwd_bf16(qkv, b, T, M.heads, 64, 0.125f, att, lse, 0, 0, stream));
     else RUN("attention", ftx_attn_fwd_tiled(qkv, b, T, M.heads, 64, 0.125f, att, lse, 0, 0, stream));
     RUN("proj", gemm(att, B.proj_w, 0, nullptr, nullptr, rows, dim, dim, FTX_EPI_NONE, proj, nullptr, stream));
     float *s2 = at(P.r[s == at(P.r[0]) ? 1 : 0]);

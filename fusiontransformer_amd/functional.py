@@ -1547,9 +1547,10 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------- ViT self-attention
-# (forward entry, its launch-log kind, backward entry, its kind) per precision
-_ATTENTION = {False: ("ftx_attn_fwd_tiled", "attn_fwd", "ftx_attn_bwd_tiled", "attn_bwd"),
-              True: ("ftx_attn_fwd_bf16", "attn_fwd_bf16", "ftx_attn_bwd_bf16", "attn_bwd_bf16")}
+# (forward entry, its launch-log kind, backward entry, its kind) per operand mode (FP32 == False and BF16 == True, as ever)
+_ATTENTION = {FP32: ("ftx_attn_fwd_tiled", "attn_fwd", "ftx_attn_bwd_tiled", "attn_bwd"),
+              BF16: ("ftx_attn_fwd_bf16", "attn_fwd_bf16", "ftx_attn_bwd_bf16", "attn_bwd_bf16"),
+              SPLIT: ("ftx_attn_fwd_split", "attn_fwd_split", "ftx_attn_bwd_split", "attn_bwd_split")}
 
 
 class _Attention(torch.autograd.Function):
@@ -1585,12 +1586,15 @@ class _Attention(torch.autograd.Function):
         return gqkv, None, None, None
 
 
-def attention(qkv, scale, tiling=(0, 0), bf16=False):
+def attention(qkv, scale, tiling=(0, 0), bf16=False, operands=None):
     """softmax(Q K^T * scale) V for qkv (B, T, 3, heads, 64) -> (B, T, heads*64).  `tiling` = (waves per block, key groups) of the
     kernels, (0, 0) = chosen per launch (ftx_attn_fwd_tiled in include/ftx.h): a per-call argument for tests and tools.
     bf16=True: the bf16-operand kernels (ftx_attn_fwd_bf16 / ftx_attn_bwd_bf16: Q, K, V, dO, P and dS rounded to bf16 as MFMA
-    operands, fp32 accumulation, softmax statistics and storage; the contract is stated in include/ftx.h)."""
-    return _Attention.apply(qkv, scale, tiling, bool(bf16))
+    operands, fp32 accumulation, softmax statistics and storage; the contract is stated in include/ftx.h).
+    operands="split": the fp32-accurate kernels on the bf16 MFMA (ftx_attn_fwd_split / ftx_attn_bwd_split: every MFMA operand in three
+    bf16 pieces, six piece products; contract in include/ftx.h); its tilings are those ftx_attn_split_tiling_built reports.  `bf16`,
+    `operands` name the mode as for the sparse ops (operand_mode): bf16=True next to operands="split" is refused."""
+    return _Attention.apply(qkv, scale, tiling, operand_mode(bf16, operands))
 
 
 # ---------------------------------------------------------------- bf16-operand ViT Linears

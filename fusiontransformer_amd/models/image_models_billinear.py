@@ -164,7 +164,7 @@ class Net2DBillinear(nn.Module):
         eval mode, with gradients disabled, on the GPU and with fp32 parameters runs sample_down as before and then the patch embedding,
         the live blocks and the tap stems as one library call per trunk segment (up to the middle tap, up to the late tap) over an arena
         this module owns; the lift and the heads stay where they are.  It engages only when every live block runs the linears the library
-        owns (vit_linear_impl "ftx_split", or "ftx" with set_bf16) and one attention impl ("ftx" or "ftx_bf16"); anything else -- training
+        owns (vit_linear_impl "ftx_split", or "ftx" with set_bf16) and one attention impl ("ftx", "ftx_bf16" or "ftx_split"); anything else -- training
         mode, gradients, CPU tensors, vit_linear_impl="library" -- takes the existing path exactly as with the switch off, and
         native_eval_reason() says why."""
         self.image_native_eval = bool(on)

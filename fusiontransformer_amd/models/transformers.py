@@ -8,8 +8,9 @@ restated here with the same attribute names, so DeiT checkpoints keyed
 
 The dense contractions (patch-embed conv, qkv / proj / MLP linears) go through
 torch's hipBLASLt GEMMs; softmax(QK^T/8)V runs in libftx's fused attention
-kernel when `attn_impl == "ftx"` (exact fp32) or `"ftx_bf16"` (bf16 operands, fp32 accumulation and softmax:
-functional.attention(bf16=True)), otherwise as the three explicit ops timm uses.
+kernel when `attn_impl == "ftx"` (exact fp32), `"ftx_bf16"` (bf16 operands, fp32 accumulation and softmax:
+functional.attention(bf16=True)) or `"ftx_split"` (fp32-accurate on the bf16 MFMA: every operand in three bf16 pieces,
+functional.attention(operands="split")), otherwise as the three explicit ops timm uses.
 
 `SpatialTransformer` / `ScaleUpModule` (reference models/transformers.py:102-156) are at the end of the file: learned affine
 resampling on libftx's affine-sampling kernels (functional.affine_sample / affine_lift)."""
@@ -167,6 +168,11 @@ class Mlp(nn.Module):
                 and self.fc1.bias is not None and self.fc2.bias is not None)
 
 
+# attn_impl values that run libftx's fused attention kernels, and the operand mode of functional.attention each one names; any other
+# value ("torch") is the three explicit ops
+ATTN_OPERANDS = {"ftx": "fp32", "ftx_bf16": "bf16", "ftx_split": "split"}
+
+
 class Attention(nn.Module):
     def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0.0, proj_drop=0.0):
         super().__init__()
@@ -182,9 +188,9 @@ class Attention(nn.Module):
     def forward(self, x, with_proj_bias=True):
         B, N, C = x.shape
         qkv = _linear(x, self.qkv)
-        if self.attn_impl in ("ftx", "ftx_bf16"):
+        if self.attn_impl in ATTN_OPERANDS:
             from .. import functional as spf
-            x = spf.attention(qkv.view(B, N, 3, self.num_heads, C // self.num_heads), self.scale, bf16=self.attn_impl == "ftx_bf16")
+            x = spf.attention(qkv.view(B, N, 3, self.num_heads, C // self.num_heads), self.scale, operands=ATTN_OPERANDS[self.attn_impl])
         else:
             qkv = qkv.reshape(B, N, 3, self.num_heads, C // self.num_heads).permute(2, 0, 3, 1, 4)
             q, k, v = qkv[0], qkv[1], qkv[2]
@@ -341,6 +347,7 @@ class Image2DTransformer(nn.Module):
                 lin.ftx_linear_impl = impl
 
     def set_attention_impl(self, impl: str):
+        """attn_impl of every block: "ftx" (exact fp32 MFMA, the default), "ftx_bf16", "ftx_split" (ATTN_OPERANDS) or the explicit ops."""
         for blk in self.blocks:
             blk.attn.attn_impl = impl
 

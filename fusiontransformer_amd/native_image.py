@@ -23,7 +23,8 @@ BLOCK = np.dtype([(n, _P) for n in BLOCK_FIELDS])
 TAP = np.dtype([("stem_w", _P), ("stem_b", _P), ("gamma", _P), ("beta", _P), ("mean", _P), ("var", _P), ("block", "<i4"), ("co", "<i4"),
                 ("eps", "<f4"), ("reserved", "<i4")])
 LINEAR_SPLIT, LINEAR_BF16 = 0, 1
-ATTN_FP32, ATTN_BF16 = 0, 1
+ATTN_FP32, ATTN_BF16, ATTN_SPLIT = 0, 1, 2
+_ATTN_MODE = {"ftx": ATTN_FP32, "ftx_bf16": ATTN_BF16, "ftx_split": ATTN_SPLIT}
 _LINEAR_MODE = {OWN_SPLIT: LINEAR_SPLIT, OWN_BF16: LINEAR_BF16}      # of the routes the executor runs (transformers.linear_route)
 
 _vp = ctypes.c_void_p
@@ -71,9 +72,9 @@ def modes(net):
         att.add(blk.attn.attn_impl)
     if len(lin) != 1:
         raise Unsupported("the blocks do not share one linear mode")
-    if len(att) != 1 or next(iter(att)) not in ("ftx", "ftx_bf16"):
-        raise Unsupported("attn_impl %s: the executor runs 'ftx' or 'ftx_bf16' on every block" % sorted(att))
-    return lin.pop(), (ATTN_BF16 if att.pop() == "ftx_bf16" else ATTN_FP32)
+    if len(att) != 1 or next(iter(att)) not in _ATTN_MODE:
+        raise Unsupported("attn_impl %s: the executor runs 'ftx', 'ftx_bf16' or 'ftx_split' on every block" % sorted(att))
+    return lin.pop(), _ATTN_MODE[att.pop()]
 
 
 def _taps_of(net):

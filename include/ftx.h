@@ -431,6 +431,24 @@ int ftx_attn_bwd_tiled(const float *qkv, const float *out, const float *grad_out
  * ((0, 0) = chosen per launch; built (4,2) (2,2) (2,4) (1,2) (1,4) (1,8); anything else refused).  workspace: ftx_attn_bwd_workspace_bytes. */
 int ftx_attn_fwd_bf16(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw, int32_t split, void *stream);
 int ftx_attn_bwd_bf16(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split, void *stream);
+/* fp32-accurate attention on the bf16 MFMA: the same calls once more (models/transformers.py attn_impl "ftx_split").
+ * Precision contract.  Storage stays fp32: qkv, out, lse, grad_out, grad_qkv as above.  Every MFMA operand is split into three bf16
+ * pieces, x = h + m + l with h = bf16(x), m = bf16(x - h), l = bf16((x - h) - m) (round-to-nearest-even, the subtractions in fp32): Q, K,
+ * V and dO from their stored values, and the accumulator tiles that are operands -- P in the forward and the dK / dV pass, dS in the dK /
+ * dV and dQ passes -- from their fp32 registers; nothing is rounded to a single bf16.  Every product is the six piece products mm, hl, lh,
+ * hm, mh, hh (first letter: the staged tile's piece) on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, in that order per 16-wide step of
+ * the reduction.  Grouping: per product of one staged 32-token tile (32 x 32 x 64 for the scores and dP, 32 x 32 x 32 for P.V, dV, dK and dQ)
+ * the five corrections run in an accumulator of their own that starts at zero, hh runs in the product's accumulator, and the corrections
+ * are added to it once when that tile's product ends.  scale * log2(e) multiplies the fp32 score; it is not folded into an operand.  dO is
+ * exact everywhere: delta = rowsum(dO * O) in fp32, the fp32 kernels' delta.  Softmax max, row sum, lse, rescale and the P rebuilt from lse
+ * are fp32, as in the other two families.  No atomics: deterministic for a given tiling.  Meets the bars of the fp32 kernels
+ * (tests/attn_ref.py); the terms it leaves out (ll, ml, lm) are below 2^-24 of a product.
+ * Tilings: (0, 0) = chosen per launch by the family's own rule; ftx_attn_split_tiling_built(qw, split, backward) != 0 says whether an
+ * explicit (qw, split) is built for the forward (backward == 0) or the backward (the set is a subset of the six of ftx_attn_fwd_tiled and
+ * holds (4,2)); anything else is refused.  workspace: ftx_attn_bwd_workspace_bytes. */
+int32_t ftx_attn_split_tiling_built(int32_t qw, int32_t split, int32_t backward);
+int ftx_attn_fwd_split(const float *qkv, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *out, float *lse, int32_t qw, int32_t split, void *stream);
+int ftx_attn_bwd_split(const float *qkv, const float *out, const float *grad_out, const float *lse, int32_t b, int32_t t, int32_t h, int32_t d, float scale, float *grad_qkv, void *workspace, size_t workspace_bytes, int32_t qw, int32_t split, void *stream);
 
 /* ---- bf16-operand ViT Linears (timm Mlp / Attention qkv, proj, fc1, fc2: models/transformers.py:36-55) (csrc/ftx_dense_bf16.hip: the
  *      family's description and entries; the kernels, shared with the split entries below: csrc/ftx_dense_common.h) ----
@@ -785,7 +803,8 @@ int ftx_rows_add_bias(const float *r, const float *p, const float *pb, int64_t n
  * the first block, else the previous block's MLP output with fc2's bias as y_bias), the qkv GEMM with FTX_EPI_BIAS, attention (scale
  * 1/8), the proj GEMM with FTX_EPI_NONE, ftx_add_layernorm_fwd with y_bias = proj's bias, fc1 with FTX_EPI_BIAS_GELU, fc2 with
  * FTX_EPI_NONE.  linear_mode: 0 = ftx_dense_gemm_split, 1 = ftx_dense_gemm_bf16 (and the matching patch embedding and tap stem);
- * attn_mode: 0 = ftx_attn_fwd_tiled(..., 0, 0) (the automatic tiling, what ftx_attn_fwd runs), 1 = ftx_attn_fwd_bf16(..., 0, 0).  At a tap the stream r + (p + pb) becomes one tensor (ftx_rows_add_bias) and
+ * attn_mode: 0 = ftx_attn_fwd_tiled(..., 0, 0) (the automatic tiling, what ftx_attn_fwd runs), 1 = ftx_attn_fwd_bf16(..., 0, 0),
+ * 2 = ftx_attn_fwd_split(..., 0, 0); any other value is refused.  At a tap the stream r + (p + pb) becomes one tensor (ftx_rows_add_bias) and
  * ftx_vit_tap_stem_* writes tap_out_host[i]; both residual forms round in that order, so the results do not depend on where a caller
  * materialises.  Taps in front of block_first are skipped (an earlier call wrote them).
  * Refused before the first launch (FTX_EINVAL): heads * 64 != dim, dim outside {256, 512, 768, 1024}, hidden % 64 != 0, taps not
