@@ -62,11 +62,11 @@ def init_process_group(backend=None, force=False):
 
 
 class _Bucket:
-    __slots__ = ("params", "flat", "views", "work", "launched", "tail_seen", "hold", "events")
+    __slots__ = ("params", "flat", "views", "work", "launched", "tail_seen", "hold", "events", "complete")
 
     def __init__(self, params, flat, views):
         self.params, self.flat, self.views = params, flat, views
-        self.work, self.launched, self.tail_seen, self.hold, self.events = None, False, False, None, None
+        self.work, self.launched, self.tail_seen, self.hold, self.events, self.complete = None, False, False, None, None, False
 
 
 class GradReducer:
@@ -76,8 +76,14 @@ class GradReducer:
     accumulated on); nothing overlaps yet.  From step 1 on the buckets follow that order (rank 0's, broadcast) and only the LAST
     parameter of each bucket keeps a hook: ~330 Python hook calls per backward cost 2.5-3 ms per step on MI355X (measured with a
     one-rank RCCL communicator: 27.6 ms without a reducer, 30.2-31.6 ms with per-parameter hooks, the collectives themselves free).
-    When a bucket's tail arrives, every gradient of the bucket is checked for presence (p.grad was set to None at the start of the
-    step); a bucket that is not complete -- the order changed -- simply waits for a later tail or for finish()."""
+    When a bucket's tail arrives the bucket is MARKED: every gradient of it is checked for presence (p.grad was set to None at the
+    start of the step) and one event is recorded per known accumulating stream.  Three rules keep the exchange behind its gradients:
+    a bucket goes out early only behind a mark at which it was complete; a bucket that was incomplete at its tail -- the order
+    changed -- and every bucket sent from finish() is marked AGAIN immediately before the exchange stream waits, so the events lie
+    behind the late gradient's producer; every tail hook and finish() add their current stream to the known streams, so a stream
+    that starts accumulating gradients in a later step is covered from its first tail on.  A reducer that issues no collectives
+    (world size 1) packs nothing from a hook: it packs in finish(), on the caller's stream, which the autograd engine has joined
+    with every stream that accumulated a gradient."""
 
     def __init__(self, model, bucket_mb: float = 128.0, process_group=None, broadcast_params=True, force_collectives=False):
         """force_collectives: issue the broadcasts and all-reduces even at world size 1 (needs an initialised process group,
@@ -91,7 +97,7 @@ class GradReducer:
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.step_idx = 0
         self._comm = {}
-        self._streams = {}          # every stream a gradient was accumulated on (recorded in step 0)
+        self._streams = {}          # every stream a gradient was seen accumulated on (_note_stream: every hook, and finish())
         self.ready_order = []
         self._rebuilt = False
         self._record = False
@@ -102,9 +108,11 @@ class GradReducer:
                 dist.broadcast(t.data, src=0, group=self.pg)
         self._build(list(reversed(self.params)))
         self._handles = [p.register_post_accumulate_grad_hook(self._on_grad_ready) for p in self.params]
-        # The hooks keep the AccumulateGrad nodes (created on the default stream) alive while the model's
-        # branches run on their own streams; autograd then orders each accumulation after its producer
-        # stream, which is exactly what the exchange relies on.  The advisory warning about it is noise.
+        # Post-accumulate hooks do not keep AccumulateGrad nodes alive, so gradients are accumulated on the branch streams their
+        # producers ran on, not on the default stream, and nothing here may assume otherwise: the exchange orders itself behind
+        # the accumulating streams with its own events (_note_stream, _mark), and a reducer without collectives packs only after
+        # backward() has returned, when autograd has joined those streams with the caller's.  Where a node does outlive its
+        # iteration, autograd synchronises the two streams itself; its advisory warning about that adds nothing here.
         try:
             torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
         except AttributeError:
@@ -159,10 +167,12 @@ class GradReducer:
             self._rebuilt = True
             for h in self._handles:
                 h.remove()
-            # one hook per bucket, on the parameter whose gradient arrived last in step 0
-            self._handles = [b.params[-1].register_post_accumulate_grad_hook(lambda p, i=i: self._on_bucket_tail(i)) for i, b in enumerate(self.buckets)]
+            # one hook per bucket, on the parameter whose gradient arrived last in step 0; none when no collective is issued
+            # (everything is packed in finish() then)
+            self._handles = [b.params[-1].register_post_accumulate_grad_hook(lambda p, i=i: self._on_bucket_tail(i))
+                             for i, b in enumerate(self.buckets)] if self.active else []
         for b in self.buckets:
-            b.work, b.launched, b.tail_seen, b.hold, b.events = None, False, False, None, None
+            b.work, b.launched, b.tail_seen, b.hold, b.events, b.complete = None, False, False, None, None, False
         for p in self.params:
             p.grad = None    # autograd then MOVES each gradient into place (no add kernel per parameter); _launch packs the bucket
         self.next_to_launch = 0
@@ -203,28 +213,45 @@ class GradReducer:
             b.hold = src
         return True
 
+    def _note_stream(self, device):
+        """The current stream accumulates gradients (or, in finish(), has been joined with those that do): _mark covers it from now on."""
+        if device.type == "cuda":
+            st = torch.cuda.current_stream(device)
+            self._streams[st.cuda_stream] = st
+
     def _mark(self, b):
-        """One event per accumulating stream, recorded NOW: everything that produced this bucket's gradients has been issued."""
+        """Which gradients of the bucket are present, and one event per known accumulating stream, recorded NOW: everything that
+        produced the gradients present has been issued before those events.  Called on every device; only the events are CUDA's."""
+        b.complete = all(p.grad is not None for p in b.params)
         b.events = []
-        for st in self._streams.values():
-            ev = torch.cuda.Event()
-            ev.record(st)
-            b.events.append(ev)
+        if b.flat.is_cuda:
+            for st in self._streams.values():
+                ev = torch.cuda.Event()
+                ev.record(st)
+                b.events.append(ev)
 
     def _launch(self, b, early=False):
         """Everything here runs on the autograd thread when early=True, between two backward nodes: host time spent here delays the
         issue of the rest of the backward one to one (measured: 7 early launches of ~0.4 ms each cost MORE than not overlapping the
         exchange at all on one GPU), hence few, large buckets and nothing in this path that can wait for finish()."""
         if not self.active:
-            b.launched = self._pack(b, early)
+            # no collective, no exchange stream: only finish() comes here, on the caller's stream, which autograd has joined with
+            # every stream that accumulated a gradient when backward() returned
+            assert not early, "GradReducer: a reducer without collectives packs in finish() only"
+            b.launched = self._pack(b)
             return b.launched
+        # The mark made at the bucket's own tail serves only if the bucket was complete then (the usual case: its events are (nearly)
+        # reached by now, _on_bucket_tail).  A bucket that was incomplete at its tail has gradients produced AFTER that mark, and a
+        # bucket sent from finish() may never have been marked or may hold gradients of a stream joined only now: mark again.
+        if not early or not b.complete:
+            self._mark(b)
+            if early and not b.complete:
+                return False
         if b.flat.is_cuda:
             comm = self._comm_stream(b.flat.device)
             with torch.cuda.stream(comm):
-                # order the exchange after everything that had been queued on every gradient-accumulating stream when the bucket's
-                # tail arrived (_mark: one event per stream, nothing blocks compute)
-                if b.events is None:
-                    self._mark(b)
+                # order the exchange after everything that had been queued on every gradient-accumulating stream at the mark
+                # (one event per stream, nothing blocks compute)
                 for ev in b.events:
                     comm.wait_event(ev)
                 if not self._pack(b, early):
@@ -254,12 +281,11 @@ class GradReducer:
         """Step 0 (a hook on every parameter): learn the ready order and the accumulating streams; nothing is launched early."""
         if self._record:
             self.ready_order.append(p)
-        if p.is_cuda:
-            st = torch.cuda.current_stream()     # the stream that just accumulated this gradient
-            self._streams[st.cuda_stream] = st
+        self._note_stream(p.device)              # the stream that just accumulated this gradient
 
     def _on_bucket_tail(self, i):
-        """Bucket i is complete on the host side: mark it (events on the accumulating streams) and launch the buckets BEFORE it.
+        """Bucket i's last gradient (by the recorded order) has arrived on the current stream: mark it (which gradients are present,
+        events on the accumulating streams) and launch the buckets BEFORE it.
         One bucket of delay on purpose.  The host issues the backward several milliseconds ahead of the GPU, so a stream-side wait
         enqueued at a bucket's own tail stays pending for that long, and pending waits are expensive on this stack: +2.5 ms per step
         on one GPU with no byte moved, all of it gone when the waits are removed (why is not fully established: the exchange stream
@@ -269,8 +295,8 @@ class GradReducer:
         t0 = time.perf_counter()
         b = self.buckets[i]
         b.tail_seen = True
-        if b.flat.is_cuda and self.active:
-            self._mark(b)
+        self._note_stream(b.flat.device)
+        self._mark(b)
         before = self.next_to_launch
         self._launch_ready_prefix(i)
         self.hook_stats["early_launches"] += self.next_to_launch - before
@@ -280,9 +306,8 @@ class GradReducer:
 
     def finish(self):
         """Call after backward: launches what has not gone out yet (in bucket order) and waits."""
-        if self.buckets and self.buckets[0].flat.is_cuda:
-            cur = torch.cuda.current_stream()
-            self._streams[cur.cuda_stream] = cur
+        if self.buckets:
+            self._note_stream(self.buckets[0].flat.device)
         for b in self.buckets:
             if not b.launched:
                 self._launch(b)

@@ -155,3 +155,175 @@ def test_bucket_waits_when_the_gradient_order_changes():
     assert p.exitcode == 0
     assert ok, "gradients changed when the ready order changed"
     assert rebuilt and nb == 4 and early >= 1 and deferred >= 1, (nb, early, deferred)
+
+
+# ---- the ordering contract of the exchange, stated without timing -------------------------------------------------------------------
+# Every pack of a bucket is preceded by a mark of that bucket made after the last of its gradients arrived, and that mark covers
+# every stream a gradient of the step was accumulated on; a pack issued from a hook (before finish()) needs a mark at which the bucket
+# was complete.  GradReducer marks (_mark), packs (_pack) and learns streams (_note_stream) through small methods called on every
+# device, so a subclass can log them on the CPU, with pretend streams.  tests/test_dist_order_gpu.py shows the same on the GPU.
+
+def _contract_worker(port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    from fusiontransformer_amd.dist import GradReducer, init_process_group
+    init_process_group("gloo", force=True)
+    torch.manual_seed(6)
+
+    class Logged(GradReducer):
+        log, now = None, "s0"                    # `now`: the pretend current stream
+
+        def _state(self, b):
+            return (self.buckets.index(b), tuple(p.grad is not None for p in b.params), frozenset(self._streams))
+
+        def _note_stream(self, device):
+            self._streams[self.now] = self.now
+
+        def _mark(self, b):
+            super()._mark(b)
+            self.log.append(("mark",) + self._state(b) + (b.complete,))
+
+        def _pack(self, b, early=False):
+            state = self._state(b)
+            done = super()._pack(b, early)
+            if done:
+                self.log.append(("pack",) + state)
+            return done
+
+        def finish(self):
+            self.log.append(("finish",))
+            super().finish()
+
+    def rig(pairs, **kw):
+        names = [k + str(i + 1) for i in range(pairs) for k in "ab"]
+        model = torch.nn.ModuleDict({n: torch.nn.Linear(6, 6, bias=False) for n in names})
+        twin = torch.nn.ModuleDict({n: torch.nn.Linear(6, 6, bias=False) for n in names})
+        twin.load_state_dict(model.state_dict())
+        log = []
+        for n in names:                           # registered before the reducer's hooks: an arrival is logged before the mark it causes
+            model[n].weight.register_post_accumulate_grad_hook(lambda p, n=n: log.append(("grad", n, red.now)))
+        red = Logged(model, bucket_mb=2 * 36 * 4 / 2 ** 20, **kw)     # two weights fill a bucket
+        red.log = log
+
+        def step(order, stream="s0"):
+            """-> (this step's log, bucket of every layer, names whose gradient differs from the twin's; a layer left out of
+            `order` must end with zeros)"""
+            del log[:]
+            red.now = stream
+            x = torch.randn(3, 6)
+            twin.zero_grad(set_to_none=True)
+            red.begin_step()
+            for n in order:
+                twin[n](x).pow(2).sum().backward()
+                model[n](x).pow(2).sum().backward()
+            red.now = "s0"                        # the caller's stream
+            red.finish()
+            want = {n: twin[n].weight.grad if n in order else torch.zeros(6, 6) for n in names}
+            bad = [n for n in names if model[n].weight.grad is None or not torch.equal(model[n].weight.grad, want[n])]
+            where = {n: i for i, b in enumerate(red.buckets) for n in names if any(model[n].weight is p for p in b.params)}
+            return list(log), where, bad
+        step(names)
+        step(names)
+        assert red._rebuilt and [len(b.params) for b in red.buckets] == [2] * pairs
+        return names, step
+
+    out = {}
+    names, step = rig(2, force_collectives=True)
+    out["unchanged"] = step(names)
+    out["flipped, sent from finish"] = step(["b1", "b2", "a1", "a2"])
+    out["new stream"] = step(names, stream="s1")
+    out["no gradient"] = step(["a1", "b1", "a2"])
+    names3, step3 = rig(3, force_collectives=True, broadcast_params=False)
+    out["flipped, sent from a later tail"] = step3(["b1", "a1", "a2", "b2", "a3", "b3"])
+    names1, step1 = rig(2)                        # no collectives: packs in finish() only
+    out["inactive"] = step1(names1)
+    out["inactive, no gradient"] = step1(["a1", "b1", "a2"])
+    q.put(out)
+    dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def contract_logs():
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_contract_worker, args=(_free_port(), q))
+    p.start()
+    out = q.get(timeout=120)
+    p.join(timeout=60)
+    assert p.exitcode == 0
+    return out
+
+
+def _assert_contract(log, where, bad, active=True):
+    """The contract, read off one step's log.  -> the buckets packed before finish(), in order."""
+    assert bad == [], "gradients differ from the twin's: %s" % bad
+    assert [e[0] for e in log].count("finish") == 1
+    early, arrived, streams, last_mark, in_finish, packed = [], set(), set(), {}, False, []
+    for e in log:
+        if e[0] == "grad":
+            arrived.add(e[1])
+            streams.add(e[2])
+        elif e[0] == "finish":
+            in_finish = True
+        elif e[0] == "mark":
+            last_mark[e[1]] = (e, set(arrived), in_finish)
+        else:
+            _, i, present, known = e
+            packed.append(i)
+            members = {n for n, k in where.items() if k == i}
+            assert sum(present) == len(members & arrived), (e, arrived)
+            if not in_finish:
+                early.append(i)
+            if not active:
+                assert in_finish, "a reducer without collectives packed bucket %d from a hook" % i
+                continue
+            assert i in last_mark, "bucket %d was packed without a mark" % i
+            (_, _, seen, covered, complete), arrived_then, marked_in_finish = last_mark[i]
+            assert members & arrived <= arrived_then, "bucket %d: %s arrived after the mark its pack waited for" % (i, sorted((members & arrived) - arrived_then))
+            assert seen == present and complete == all(present)
+            assert streams <= covered, "bucket %d: the mark does not cover stream(s) %s" % (i, sorted(streams - covered))
+            if in_finish:
+                assert marked_in_finish, "bucket %d went out from finish() behind a mark made earlier" % i
+            else:
+                assert complete, "bucket %d went out early behind a mark at which it was incomplete" % i
+    assert packed == sorted(set(where.values())), "every bucket is packed once, in bucket order: %s" % packed
+    return early
+
+
+def test_contract_unchanged_order_overlaps_behind_the_tail_marks(contract_logs):
+    log, where, bad = contract_logs["unchanged"]
+    assert _assert_contract(log, where, bad) == [0]
+    # the usual case costs nothing extra: bucket 0 is marked once, at its own tail, and goes out behind that mark
+    assert [e[1] for e in log if e[0] == "mark"] == [0, 1, 1]
+
+
+def test_contract_flipped_order_bucket_sent_from_finish(contract_logs):
+    log, where, bad = contract_logs["flipped, sent from finish"]
+    assert _assert_contract(log, where, bad) == []
+    assert where["a1"] == where["b1"] == 0 and where["a2"] == where["b2"] == 1
+
+
+def test_contract_flipped_order_bucket_sent_from_a_later_tail(contract_logs):
+    log, where, bad = contract_logs["flipped, sent from a later tail"]
+    # bucket 0 (incomplete at its tail, a1 late) leaves from bucket 1's tail behind a NEW mark; bucket 1 from bucket 2's tail
+    assert _assert_contract(log, where, bad) == [0, 1]
+    assert [e[1] for e in log if e[0] == "mark"][:3] == [0, 1, 0]
+
+
+def test_contract_stream_first_seen_in_a_later_step_is_covered(contract_logs):
+    log, where, bad = contract_logs["new stream"]
+    assert _assert_contract(log, where, bad) == [0]
+    assert all("s1" in e[3] for e in log if e[0] == "mark")
+
+
+def test_contract_parameter_without_a_gradient(contract_logs):
+    log, where, bad = contract_logs["no gradient"]
+    # b2 is bucket 1's tail and never arrives: no hook fires after bucket 0's own tail, so both buckets leave from finish()
+    assert _assert_contract(log, where, bad) == []
+    assert [e[2] for e in log if e[0] == "pack"] == [(True, True), (True, False)]
+
+
+def test_contract_reducer_without_collectives_packs_in_finish_only(contract_logs):
+    for case in ("inactive", "inactive, no gradient"):
+        log, where, bad = contract_logs[case]
+        assert _assert_contract(log, where, bad, active=False) == []
+        assert not [e for e in log if e[0] == "mark"]
