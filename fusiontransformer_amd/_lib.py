@@ -181,6 +181,11 @@ SIGNATURES = {
     "ftx_vit_eval_arena_bytes": (_sz, [_vp, _i32, _i32]),
     "ftx_vit_eval_release": (C.c_int, [_vp]),
     "ftx_vit_eval": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ftx_vit_train_block_bytes": (_i32, []),
+    "ftx_vit_train_arena_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "ftx_vit_train_release": (C.c_int, [_vp]),
+    "ftx_vit_train_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ftx_vit_train_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

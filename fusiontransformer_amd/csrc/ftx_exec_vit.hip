@@ -10,33 +10,12 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
-#include "ftx_common.h"
+#include "ftx_vit_tables.h"
 
 using namespace ftx;
+using namespace ftx::vit;   // the records and their checker, shared with the training executor (ftx_vit_tables.h)
 
-// ---------------------------------------------------------------- tables (layouts documented in include/ftx.h)
 namespace {
-
-struct Model {
-  const float *patch_w, *patch_b, *cls, *dist, *pos;
-  int32_t dim, heads, hidden, patch, grid, t0, in_chans;
-  float eps;
-};
-struct Block {
-  const float *norm1_w, *norm1_b, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2_w, *norm2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
-};
-struct Tap {
-  const float *stem_w, *stem_b, *gamma, *beta, *mean, *var;
-  int32_t block, co;
-  float eps;
-  int32_t reserved;
-};
-static_assert(sizeof(Model) == 72 && sizeof(Block) == 96 && sizeof(Tap) == 64, "table records are packed");
-
-constexpr int kMaxBlocks = 64;
-constexpr int kMaxBatch = 4096;
-
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // Where everything lives, in bytes from the arena's start.  A function of (model sizes, b) alone.
 struct Plan {
@@ -44,22 +23,8 @@ struct Plan {
   int64_t r[2] = {0, 0}, m = 0, h = 0, qkv = 0, att = 0, proj = 0, pre = 0, act = 0, x = 0, lse = 0, stats = 0, total = 0;
 };
 
-int check_model(const char *who, const Model *M, int32_t n_blocks, int32_t b) {
-  FTX_REQUIRE(M, "%s: null model record", who);
-  FTX_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "%s: block count %d outside [1, %d]", who, n_blocks, kMaxBlocks);
-  FTX_REQUIRE(b >= 0 && b <= kMaxBatch, "%s: batch %d outside [0, %d]", who, b, kMaxBatch);
-  FTX_REQUIRE(M->dim == 256 || M->dim == 512 || M->dim == 768 || M->dim == 1024, "%s: dim %d is not one the LayerNorm kernel takes (256, 512, 768, 1024)", who,
-              M->dim);
-  FTX_REQUIRE(M->heads >= 1 && M->heads * 64 == M->dim, "%s: heads * 64 != dim (heads=%d dim=%d)", who, M->heads, M->dim);
-  FTX_REQUIRE(M->hidden >= 64 && M->hidden % 64 == 0 && M->hidden <= 16384, "%s: hidden must be a multiple of 64 (hidden=%d)", who, M->hidden);
-  FTX_REQUIRE(M->t0 == 1 || M->t0 == 2, "%s: t0 must be 1 or 2 (t0=%d)", who, M->t0);
-  FTX_REQUIRE(M->patch >= 4 && M->patch % 4 == 0 && M->patch <= 64 && M->grid >= 1 && M->grid <= 256 && M->in_chans >= 1 && M->in_chans <= 64,
-              "%s: patch %d (a multiple of 4), grid %d or channels %d out of range", who, M->patch, M->grid, M->in_chans);
-  return FTX_OK;
-}
-
 void make_plan(const Model &M, int32_t b, Plan &P) {
-  P.tokens = M.t0 + (int64_t)M.grid * M.grid;
+  P.tokens = tokens_of(M);
   P.rows = (int64_t)b * P.tokens;
   const int64_t row = align256(4 * P.rows * M.dim), wide = align256(4 * P.rows * M.hidden);
   int64_t off = 0;
@@ -127,11 +92,8 @@ extern "C" int ftx_vit_eval(const void *model_host, const void *blocks_host, int
   int rc = check_model(who, Mp, n_blocks, b);
   if (rc != FTX_OK) return rc;
   const Model &M = *Mp;
-  FTX_REQUIRE(blocks, "%s: null block table", who);
-  FTX_REQUIRE(block_first >= 0 && block_first <= block_last && block_last < n_blocks, "%s: blocks [%d, %d] outside 0..%d", who, block_first, block_last,
-              n_blocks - 1);
-  FTX_REQUIRE(linear_mode == 0 || linear_mode == 1, "%s: linear_mode must be 0 (split) or 1 (bf16)", who);
-  FTX_REQUIRE(attn_mode >= 0 && attn_mode <= 2, "%s: attn_mode must be 0 (fp32), 1 (bf16) or 2 (split)", who);
+  rc = check_range(who, blocks, n_blocks, block_first, block_last, linear_mode, attn_mode);
+  if (rc != FTX_OK) return rc;
   FTX_REQUIRE(n_taps >= 0 && n_taps <= kMaxBlocks && (taps || !n_taps) && (tap_out_host || !n_taps), "%s: null tap table or tap count outside [0, %d]", who,
               kMaxBlocks);
   for (int i = 0; i < n_taps; ++i) {
@@ -144,14 +106,8 @@ extern "C" int ftx_vit_eval(const void *model_host, const void *blocks_host, int
     FTX_REQUIRE(b == 0 || tap_out_host[i], "%s: tap %d: null output", who, i);
     FTX_REQUIRE(al16(T.stem_w) && al16(T.stem_b) && al16(tap_out_host[i]), "%s: tap %d: stem weight, bias and output must be 16-byte aligned", who, i);
   }
-  for (int i = block_first; i <= block_last; ++i) {
-    const Block &B = blocks[i];
-    FTX_REQUIRE(B.norm1_w && B.norm1_b && B.qkv_w && B.qkv_b && B.proj_w && B.proj_b && B.norm2_w && B.norm2_b && B.fc1_w && B.fc1_b && B.fc2_w && B.fc2_b,
-                "%s: block %d: null parameter", who, i);
-    FTX_REQUIRE(al16(B.norm1_w) && al16(B.norm1_b) && al16(B.qkv_w) && al16(B.qkv_b) && al16(B.proj_w) && al16(B.proj_b) && al16(B.norm2_w) && al16(B.norm2_b) &&
-                    al16(B.fc1_w) && al16(B.fc1_b) && al16(B.fc2_w) && al16(B.fc2_b),
-                "%s: block %d: parameters must be 16-byte aligned", who, i);
-  }
+  rc = check_blocks(who, blocks, block_first, block_last);
+  if (rc != FTX_OK) return rc;
   if (block_first > 0)
     FTX_REQUIRE(blocks[block_first - 1].fc2_b && al16(blocks[block_first - 1].fc2_b), "%s: block %d: null or misaligned parameter (fc2 bias)", who,
                 block_first - 1);

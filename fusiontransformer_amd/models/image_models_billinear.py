@@ -117,7 +117,7 @@ class Net2DBillinear(nn.Module):
             ckpt = torch.load(kw["IMAGE_PRETRAINED_PATH"], map_location="cpu", weights_only=True)["state_dict"]
             new_state_dict = OrderedDict((k.replace("backbone.", ""), v) for k, v in ckpt.items() if "backbone" in k)
             self.backbone.load_state_dict(new_state_dict)
-        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl
+        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl, image_native_train
         # Training on the GPU runs the trunk as HIP graphs, one per tapped segment (transformers.py): ~500 kernel launches
         # per step become 4 graph launches, which takes 7 ms off the host side of a step (batch 4: the host issue time
         # drops from ~24 to ~17 ms, so the step stays GPU-bound on a slow host; +26-30 % frames/s at batch 1-2).
@@ -178,6 +178,16 @@ class Net2DBillinear(nn.Module):
     def native_eval_reason(self):
         """Why the last forward did not run the native executor; None when it did."""
         return self._native_reason
+
+    def set_native_train(self, on=True):
+        """cfg.MODEL.image_native_train: the trunk's training passes through the native training executor, one autograd node per trunk
+        segment (Image2DTransformer.set_native_train); sample_down, the embedding, the tap stems, the lift and the heads stay as they are."""
+        self.backbone.set_native_train(on)
+        return self
+
+    def native_train_reason(self):
+        """Why the last forward did not run the native training executor; None when it did."""
+        return self.backbone.native_train_reason()
 
     def _native_executor(self, img):
         """The executor when this forward is one it runs (see set_native_eval), else None (and the reason is kept)."""

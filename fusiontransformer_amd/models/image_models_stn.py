@@ -9,7 +9,10 @@ per frame, written in the forward and again in the backward) and then picks ~20k
 samples the 384x384 map at those pixels directly (functional.affine_lift): the resampled map never exists.
 
 The trunk runs eagerly in this model: its input carries the gradient of `stn_down`'s theta, a requires_grad pattern the HIP-graph
-capture of the trunk has not been exercised with."""
+capture of the trunk has not been exercised with.  `cfg.MODEL.image_native_train` (`set_native_train`) is the other way to take the
+trunk's per-op launches off the Python side: every block then runs as one autograd node of the native training executor
+(Image2DTransformer.set_native_train), which delivers the input's gradient to `stn_down` and is bit-identical to the eager trunk;
+it needs vit_linear_impl "ftx_split" (or "ftx" with vit_bf16).  Time of this model: not measured."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -55,7 +58,7 @@ class Net2DSeg(nn.Module):
             ckpt = torch.load(kw["IMAGE_PRETRAINED_PATH"], map_location="cpu", weights_only=True)["state_dict"]
             new_state_dict = OrderedDict((k.replace("backbone.", ""), v) for k, v in ckpt.items() if "backbone" in k)
             self.backbone.load_state_dict(new_state_dict)
-        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl
+        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl, image_native_train
         # parameters that can never receive a gradient: the final `norm` (forward_blocks never applies it) and blocks past the last tap
         for p in self.backbone.norm.parameters():
             p.requires_grad_(False)
@@ -86,6 +89,15 @@ class Net2DSeg(nn.Module):
             m.up_stn.set_loc_impl(impl)
         self.stn_loc_impl = impl
         return self
+
+    def set_native_train(self, on=True):
+        """cfg.MODEL.image_native_train: every block of the trunk as one node of the native training executor (see the module docstring)."""
+        self.backbone.set_native_train(on)
+        return self
+
+    def native_train_reason(self):
+        """Why the last forward did not run the native training executor; None when it did."""
+        return self.backbone.native_train_reason()
 
     def get_img_feats(self, img_indices, block_id: str, image_shape: tuple, backbone_output: Dict):
         """reference image_models_stn.py:63-100 -> (sum N, feat_channels): the rows the reference picks out of the map that

@@ -352,11 +352,87 @@ class Image2DTransformer(nn.Module):
             blk.attn.attn_impl = impl
 
     def set_switches(self, kw):
-        """The three switches above from an image model's backbone_2d_kwargs (cfg.MODEL.attn_impl / vit_bf16 / vit_linear_impl)."""
+        """The three switches above and set_native_train from an image model's backbone_2d_kwargs (cfg.MODEL.attn_impl / vit_bf16 /
+        vit_linear_impl / image_native_train)."""
         self.set_attention_impl(kw.get("attn_impl", "ftx"))
         if kw.get("vit_bf16", False):
             self.set_bf16(True)   # BASELINE configs[4] "bf16 forward"; default is fp32 like the reference
         self.set_linear_impl(kw.get("vit_linear_impl", "library"))
+        self.set_native_train(bool(kw.get("image_native_train", False)))      # cfg.MODEL.image_native_train
+
+    # ---- native training executor of the trunk -------------------------------------------------------------
+    image_native_train = False
+
+    def set_native_train(self, on=True):
+        """Opt-in native executor for the training passes of the trunk (include/ftx.h: ftx_vit_train_fwd / ftx_vit_train_bwd).  With it
+        on, a forward in training mode with gradients enabled, on float32 CUDA tensors and outside a stream capture, runs `_embed` as
+        before and then every trunk segment -- the segments of `_segment_ends()` when `graph_taps` is set, every live block otherwise:
+        those of the eager path -- as one autograd node whose forward and backward are one library call each
+        (native_image_train._VitSegment), issuing the kernels of Block.chain in its order: outputs, gradients and parameters after the
+        step are bit-identical to the switch being off.  It needs no capture, no static buffers and no per-shape state, and it runs
+        after an eager pass.  It engages only when every live block passes Block._fused, runs the linears the library owns
+        (vit_linear_impl "ftx_split", or "ftx" with set_bf16) and one attention impl of "ftx", "ftx_bf16", "ftx_split", and every
+        parameter of the live blocks requires a gradient; anything else takes the existing path exactly as with the switch off, and
+        native_train_reason() says why.  Asked before the HIP graphs; like an eager pass it ends new captures on this trunk."""
+        self.image_native_train = bool(on)
+        if not on:
+            self.__dict__["_native_tr"] = None
+            self.__dict__["_native_tr_reason"] = "the switch is off"
+        return self
+
+    def native_train_reason(self):
+        """Why the last forward_blocks did not run the native training executor; None when it did."""
+        return self.__dict__.get("_native_tr_reason", "the switch is off")
+
+    def _native_trainer(self, x):
+        """The training executor when this forward is one it runs (see set_native_train), else None (and the reason is kept)."""
+        why = None
+        if not self.image_native_train:
+            why = "the switch is off"
+        elif not self.training:
+            why = "eval mode"
+        elif not torch.is_grad_enabled():
+            why = "gradients are disabled"
+        elif not x.is_cuda or x.dtype != torch.float32:
+            why = "the input is not a float32 tensor on the GPU"
+        elif torch.cuda.is_current_stream_capturing():
+            why = "the stream is being captured"
+        else:
+            live = [b for i, b in enumerate(self.blocks) if self.last_block is None or i <= self.last_block]
+            probe = x.new_empty((0, self.embed_dim))      # what Block._fused asks of the tokens: device, dtype and width
+            if not all(b._fused(probe) for b in live):
+                why = "a live block does not run the fused chain (Block._fused)"
+            elif not all(p.requires_grad for b in live for p in b.parameters()):
+                why = "a parameter of a live block is frozen (requires_grad is off)"
+            else:
+                from .. import native_image_train as nit
+                try:
+                    ex = self.__dict__.get("_native_tr")
+                    if ex is None:
+                        ex = self.__dict__["_native_tr"] = nit.NativeImageTrain(self)
+                    ex.ready()      # one pass over the live blocks; the table and the modes are cached behind it
+                except nit.Unsupported as err:
+                    why = str(err)
+        self.__dict__["_native_tr_reason"] = why
+        return self.__dict__["_native_tr"] if why is None else None
+
+    def _forward_native_train(self, ex, x, on_block):
+        """forward_blocks through the training executor: `_embed` here, then one node per segment.  As on the graphed path only segment
+        ends exist as tensors: the taps' outputs with `graph_taps` set, every block's without."""
+        # as after an eager pass (forward_blocks): a capture attempted behind a backward through these parameters aborts the process
+        self._capture_off("the native training executor ran through the trunk before the capture")
+        x = self._embed(x)
+        n_live = len(self.blocks) if self.last_block is None else self.last_block + 1
+        taps = set(int(t) for t in self.graph_taps) if self.graph_taps else None
+        outputs, first = dict(), 0
+        for e in (self._segment_ends() if self.graph_taps else range(n_live)):
+            x = ex.segment(x, first, e)
+            first = e + 1
+            if taps is None or e in taps:
+                outputs[str(e)] = x[:, self.num_tokens:, :] if self.remove_tokens_outputs else x
+                if on_block is not None:
+                    on_block(e, outputs[str(e)])
+        return outputs
 
     def _embed(self, x):
         x = self.patch_embed(x)
@@ -376,6 +452,9 @@ class Image2DTransformer(nn.Module):
         With `graph_taps` set (training on the GPU) the trunk runs as one HIP graph per tapped segment --
         forward and backward: the shapes are static, and ~500 kernel launches per step become 2 x 2 graph
         launches.  Only the tapped blocks' outputs are returned then (the model reads no others)."""
+        trainer = self._native_trainer(x)
+        if trainer is not None:
+            return self._forward_native_train(trainer, x, on_block)
         graphed = self._graphed_segments(x)
         if graphed is not None:
             outputs = dict()

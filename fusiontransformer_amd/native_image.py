@@ -56,9 +56,8 @@ def tap_tensors(up):
     return conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var
 
 
-def modes(net):
-    """(linear_mode, attn_mode) that every live block of the trunk shares, or Unsupported with the reason."""
-    bb = net.backbone
+def trunk_modes(bb):
+    """(linear_mode, attn_mode) that every live block of the trunk `bb` (an Image2DTransformer) shares, or Unsupported with the reason."""
     live = [b for i, b in enumerate(bb.blocks) if bb.last_block is None or i <= bb.last_block]
     lin, att = set(), set()
     for blk in live:
@@ -77,6 +76,11 @@ def modes(net):
     return lin.pop(), _ATTN_MODE[att.pop()]
 
 
+def modes(net):
+    """trunk_modes of a Net2DBillinear's trunk."""
+    return trunk_modes(net.backbone)
+
+
 def _taps_of(net):
     """[(block index, key of net.up)] ascending; the middle tap first when both read the same block."""
     late = int(net.late_feat_block_number)
@@ -87,6 +91,37 @@ def _taps_of(net):
             raise Unsupported("the middle tap lies behind the late tap")
         taps.insert(0, (int(mid), mid))
     return taps
+
+
+def block_table(bb, dev):
+    """The block records of the live blocks of the trunk `bb` at the parameters' present addresses; dev(tensor, what) -> address keeps
+    the tensor.  Raises Unsupported for a block that is not the fused timm block."""
+    import torch.nn as nn
+    n_live = len(bb.blocks) if bb.last_block is None else bb.last_block + 1
+    blk0 = bb.blocks[0]
+    blocks = np.zeros(n_live, dtype=BLOCK)
+    for i in range(n_live):
+        blk = bb.blocks[i]
+        act = blk.mlp.act
+        if (type(blk.norm1) is not nn.LayerNorm or type(blk.norm2) is not nn.LayerNorm or not isinstance(blk.drop_path, nn.Identity)
+                or type(act) is not nn.GELU or act.approximate != "none" or blk.mlp.drop.p != 0.0 or blk.attn.proj_drop.p != 0.0
+                or blk.attn.attn_drop.p != 0.0 or blk.norm1.eps != blk0.norm1.eps or blk.norm2.eps != blk0.norm1.eps
+                or blk.attn.num_heads != blk0.attn.num_heads or blk.mlp.fc1.out_features != blk0.mlp.fc1.out_features
+                or blk.attn.scale != 0.125):
+            raise Unsupported("block %d is not the fused timm block (LayerNorm, exact GELU, no dropout, 64-wide heads)" % i)
+        for name, t in zip(BLOCK_FIELDS, block_tensors(blk)):
+            blocks[i][name] = dev(t, "block %d %s" % (i, name))
+    return blocks
+
+
+def keeper(keep):
+    """dev(tensor, what) of block_table / emit: the address of a contiguous float32 tensor, which is appended to `keep`."""
+    def dev(t, what):
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous():
+            raise Unsupported(what + ": parameters must be contiguous float32")
+        keep.append(t)
+        return t.data_ptr()
+    return dev
 
 
 def emit(net):
@@ -109,15 +144,8 @@ def emit(net):
     t0 = bb.num_tokens
     if tuple(bb.pos_embed.shape) != (1, t0 + grid * grid, dim):
         raise Unsupported("pos_embed does not match the token grid")
-    n_live = len(bb.blocks) if bb.last_block is None else bb.last_block + 1
     keep = []
-
-    def dev(t, what):
-        if t is None or t.dtype != torch.float32 or not t.is_contiguous():
-            raise Unsupported(what + ": parameters must be contiguous float32")
-        keep.append(t)
-        return t.data_ptr()
-
+    dev = keeper(keep)
     model = np.zeros(1, dtype=MODEL)
     m = model[0]
     m["patch_w"], m["patch_b"], m["cls"], m["pos"] = (dev(t, "patch embedding") for t in (conv.weight, conv.bias, bb.cls_token, bb.pos_embed))
@@ -125,18 +153,7 @@ def emit(net):
     blk0 = bb.blocks[0]
     m["dim"], m["heads"], m["hidden"], m["patch"], m["grid"], m["t0"], m["in_chans"] = dim, blk0.attn.num_heads, blk0.mlp.fc1.out_features, P, grid, t0, conv.in_channels
     m["eps"] = blk0.norm1.eps
-    blocks = np.zeros(n_live, dtype=BLOCK)
-    for i in range(n_live):
-        blk = bb.blocks[i]
-        act = blk.mlp.act
-        if (type(blk.norm1) is not nn.LayerNorm or type(blk.norm2) is not nn.LayerNorm or not isinstance(blk.drop_path, nn.Identity)
-                or type(act) is not nn.GELU or act.approximate != "none" or blk.mlp.drop.p != 0.0 or blk.attn.proj_drop.p != 0.0
-                or blk.attn.attn_drop.p != 0.0 or blk.norm1.eps != blk0.norm1.eps or blk.norm2.eps != blk0.norm1.eps
-                or blk.attn.num_heads != blk0.attn.num_heads or blk.mlp.fc1.out_features != blk0.mlp.fc1.out_features
-                or blk.attn.scale != 0.125):
-            raise Unsupported("block %d is not the fused timm block (LayerNorm, exact GELU, no dropout, 64-wide heads)" % i)
-        for name, t in zip(BLOCK_FIELDS, block_tensors(blk)):
-            blocks[i][name] = dev(t, "block %d %s" % (i, name))
+    blocks = block_table(bb, dev)
     spec = _taps_of(net)
     taps = np.zeros(len(spec), dtype=TAP)
     for r, (block, key) in zip(taps, spec):

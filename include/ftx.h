@@ -827,6 +827,57 @@ size_t ftx_vit_eval_arena_bytes(const void *model_host, int32_t n_blocks, int32_
 int ftx_vit_eval_release(const void *arena);
 int ftx_vit_eval(const void *model_host, const void *blocks_host, int32_t n_blocks, const void *taps_host, int32_t n_taps, int32_t b, const float *img, const float *tokens_in, int32_t block_first, int32_t block_last, int32_t linear_mode, int32_t attn_mode, float *const *tap_out_host, void *arena, size_t arena_bytes, void *stream);
 
+/* ---- the ViT trunk in training: one forward and one backward call per trunk segment (models/transformers.py:16-45)
+ *      (csrc/ftx_exec_vit_train.hip; the tables and their checker, shared with ftx_vit_eval: csrc/ftx_vit_tables.h) ----
+ * A segment is blocks [block_first, block_last] from one materialised token tensor x_in (b, t0 + grid grid, dim) to one materialised
+ * token tensor x_out of that shape, x_out = r + (m + fc2_b): the patch embedding, the tap stems, the lift and the heads stay with the
+ * caller.  The model and block records, linear_mode and attn_mode are ftx_vit_eval's, refused with the same texts (the model record's
+ * patch-embedding pointers are not read).
+ *
+ * ftx_vit_train_fwd issues per block what ftx_vit_eval issues -- ftx_add_layernorm_fwd (y NULL on the first block of the segment), the
+ * qkv GEMM with FTX_EPI_BIAS, attention with the automatic tiling and scale 1/8, the proj GEMM with FTX_EPI_NONE, ftx_add_layernorm_fwd
+ * with y_bias = proj's bias, fc1 with FTX_EPI_BIAS_GELU, fc2 with FTX_EPI_NONE -- into per-block regions of the arena, then
+ * ftx_rows_add_bias into x_out.  ftx_vit_train_bwd walks the blocks in reverse and issues per block: for the last block ftx_colsum of
+ * grad_out (the last fc2 bias); fc2's data gradient (w_kn = 1) with FTX_EPI_DGELU, fc2's weight gradient, fc1's data gradient, fc1's
+ * weight gradient, ftx_colsum of fc1's output gradient; ftx_add_layernorm_bwd at norm2 with with_y_bias (d gamma, d beta, d proj bias);
+ * proj's data and weight gradient; the attention backward of the mode; qkv's data gradient, weight gradient and ftx_colsum;
+ * ftx_add_layernorm_bwd at norm1 with with_y_bias (d gamma, d beta and the previous block's d fc2 bias), or without grad_s and y_bias on
+ * the first block of the segment.  x_in feeds that first norm1 and the residual: its two gradients are added by one ftx_rows_add into
+ * grad_in (b, t0 + grid grid, dim), which is fully written.  These are the calls, arguments and workspace sizes of the autograd nodes
+ * of the Python package (transformers.Block.chain), so x_out, grad_in and every parameter gradient have that path's bits.
+ *
+ * Gradient table (grads_host): n_blocks records of the block record's layout (ftx_vit_train_block_bytes() bytes each, twelve device
+ * pointers in the same order) that say where each parameter gradient is written: float32, the parameter's shape, 16-byte aligned,
+ * caller-owned, every element written (not accumulated into).  Records outside [block_first, block_last] are not read.  The LayerNorm
+ * backward writes (d gamma, d beta, d y_bias) as one (3, dim) array: where norm2_w, norm2_b, proj_b of a record are consecutive in
+ * memory (and norm1_w, norm1_b and the previous record's fc2_b, for a block behind the first of the segment) it writes them in place;
+ * otherwise they pass through the arena and three more small launches copy them.
+ *
+ * Arena: device memory, 256-byte aligned, caller-owned, the same buffer for the forward and its backward, not to be written in between.
+ * ftx_vit_train_arena_bytes(model, n_blocks, block_first, block_last, b) is a host function of its arguments alone (0 and an error
+ * text for a record or a range it refuses), a multiple of 256, growing with b and with the number of blocks.  With rows = b (t0 + grid
+ * grid), row = 4 rows dim, wide = 4 rows hidden, stat = 8 rows and lse = 4 b heads (t0 + grid grid) bytes, each rounded up to 256:
+ *   per block      what the backward reads: s, h, att, s2, h2 (row each; no s for the first block of the segment, whose s is x_in),
+ *                  qkv (3 row), pre, act (wide each), the two LayerNorm statistics (stat each), lse:
+ *                  8 row + 2 wide + 2 stat + lse, less one row for the first block;
+ *   once           3 row (the flowing gradients and the second contribution to grad_in; the forward keeps fc2's and proj's output
+ *                  there) + wide (fc1's output gradient) + 3 row (the attention's input gradient) + the largest of
+ *                  ftx_attn_bwd_workspace_bytes(b, t0 + grid grid, heads), ftx_layernorm_bwd_workspace_bytes(rows, dim),
+ *                  ftx_colsum_workspace_bytes(rows, dim | hidden | 3 dim) and ftx_dense_wgrad_<split|bf16>_workspace_bytes(rows, n, k)
+ *                  over the four Linears + 12 dim (the LayerNorm's parameter gradients on their way to buffers that are apart).
+ * Refused before the first launch (FTX_EINVAL): what ftx_vit_eval refuses of the model record, the block range and the modes; a null or
+ * not 16-byte aligned parameter or gradient pointer of a block in the range; null or misaligned x_in, x_out, grad_out, grad_in; an
+ * arena that is too small is FTX_EWORKSPACE.  b == 0 returns FTX_OK without touching the arena.  A failing launch names the block and
+ * the op.  No host synchronisation and no allocation.  The library keeps a host-side note per arena address of the forward it holds:
+ * ftx_vit_train_bwd is refused when no forward with the same (b, block_first, block_last, linear_mode, attn_mode) was issued on that
+ * arena, and when it is issued a second time (the first backward overwrites the temporaries).  ftx_vit_train_release(arena) drops the
+ * note (host only, always FTX_OK): call it before freeing an arena or giving its memory another use. */
+int32_t ftx_vit_train_block_bytes(void);
+size_t ftx_vit_train_arena_bytes(const void *model_host, int32_t n_blocks, int32_t block_first, int32_t block_last, int32_t b);
+int ftx_vit_train_release(const void *arena);
+int ftx_vit_train_fwd(const void *model_host, const void *blocks_host, int32_t n_blocks, int32_t b, const float *x_in, int32_t block_first, int32_t block_last, int32_t linear_mode, int32_t attn_mode, float *x_out, void *arena, size_t arena_bytes, void *stream);
+int ftx_vit_train_bwd(const void *model_host, const void *blocks_host, const void *grads_host, int32_t n_blocks, int32_t b, const float *x_in, const float *grad_out, int32_t block_first, int32_t block_last, int32_t linear_mode, int32_t attn_mode, float *grad_in, void *arena, size_t arena_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

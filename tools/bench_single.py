@@ -4,6 +4,7 @@ usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/s
        python tools/bench_single.py --image-stn [--steps 60] [--out profiles/image_stn_steps.json]   # only: ImageSeg beside ImageSegBilinear
        python tools/bench_single.py --native-index-ab [--steps 20]     # LidarSeg steps, native index build off / on, alternating windows
        python tools/bench_single.py --native-train-ab [--steps 20] [--ab-model LidarSeg|middle]   # the same for the training executor
+       python tools/bench_single.py --native-image-train-ab [--steps 20]   # the ViT trunk in training: HIP graphs / eager / the native training executor
        python tools/bench_single.py --native-train-steps on|off --steps N     # N untimed batch-1 steps, to count launches under a kernel trace
        python tools/bench_single.py --lidar-split [--steps 20] [--out profiles/spconv_split_steps.json]   # LidarSeg steps, default against lidar_split
 
@@ -189,6 +190,82 @@ def native_train_ab(batch, steps, warmup, windows=5, model_kind="LidarSeg"):
     return _switch_ab("native_train", batch, steps, warmup, windows, model_kind)
 
 
+def native_image_train_ab(batch, steps, warmup, windows=5, model_kind="ImageSegBilinear"):
+    """Step time of the three ways the ViT trunk trains, vit_linear_impl="ftx_split", with the method of _switch_ab: three models from
+    one seed in one process -- `graphs` (the switch off, the trunk as HIP graphs: the default path), `eager` (the switch off,
+    vit_graphs=False) and `native` (Image2DTransformer.set_native_train) -- windows of `steps` steps alternating between them; median
+    (min..max) ms per step, and per arm the loop's wall clock per step before the synchronise (the host-issue bound), the autograd nodes
+    under the image logits and the peak of torch's allocator above what was resident; for `native` the bytes of its arenas in one step."""
+    import time
+    from fusiontransformer_amd import config
+    from fusiontransformer_amd import native_image_train as nit
+    from fusiontransformer_amd.models.build import build_model
+    from fusiontransformer_amd.trainer import TrainStep
+    _, res = zip(*[_inputs(batch, cycle, "cuda") for cycle in (0, 1)])
+    arms, nets = {}, {}
+    for mode in ("graphs", "eager", "native"):      # the captures of `graphs` come first (its warm-up window runs first, too)
+        cfg = config.image_cfg() if model_kind == "ImageSegBilinear" else config.fusion_cfg(model_kind)
+        cfg.MODEL.vit_linear_impl = "ftx_split"
+        cfg.MODEL.vit_graphs = mode != "eager"
+        cfg.MODEL.image_native_train = mode == "native"
+        torch.manual_seed(0)
+        model = build_model(cfg)[0].cuda().train()
+        nets[mode] = model.image_backbone
+        arms[mode] = TrainStep(cfg, model)
+    info = {m: {} for m in arms}
+
+    def window(mode, n):
+        step = arms[mode]
+        seq = [res[i % 2] for i in range(n + 1)]
+        for x in seq:
+            x["lidar"].prepared = None
+        torch.cuda.synchronize()
+        resident = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        for i in range(n):
+            preds = step(seq[i], next_batch=seq[i + 1])
+        e1.record()
+        host = (time.perf_counter() - t0) * 1e3 / n
+        torch.cuda.synchronize()
+        info[mode].setdefault("host_issue_ms", []).append(host)
+        info[mode]["autograd_nodes"] = _graph_nodes(preds["img_seg_logit"])
+        info[mode]["peak_above_resident_bytes"] = int(torch.cuda.max_memory_allocated() - resident)
+        return e0.elapsed_time(e1) / n
+
+    for mode in arms:
+        window(mode, warmup)
+        info[mode]["host_issue_ms"] = []
+    ms = {m: [] for m in arms}
+    order = list(arms)
+    for w in range(windows):
+        for mode in order[w % 3:] + order[:w % 3]:
+            ms[mode].append(window(mode, steps))
+    spread = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    out = {"model": model_kind, "vit_linear_impl": "ftx_split", "batch": batch, "steps_per_window": steps, "windows": windows,
+           "ms_per_step": {m: spread(v) for m, v in ms.items()}, "ms_per_step_windows": ms}
+    for m in arms:
+        out[m] = dict(info[m], host_issue_ms=spread(info[m]["host_issue_ms"]))
+    trunk = nets["native"].backbone
+    out["native"]["reason"] = trunk.native_train_reason()
+    out["graphs"]["graph_state"] = nets["graphs"].backbone.graph_state()
+    ex = trunk.__dict__.get("_native_tr")
+    if ex is not None and trunk.native_train_reason() is None:
+        ends, first, total = trunk._segment_ends(), 0, 0
+        tokens = trunk.num_tokens + trunk.patch_embed.num_patches
+        for e in ends:
+            total += nit.arena_bytes(ex.model(tokens), len(ex.live()), first, e, batch)
+            first = e + 1
+        out["native"]["arena_bytes_per_step"] = int(total)
+        out["native"]["segments"] = len(ends)
+    for other in ("graphs", "eager"):
+        out["every_native_window_beats_every_%s_window" % other] = bool(max(ms["native"]) < min(ms[other]))
+        out["every_%s_window_beats_every_native_window" % other] = bool(max(ms[other]) < min(ms["native"]))
+    return out
+
+
 def lidar_split_ab(batch, steps, warmup, windows=5):
     """LidarSeg step time with the default exact-fp32 sparse convolution and with SPVCNN.set_split (the three-piece split kernels): two
     models from one seed in one process, `windows` windows of `steps` steps each, alternating."""
@@ -290,6 +367,9 @@ def main():
     ap.add_argument("--native-index-ab", action="store_true", help="only: LidarSeg step time with SPVCNN.set_native_index off / on, batch 1 and 4")
     ap.add_argument("--native-train-ab", action="store_true", help="only: step time with SPVCNN.set_native_train off / on, batch 1 and 4")
     ap.add_argument("--ab-model", default="LidarSeg", choices=["LidarSeg", "middle"], help="the model of --native-train-ab")
+    ap.add_argument("--native-image-train-ab", action="store_true",
+                    help="only: ImageSegBilinear and middle-fusion step time, vit_linear_impl=ftx_split, trunk as HIP graphs / eager / native training "
+                         "executor (Image2DTransformer.set_native_train), batch 1 and 4")
     ap.add_argument("--native-train-steps", choices=["on", "off"], help="only: --steps untimed LidarSeg batch-1 steps with the switch on / off")
     ap.add_argument("--lidar-split", action="store_true", help="only: LidarSeg step time with SPVCNN.set_split off / on, batch 4 and 1; --out writes the JSON")
     args = ap.parse_args()
@@ -298,6 +378,11 @@ def main():
     if args.native_train_ab:
         for batch in (1, 4):
             print(json.dumps(native_train_ab(batch, args.steps, args.warmup, model_kind=args.ab_model)), flush=True)
+        return
+    if args.native_image_train_ab:
+        for kind in ("ImageSegBilinear", "middle"):
+            for batch in (1, 4):
+                print(json.dumps(native_image_train_ab(batch, args.steps, args.warmup, model_kind=kind)), flush=True)
         return
     if args.native_train_steps:
         print(json.dumps(native_train_steps(args.native_train_steps, args.steps)), flush=True)
