@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libftx.so")
 
-_i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
+_i32, _i64, _f32, _vp, _sz, _u64 = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_uint64
 
 # name -> (restype, argtypes); mirrors include/ftx.h one to one
 SIGNATURES = {
@@ -162,6 +162,13 @@ SIGNATURES = {
     "ftx_spvcnn_train_arena_bytes": (_sz, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "ftx_spvcnn_train_fwd": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ftx_spvcnn_train_bwd": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ftx_spvcnn_train_fwd_rng": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _u64,
+                                           _u64]),
+    "ftx_spvcnn_train_bwd_rng": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _u64,
+                                           _u64]),
+    "ftx_dropout_sweep_elements": (_i64, []),
+    "ftx_dropout": (C.c_int, [_vp, _i64, _f32, _u64, _u64, _u64, _vp, _vp]),
+    "ftx_dropout_mask": (C.c_int, [_i64, _f32, _u64, _u64, _u64, _vp, _vp]),
     "ftx_spvcnn_index_layout_words": (_i32, []),
     "ftx_spvcnn_index_layout": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _vp]),
     "ftx_spvcnn_index_levels_arena_bytes": (_sz, [_i64]),

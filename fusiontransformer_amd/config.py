@@ -64,6 +64,8 @@ def get_cfg_defaults() -> CfgNode:
             # the LiDAR branch's GEMM operands (SPVCNN.set_bf16 / set_split; at most one of the two): rounded to bf16, or split into
             # three bf16 pieces for fp32-class results on the bf16 MFMA.  Both off: the exact fp32 MFMA.
             "lidar_bf16": False, "lidar_split": False,
+            # the LiDAR branch's Dropout from the library's counter-based stream instead of torch's (SPVCNN.set_native_dropout)
+            "lidar_native_dropout": False,
         },
         "OPTIMIZER": {"TYPE": "", "BASE_LR": 0.001, "WEIGHT_DECAY": 0.0, "Adam": {"betas": (0.9, 0.999)}},
         "TRAIN": {"BATCH_SIZE": 0, "CLASS_WEIGHTS": [], "FusionTransformer": {"lambda_xm": 0.0}},

@@ -58,6 +58,8 @@ struct Exec {
   const TrainPV *tpvs = nullptr;
   const float *grad_out = nullptr;
   int gout_slot = -1;
+  // the _rng entries': the random stream of the program's DROPOUT ops (site s draws call_base + s)
+  uint64_t seed = 0, call_base = 0;
 
   float *F(int s) const {
     if (s == in_slot) return const_cast<float *>(seg_in);
@@ -180,6 +182,9 @@ int Exec::fwd_op(int i, Carve &cv) const {
     case FTX_SPVCNN_OP_ADD_EXT:
       if (launch && add[o.layer]) RUN(ftx_rows_add(F(o.src), add[o.layer], n, o.channels, F(o.dst), stream));
       break;
+    case FTX_SPVCNN_OP_DROPOUT:
+      if (launch) RUN(ftx_dropout(F(o.src), n * o.channels, dropout_p(o), seed, call_base + (uint64_t)o.layer, 0, F(o.dst), stream));
+      break;
   }
   return FTX_OK;
 }
@@ -282,6 +287,11 @@ int Exec::bwd_op(int i, Carve &cv) const {
     case FTX_SPVCNN_OP_ADD:       // both operands take the gradient of the sum as it is: their gradient buffers ARE the sum's
     case FTX_SPVCNN_OP_ADD_EXT:   // in place: the slot's gradient is also the addend's
       break;
+    case FTX_SPVCNN_OP_DROPOUT: {   // the same mask, recomputed, on the slot's gradient in place (check_program: the buffer is the slot's own)
+      float *g = launch ? G(o.src) : nullptr;
+      RUN(ftx_dropout(g, n * o.channels, dropout_p(o), seed, call_base + (uint64_t)o.layer, 0, g, stream));
+      break;
+    }
   }
   return FTX_OK;
 }
@@ -386,18 +396,28 @@ extern "C" size_t ftx_spvcnn_train_arena_bytes(const void *layers_host, int32_t 
   return (size_t)P.total;
 }
 
-extern "C" int ftx_spvcnn_train_fwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops,
-                                    const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs,
-                                    const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment,
-                                    const float *seg_in, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out,
-                                    float **seg_out, void *stream) {
-  const char *entry = "ftx_spvcnn_train_fwd";
+namespace {
+
+// The plain entries have no random stream: they refuse a program with a DROPOUT op, before the first launch.
+int check_rng(const char *entry, const SpvcnnTables &T, bool rng) {
+  for (int i = 0; i < T.n_ops && !rng; ++i)
+    FTX_REQUIRE(T.ops[i].kind != FTX_SPVCNN_OP_DROPOUT, "%s: op %d is a Dropout, which draws from the random stream: call %s_rng with (seed, call_base)", entry, i,
+                entry);
+  return FTX_OK;
+}
+
+int train_fwd(const char *entry, bool rng, uint64_t seed, uint64_t call_base, const void *layers_host, const void *train_layers_host, int32_t n_layers,
+              const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs,
+              const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in,
+              const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, float **seg_out, void *stream) {
   const SpvcnnTables T = spvcnn_tables(layers_host, n_layers, ops_host, n_ops, rows_host, maps_host, n_maps, pvs_host, n_pvs, routes_host, grad_routes_host);
   SlotFacts F;
   Plan P;
   int rc = make_plan(T, F, P);
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE(train_layers_host || !n_layers, "%s: null train table", entry);
+  rc = check_rng(entry, T, rng);
+  if (rc != FTX_OK) return rc;
   rc = check_call(entry, T, F, P, first_segment, last_segment, seg_in, arena, arena_bytes);
   if (rc != FTX_OK) return rc;
   const int out_slot = F.out_slot[last_segment];
@@ -406,6 +426,8 @@ extern "C" int ftx_spvcnn_train_fwd(const void *layers_host, const void *train_l
   E.add[0] = add_early;
   E.add[1] = add_middle;
   E.out = out;
+  E.seed = seed;
+  E.call_base = call_base;
   // everything above answered on the host; from here on launches only
   for (int i = 0; i < n_ops; ++i) {
     if (T.ops[i].segment < first_segment || T.ops[i].segment > last_segment) continue;
@@ -418,12 +440,10 @@ extern "C" int ftx_spvcnn_train_fwd(const void *layers_host, const void *train_l
   return FTX_OK;
 }
 
-extern "C" int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops,
-                                    const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, const void *train_pvs_host,
-                                    int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment,
-                                    int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in,
-                                    void *stream) {
-  const char *entry = "ftx_spvcnn_train_bwd";
+int train_bwd(const char *entry, bool rng, uint64_t seed, uint64_t call_base, const void *layers_host, const void *train_layers_host, int32_t n_layers,
+              const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host,
+              const void *train_pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment,
+              int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in, void *stream) {
   const SpvcnnTables T = spvcnn_tables(layers_host, n_layers, ops_host, n_ops, rows_host, maps_host, n_maps, pvs_host, n_pvs, routes_host, grad_routes_host);
   const TrainLayer *tl = (const TrainLayer *)train_layers_host;
   SlotFacts F;
@@ -431,6 +451,8 @@ extern "C" int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_l
   int rc = make_plan(T, F, P);
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE((tl || !n_layers) && (train_pvs_host || !n_pvs), "%s: null train table", entry);
+  rc = check_rng(entry, T, rng);
+  if (rc != FTX_OK) return rc;
   rc = check_call(entry, T, F, P, first_segment, last_segment, seg_in, arena, arena_bytes);
   if (rc != FTX_OK) return rc;
   FTX_REQUIRE(grad_out && ((uintptr_t)grad_out & 15) == 0, "%s: null or misaligned output gradient", entry);
@@ -444,6 +466,8 @@ extern "C" int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_l
   E.tpvs = (const TrainPV *)train_pvs_host;
   E.grad_out = grad_out;
   E.gout_slot = F.out_slot[last_segment];
+  E.seed = seed;
+  E.call_base = call_base;
   for (int i = n_ops - 1; i >= 0; --i) {
     if (T.ops[i].segment < first_segment || T.ops[i].segment > last_segment) continue;
     Carve cv;
@@ -453,4 +477,44 @@ extern "C" int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_l
   }
   if (grad_in) *grad_in = first_segment ? E.G(E.in_slot) : nullptr;
   return FTX_OK;
+}
+
+}  // namespace
+
+extern "C" int ftx_spvcnn_train_fwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops,
+                                    const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs,
+                                    const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment,
+                                    const float *seg_in, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out,
+                                    float **seg_out, void *stream) {
+  return train_fwd("ftx_spvcnn_train_fwd", false, 0, 0, layers_host, train_layers_host, n_layers, ops_host, n_ops, rows_host, maps_host, n_maps, pvs_host, n_pvs,
+                   routes_host, grad_routes_host, first_segment, last_segment, seg_in, add_early, add_middle, arena, arena_bytes, out, seg_out, stream);
+}
+
+extern "C" int ftx_spvcnn_train_fwd_rng(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops,
+                                        const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs,
+                                        const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment,
+                                        const float *seg_in, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out,
+                                        float **seg_out, void *stream, uint64_t seed, uint64_t call_base) {
+  return train_fwd("ftx_spvcnn_train_fwd_rng", true, seed, call_base, layers_host, train_layers_host, n_layers, ops_host, n_ops, rows_host, maps_host, n_maps,
+                   pvs_host, n_pvs, routes_host, grad_routes_host, first_segment, last_segment, seg_in, add_early, add_middle, arena, arena_bytes, out, seg_out,
+                   stream);
+}
+
+extern "C" int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops,
+                                    const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, const void *train_pvs_host,
+                                    int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment,
+                                    int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in,
+                                    void *stream) {
+  return train_bwd("ftx_spvcnn_train_bwd", false, 0, 0, layers_host, train_layers_host, n_layers, ops_host, n_ops, rows_host, maps_host, n_maps, pvs_host,
+                   train_pvs_host, n_pvs, routes_host, grad_routes_host, first_segment, last_segment, seg_in, grad_out, arena, arena_bytes, grad_in, stream);
+}
+
+extern "C" int ftx_spvcnn_train_bwd_rng(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops,
+                                        const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, const void *train_pvs_host,
+                                        int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment,
+                                        int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in,
+                                        void *stream, uint64_t seed, uint64_t call_base) {
+  return train_bwd("ftx_spvcnn_train_bwd_rng", true, seed, call_base, layers_host, train_layers_host, n_layers, ops_host, n_ops, rows_host, maps_host, n_maps,
+                   pvs_host, train_pvs_host, n_pvs, routes_host, grad_routes_host, first_segment, last_segment, seg_in, grad_out, arena, arena_bytes, grad_in,
+                   stream);
 }

@@ -3,6 +3,7 @@
 // Nothing here places memory or launches; each executor places its own arena from the facts the checker leaves.  Where the two
 // executors ask different things of the same program the checker says so in a `train` / eval branch at that point.
 #pragma once
+#include <string.h>
 #include <string>
 #include <vector>
 #include "ftx_common.h"
@@ -20,7 +21,7 @@ constexpr int kMaxSlots = 256;
 constexpr int kMaxOps = 4096;
 constexpr int kMaxSegments = 8;   // of the training program; the eval program has the three of FTX_SPVCNN_SEG_*
 constexpr int64_t kOstatMaxRows = 64 * 4096;
-constexpr const char *kKindName[] = {"?", "conv_bn", "linear_bn", "voxelize", "devoxelize", "concat", "add", "add_ext"};
+constexpr const char *kKindName[] = {"?", "conv_bn", "linear_bn", "voxelize", "devoxelize", "concat", "add", "add_ext", "dropout"};
 
 // the tables of one call, as the entry points are given them (layouts documented in include/ftx.h); groutes is the training executor's
 struct SpvcnnTables {
@@ -79,6 +80,13 @@ struct SlotFacts {
   int n_segments = 0, in_slot[kMaxSegments], out_slot[kMaxSegments];
 };
 
+// p of a DROPOUT op: reserved0 holds its IEEE bits
+inline float dropout_p(const Op &o) {
+  float p;
+  memcpy(&p, &o.reserved0, sizeof p);
+  return p;
+}
+
 // an executor's error at op i, around the text of the per-op entry point that refused
 inline int fail(const char *entry, int i, const Op &o, int rc) {
   const std::string inner = ftx_last_error();
@@ -122,7 +130,7 @@ static inline int check_program(const SpvcnnTables &T, bool train, SlotFacts &F)
   auto slot_ok = [](int s) { return s >= 0 && s < kMaxSlots; };
   for (int i = 0; i < n_ops; ++i) {
     const Op &o = ops[i];
-    FTX_REQUIRE(o.kind >= FTX_SPVCNN_OP_CONV_BN && o.kind <= FTX_SPVCNN_OP_ADD_EXT, "%s: op %d: unknown kind %d", who, i, o.kind);
+    FTX_REQUIRE(o.kind >= FTX_SPVCNN_OP_CONV_BN && o.kind <= FTX_SPVCNN_OP_DROPOUT, "%s: op %d: unknown kind %d", who, i, o.kind);
     const char *kn = kKindName[o.kind];
     if (train)   // one autograd node per segment: any number of them, none skipped
       FTX_REQUIRE((o.segment == seg || o.segment == seg + 1) && o.segment < kMaxSegments && (i > 0 || o.segment == 0),
@@ -266,8 +274,17 @@ static inline int check_program(const SpvcnnTables &T, bool train, SlotFacts &F)
         if (train)
           FTX_REQUIRE(F.uses[o.src] == 0, "%s: op %d (%s): slot %d is read before the addend reaches it, and the backward would read it after", who, i, kn, o.src);
         break;
+      case FTX_SPVCNN_OP_DROPOUT: {   // train only: in place like ADD_EXT; no gradient goes anywhere, the backward scales the slot's gradient in place
+        FTX_REQUIRE(train, "%s: op %d (%s): the eval program has no Dropout (it is the identity in eval mode)", who, i, kn);
+        FTX_REQUIRE(o.dst == o.src && o.layer >= 0 && F.level[o.src] == o.level && F.ch[o.src] == o.channels && o.src >= FTX_SPVCNN_SLOT_FIRST,
+                    "%s: op %d (%s): Dropout works in place on an arena slot (layer = its site number >= 0)", who, i, kn);
+        FTX_REQUIRE(F.uses[o.src] == 0, "%s: op %d (%s): slot %d is read before the Dropout reaches it, and the backward would read it after", who, i, kn, o.src);
+        const float p = dropout_p(o);
+        FTX_REQUIRE(p >= 0.0f && p < 1.0f, "%s: op %d (%s): p = %g outside [0, 1)", who, i, kn, (double)p);
+        break;
+      }
     }
-    if (o.kind != FTX_SPVCNN_OP_ADD_EXT) {
+    if (o.kind != FTX_SPVCNN_OP_ADD_EXT && o.kind != FTX_SPVCNN_OP_DROPOUT) {
       FTX_REQUIRE(o.dst != FTX_SPVCNN_SLOT_INPUT && F.def[o.dst] < 0, "%s: op %d (%s): slot %d is written twice", who, i, kn, o.dst);
       FTX_REQUIRE(o.dst != FTX_SPVCNN_SLOT_OUTPUT || o.level == kLevels - 1, "%s: op %d (%s): the output slot holds point rows", who, i, kn);
       if (train)
@@ -290,6 +307,12 @@ static inline int check_program(const SpvcnnTables &T, bool train, SlotFacts &F)
   for (int i = 0; i < n_ops; ++i) F.out_slot[ops[i].segment] = ops[i].dst;
   for (int s = 0; s < F.n_segments; ++s) F.in_slot[s] = s ? F.out_slot[s - 1] : FTX_SPVCNN_SLOT_INPUT;
   FTX_REQUIRE(F.out_slot[F.n_segments - 1] == FTX_SPVCNN_SLOT_OUTPUT && F.def[FTX_SPVCNN_SLOT_OUTPUT] >= 0, "%s: the last op writes the output slot", who);
+  for (int i = 0; i < n_ops; ++i) {   // the backward of a Dropout scales its slot's gradient buffer in place: that buffer is the slot's own, inside the arena
+    const Op &o = ops[i];
+    if (o.kind != FTX_SPVCNN_OP_DROPOUT) continue;
+    FTX_REQUIRE(F.galias[o.src] < 0 && F.out_slot[o.segment] != o.src, "%s: op %d (dropout): slot %d is an operand of an add or the result of its segment: "
+                "its gradient is another buffer's", who, i, o.src);
+  }
   for (int s = FTX_SPVCNN_SLOT_OUTPUT; s < kMaxSlots; ++s) {
     if (F.def[s] < 0) continue;
     if (F.galias[s] >= 0) FTX_REQUIRE(F.uses[s] == 1, "%s: slot %d is an operand of an add and of another op: its gradient would need a copy", who, s);

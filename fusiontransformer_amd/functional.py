@@ -2076,3 +2076,8 @@ def resize_bilinear_u8(image_u8: torch.Tensor, size) -> torch.Tensor:
     check(L.ftx_resize_bilinear_u8(ptr(image_u8), st[0] if batched else 0, st[-3], n, h, w, c, ptr(bx), ptr(kx), ksx, ptr(by), ptr(ky), ksy,
                                    oh, ow, ptr(out), ws, nbytes, stream()), "ftx_resize_bilinear_u8")
     return out if batched else out[0]
+
+
+# ---------------------------------------------------------------- Dropout
+# The counter-based Dropout of the library; the node and its wrappers live in dropout.py.
+from .dropout import dropout, dropout_mask  # noqa: E402,F401

@@ -19,6 +19,7 @@ from ..sparse import PendingIndex, PointTensor, PreparedIndex, SparseTensor, cat
 from .utils import initial_voxelize_steps, point_index, point_to_voxel, voxel_index, voxel_to_point
 
 __all__ = ["SPVCNN", "Conv3d", "BatchNorm", "ReLU"]
+_U64 = (1 << 64) - 1
 
 
 class Conv3d(nn.Module):
@@ -248,6 +249,10 @@ class SPVCNN(nn.Module):
         # cfg.MODEL.lidar_native_train: the training forward and backward through the native executor, see set_native_train
         self._native_tr = None
         self.set_native_train(bool(kwargs.get("lidar_native_train", False)))
+        # cfg.MODEL.lidar_native_dropout: Dropout from the library's counter-based stream, see set_native_dropout.  Plain attributes, not
+        # buffers: the state_dict keys stay the reference's
+        self._drop_seed, self._drop_forwards, self._drop_last = 0, 0, None
+        self.set_native_dropout(bool(kwargs.get("lidar_native_dropout", False)))
         # optional injected keep-masks {'y1': (N4,C), 'y3': (N2,C)} so a train-mode run can be
         # compared with the oracle (Dropout RNG streams differ between CPU and GPU)
         self.dropout_masks = None
@@ -317,7 +322,8 @@ class SPVCNN(nn.Module):
         gradients enabled and features on the GPU, builds the batch's coordinate structures as before and then runs the network -- first
         convolution of the stem to z3.F -- as five segments, each ONE autograd node whose forward and backward are one library call
         (stem | encoder | z1 -> y1 | up1, up2, z2 -> y3 | up3, up4, z3: a segment ends where a Dropout follows, which stays torch's),
-        over one arena per forward instead of ~200 nodes through Python.  Same kernels in the same order: logits, every gradient and
+        over one arena per forward instead of ~200 nodes through Python; with set_native_dropout also on, Dropout is an op of the program
+        and the segments are three (stem | encoder | decoder).  Same kernels in the same order: logits, every gradient and
         every running statistic are bit-identical to the switch being off.  Independent of set_native_eval, set_native_index and
         set_bf16.  In eval mode, without gradients, on CPU tensors, with a frozen parameter, for a module tree the emitter refuses or
         a batch the library refuses, the existing path runs exactly as with the switch off."""
@@ -325,6 +331,58 @@ class SPVCNN(nn.Module):
         if not on:
             self._native_tr = None
         return self
+
+    def set_native_dropout(self, on=True, seed=None):
+        """Opt-in Dropout from the library's counter-based stream (include/ftx.h: ftx_dropout) instead of torch's.  With it on, a forward in
+        training mode with gradients enabled draws both Dropouts (y1: site 0, y3: site 1, p of self.dropout) as functional.dropout with
+        call = call_base + site, where call_base = 2 * (training forwards so far that reached Dropout): the masks are a pure function of
+        (seed, call, element), identical on every device and torch version, recomputed in the backward, and last_dropout_masks() states
+        them after the fact.  `seed`: None takes torch.initial_seed() as it is NOW, masked to 64 bits.  With set_native_train also on,
+        Dropout is an op of the training program, which then runs in three segments (stem | encoder | decoder) as the eval executor
+        does; the two paths agree bit for bit for equal dropout_state().  Injected `dropout_masks` and this switch exclude each other
+        (ValueError in the forward).  Eval mode and forwards without gradients are unchanged; independent of every other switch.  Not
+        for a forward captured into a HIP graph: seed and call go to the kernel by value, so a replay would repeat its masks."""
+        self.lidar_native_dropout = bool(on)
+        if on:
+            self._drop_seed = (torch.initial_seed() if seed is None else int(seed)) & _U64
+        self._native_tr = None        # the training program is another one: emitted again at the next forward
+        return self
+
+    def dropout_state(self):
+        """{seed, forwards} of the native Dropout: what set_dropout_state takes to make the next training forward draw the same masks."""
+        return {"seed": self._drop_seed, "forwards": self._drop_forwards}
+
+    def set_dropout_state(self, state):
+        seed, forwards = int(state["seed"]), int(state["forwards"])
+        if not 0 <= seed <= _U64 or forwards < 0:
+            raise ValueError("set_dropout_state: seed in [0, 2^64) and forwards >= 0 expected")
+        self._drop_seed, self._drop_forwards = seed, forwards
+        return self
+
+    def last_dropout_masks(self):
+        """{'y1': (N4, C) bool, 'y3': (N2, C) bool}: the keep-masks the most recent native-Dropout training forward applied, recomputed
+        from its (seed, call_base) and the row counts of last_index -- what an oracle takes as `dropout_masks`."""
+        if self._drop_last is None:
+            raise RuntimeError("last_dropout_masks: no training forward has drawn a native Dropout mask yet")
+        seed, base = self._drop_last
+        x4, x2 = self.last_index["x4"].C, self.last_index["x2"].C
+        return {"y1": spf.dropout_mask((x4.shape[0], self.cs[4]), self.dropout.p, seed, base & _U64, device=x4.device),
+                "y3": spf.dropout_mask((x2.shape[0], self.cs[6]), self.dropout.p, seed, (base + 1) & _U64, device=x2.device)}
+
+    def _native_dropout_here(self):
+        """Whether this forward draws its Dropout from the library's stream (see set_native_dropout)."""
+        if not (self.lidar_native_dropout and self.training and torch.is_grad_enabled()):
+            return False
+        if self.dropout_masks is not None:
+            raise ValueError("SPVCNN: dropout_masks are injected while set_native_dropout is on: it is one or the other")
+        return True
+
+    def _take_call_base(self):
+        """call_base of this training forward (its two sites draw call_base and call_base + 1); counts the forward."""
+        base = 2 * self._drop_forwards
+        self._drop_forwards += 1
+        self._drop_last = (self._drop_seed, base)
+        return base
 
     def _native_trainer(self, x):
         """The training executor when this forward is one it runs (see set_native_train), else None."""
@@ -334,7 +392,7 @@ class SPVCNN(nn.Module):
         if self._native_tr is None:
             from .. import native_train
             try:
-                self._native_tr = native_train.NativeTrain(self)
+                self._native_tr = native_train.NativeTrain(self, native_dropout=self.lidar_native_dropout)
             except native_train.Unsupported:
                 self._native_tr = False
         if not self._native_tr or not self._native_tr.trainable():
@@ -342,17 +400,21 @@ class SPVCNN(nn.Module):
         return self._native_tr
 
     def _native_train_steps(self, run, z, x0, fuse_early, fuse_middle):
-        """_backbone_steps from "voxelized" on through the training executor: one autograd node per segment, Dropout between them."""
+        """_backbone_steps from "voxelized" on through the training executor: one autograd node per segment, Dropout between them --
+        or, with set_native_dropout, inside the third and last (run.rng holds the pair its two ops draw with)."""
         z0 = run.segment(0, x0.F)
         early = yield from _addend_steps(fuse_early, "need_early")
         yield "stem"
         z1 = run.segment(1, z0, early)
         middle = yield from _addend_steps(fuse_middle, "need_middle")
         yield "stage4"
-        y1 = self._drop(run.segment(2, z1, middle), "y1")
-        y3 = self._drop(run.segment(3, y1), "y3")
-        yield "up2"
-        feats = run.segment(4, y3)
+        if run.rng is not None:
+            feats = run.segment(2, z1, middle)
+        else:
+            y1 = self._drop(run.segment(2, z1, middle), "y1")
+            y3 = self._drop(run.segment(3, y1), "y3")
+            yield "up2"
+            feats = run.segment(4, y3)
         yield "up4"
         self._keep_index(z, x0)
         return feats
@@ -393,6 +455,12 @@ class SPVCNN(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def _drop(self, feats, name):
+        if self._native_dropout_here():
+            site = ("y1", "y3").index(name)
+            if site == 0:
+                self._take_call_base()
+            seed, base = self._drop_last
+            return spf.dropout(feats, self.dropout.p, seed, (base + site) & _U64, inplace=True)
         if self.dropout_masks is not None and self.training:
             return feats * self.dropout_masks[name] / (1.0 - 0.3)
         return self.dropout(feats)
@@ -417,11 +485,14 @@ class SPVCNN(nn.Module):
         yield "voxelized"
         if trainer is not None:
             from ..native_train import Refused
+            rng = (self._drop_seed, (2 * self._drop_forwards) & _U64) if self._native_dropout_here() else None
             try:
-                run = trainer.begin(z, x0)
+                run = trainer.begin(z, x0) if rng is None else trainer.begin(z, x0, rng=rng)
             except Refused:
                 run = None        # refused before anything was launched: the per-op path below
             if run is not None:
+                if rng is not None:
+                    self._take_call_base()      # what `rng` holds: counted once the executor has taken the forward
                 return (yield from self._native_train_steps(run, z, x0, fuse_early, fuse_middle))
         x0 = self._stem(x0)
         z0 = voxel_to_point(x0, z, nearest=False)

@@ -26,7 +26,7 @@ PV = np.dtype([("vox_idx", _P), ("vox_counts", _P), ("vox_order", _P), ("vox_seg
                ("n_vox", "<i8"), ("level", "<i4"), ("reserved", "<i4")])
 
 LAYER_CONV_BN, LAYER_LINEAR_BN = 1, 2
-OP_CONV_BN, OP_LINEAR_BN, OP_VOXELIZE, OP_DEVOXELIZE, OP_CONCAT, OP_ADD, OP_ADD_EXT = 1, 2, 3, 4, 5, 6, 7
+OP_CONV_BN, OP_LINEAR_BN, OP_VOXELIZE, OP_DEVOXELIZE, OP_CONCAT, OP_ADD, OP_ADD_EXT, OP_DROPOUT = 1, 2, 3, 4, 5, 6, 7, 8
 ROUTE_ROWS = 4
 ROUTES = {spf._EMPTY: 0, spf._DIRECT: 1, spf._OSTAT: 2, spf._PAIRS: 3}
 SLOT_INPUT, SLOT_OUTPUT, SLOT_FIRST = 0, 1, 2
@@ -76,10 +76,14 @@ class Program:
         self.n_slots += 1
         return self.n_slots - 1
 
-    def _op(self, kind, seg, src, level, channels, layer=-1, map_=-1, src2=-1, relu=0, dst=None):
+    def _op(self, kind, seg, src, level, channels, layer=-1, map_=-1, src2=-1, relu=0, dst=None, reserved0=0):
         dst = self._slot() if dst is None else dst
-        self.ops.append((kind, seg, layer, map_, src, src2, dst, int(relu), level, channels, 0, 0))
+        self.ops.append((kind, seg, layer, map_, src, src2, dst, int(relu), level, channels, reserved0, 0))
         return dst
+
+    def dropout(self, seg, slot, level, channels, site, p):
+        """OP_DROPOUT in place on `slot` (the training program's alone): site number in `layer`, the float32 bits of p in reserved0."""
+        return self._op(OP_DROPOUT, seg, slot, level, channels, layer=site, dst=slot, reserved0=int(np.float32(p).view(np.int32)))
 
     def conv_bn(self, seg, conv, bn, src, level, residual=-1, relu=True):
         """-> (slot, level) of Conv3d -> BatchNorm (-> + residual) (-> ReLU), as models/spvcnn._conv_bn."""
@@ -131,11 +135,12 @@ class Program:
         return np.array(self.ops, dtype=OP)
 
 
-def emit_program(net, segments=(SEG_STEM, SEG_ENCODER, SEG_DECODER, SEG_DECODER, SEG_DECODER)) -> Program:
+def emit_program(net, segments=(SEG_STEM, SEG_ENCODER, SEG_DECODER, SEG_DECODER, SEG_DECODER), dropout=False) -> Program:
     """The forward of SPVCNN._backbone_steps from "voxelized" on, op by op in the order that method issues them.  `segments`: the
     segment number of the stem, of the encoder, of the voxelise that feeds the first Dropout (with the middle-fusion add in front of
     it), of the decoder up to the voxelise that feeds the second Dropout, and of the rest.  Dropout is the identity in eval mode, so the
-    eval program runs the last three as one; the training program (native_train.py) ends a segment at each."""
+    eval program runs the last three as one; the training program (native_train.py) ends a segment at each, or -- dropout=True, never for
+    eval -- holds an OP_DROPOUT (site 0 for y1, site 1 for y3, p of net.dropout) behind each of the two and runs in the same three."""
     P = Program()
     s_stem, s_enc, s_y1, s_dec, s_rest = segments
     cs = net.cs
@@ -160,6 +165,8 @@ def emit_program(net, segments=(SEG_STEM, SEG_ENCODER, SEG_DECODER, SEG_DECODER,
     # ---- decoder
     P._op(OP_ADD_EXT, s_y1, z1, POINTS, cs[4], layer=1, dst=z1)
     cur = P._op(OP_VOXELIZE, s_y1, z1, 4, cs[4], map_=pv[16])
+    if dropout:
+        P.dropout(s_y1, cur, 4, cs[4], 0, net.dropout.p)
 
     def up(seg, mod, cur, level, skip, o):
         cur, level = P.block(seg, mod[0], cur, level)
@@ -173,6 +180,8 @@ def emit_program(net, segments=(SEG_STEM, SEG_ENCODER, SEG_DECODER, SEG_DECODER,
     t = P.linear_bn_relu(s_dec, net.point_transforms[1], z1)
     z2 = P._op(OP_ADD, s_dec, z2v, POINTS, cs[6], src2=t)
     cur = P._op(OP_VOXELIZE, s_dec, z2, 2, cs[6], map_=pv[4])
+    if dropout:
+        P.dropout(s_dec, cur, 2, cs[6], 1, net.dropout.p)
     cur, level = up(s_rest, net.up3, cur, 2, skips[1], cs[7])
     cur, level = up(s_rest, net.up4, cur, level, skips[0], cs[8])
     z3v = P._op(OP_DEVOXELIZE, s_rest, cur, POINTS, cs[8], map_=pv[1])

@@ -1,7 +1,9 @@
 """Host side of the native training executor of the SPVCNN LiDAR branch (include/ftx.h: ftx_spvcnn_train_fwd / _bwd).
 
 The program is native_eval's (the same walk, records, tables and routes), cut into five segments: a segment ends at each of the two
-voxelisations that feed a Dropout, so Dropout stays torch's, with its RNG stream and the injected masks.  Each segment is ONE
+voxelisations that feed a Dropout, so Dropout stays torch's, with its RNG stream and the injected masks.  With the library's own
+counter-based Dropout (SPVCNN.set_native_dropout; include/ftx.h: ftx_dropout) the two are ops of the program instead, which then runs
+in the eval program's three segments through ftx_spvcnn_train_fwd_rng / _bwd_rng.  Each segment is ONE
 autograd node (`_Segment`): its forward is one library call, its backward one library call that walks the segment's ops in reverse
 and issues what the per-op nodes of functional.py issue.  Everything the backward reads lives in one arena per forward, allocated
 from torch's allocator and freed when the graph dies."""
@@ -21,6 +23,7 @@ from .native_eval import Unsupported, _P, _ptr
 TRAIN_LAYER = np.dtype([("dweight", _P), ("dbias", _P), ("dgamma", _P), ("dbeta", _P), ("momentum", "<f4"), ("reserved", "<i4")])
 TRAIN_PV = np.dtype([("devox_order", _P), ("devox_seg_off", _P)])
 SEGMENTS = (0, 1, 2, 3, 4)       # stem | encoder | z1 (+ middle addend) -> y1 | Dropout, up1, up2, z2 -> y3 | Dropout, up3, up4, z3
+SEGMENTS_DROPOUT = (0, 1, 2, 2, 2)      # SPVCNN.set_native_dropout: Dropout is an op of the program, so stem | encoder | decoder as in eval
 GRAD_FIELDS = ("dweight", "dbias", "dgamma", "dbeta")      # of the refs (weight, bias, gamma, beta) of a layer, in that order
 _K, _SEG, _LAYER, _MAP, _SRC, _SRC2, _DST, _RELU, _LEVEL, _CH = range(10)     # fields of an op tuple
 
@@ -54,13 +57,20 @@ def saved_slots(op):
 
 
 class TrainProgram:
-    """The training program of one SPVCNN: `program` (native_eval.Program with five segments), `backward` (the op indices in the order
+    """The training program of one SPVCNN: `program` (native_eval.Program with five segments, or -- native_dropout -- three and the two
+    Dropouts as ops), `backward` (the op indices in the order
     the backward issues them), `contributions` (per slot the ops whose backward writes its gradient), `grad_table` (per parameter where
     its gradient goes: (layer, field of TRAIN_LAYER, (dict, name) of the parameter)) and the per-segment views of these."""
 
-    def __init__(self, net):
-        self.program = P = ne.emit_program(net, segments=SEGMENTS)
-        self.n_segments = len(set(SEGMENTS))
+    def __init__(self, net, native_dropout=False):
+        self.native_dropout = bool(native_dropout)
+        if self.native_dropout:
+            self.segments = SEGMENTS_DROPOUT
+            self.program = P = ne.emit_program(net, segments=SEGMENTS_DROPOUT, dropout=True)
+        else:
+            self.segments = SEGMENTS
+            self.program = P = ne.emit_program(net, segments=SEGMENTS)
+        self.n_segments = len(set(self.segments))
         ops = P.ops
         self.backward = list(range(len(ops) - 1, -1, -1))
         self.contributions = {}
@@ -157,9 +167,9 @@ def _alias(storage, byte_offset, shape, device):
 class NativeTrain(ne._Host):
     """Per-module state of the training executor: the program and the model table.  Runs are per forward."""
 
-    def __init__(self, net):
+    def __init__(self, net, native_dropout=False):
         check_record_sizes()
-        self.tp = TrainProgram(net)
+        self.tp = TrainProgram(net, native_dropout)
         super().__init__(self.tp.program)
         self.runs = 0              # forwards this executor ran (the tests' witness)
         self.last_arena_bytes = 0
@@ -167,11 +177,14 @@ class NativeTrain(ne._Host):
     def trainable(self):
         return all(p.requires_grad for p in self.tp.parameters())
 
-    def begin(self, z, x0, arena=None):
+    def begin(self, z, x0, arena=None, rng=None):
         """Fill the tables of one batch and allocate its arena; raises Refused (nothing launched) for a batch the library does not take.
         arena (optional): nbytes -> a contiguous uint8 CUDA tensor of that many bytes, 256-byte aligned, to run in instead of a fresh
-        torch.empty -- a view into a larger buffer is fine (the tests' guard bands)."""
+        torch.empty -- a view into a larger buffer is fine (the tests' guard bands).
+        rng: (seed, call_base) of this forward's Dropout ops, for a program that holds them (SPVCNN.set_native_dropout), else None."""
         tp = self.tp
+        if tp.native_dropout != (rng is not None):
+            raise ValueError("native train: (seed, call_base) go with a program that holds Dropout ops, and only with it")
         try:
             layers = self.model_table()
         except Unsupported as e:
@@ -199,13 +212,14 @@ class NativeTrain(ne._Host):
                 raise ValueError(f"native train: the arena must be {need} bytes on {feats.device}, 256-byte aligned")
         self.runs += 1
         self.last_arena_bytes = need
-        return _Run(self, layers, tl, rows, maps, pvs, tpvs, routes, groutes, (kms, z, x0, segs), feats, arena)
+        return _Run(self, layers, tl, rows, maps, pvs, tpvs, routes, groutes, (kms, z, x0, segs), feats, arena, rng)
 
 
 class _Run:
     """One forward and its backward: the batch tables, the arena, and how far either direction has come."""
 
-    def __init__(self, ex, layers, tl, rows, maps, pvs, tpvs, routes, groutes, keep, feats, arena):
+    def __init__(self, ex, layers, tl, rows, maps, pvs, tpvs, routes, groutes, keep, feats, arena, rng=None):
+        self.rng = rng                # (seed, call_base): the backward recomputes the masks from the pair the forward drew with
         self.ex, self.layers, self.tl, self.rows, self.maps, self.pvs, self.tpvs = ex, layers, tl, rows, maps, pvs, tpvs
         self.routes, self.groutes, self.keep, self.feats, self.arena = routes, groutes, keep, feats, arena
         self.storage = arena.untyped_storage()
@@ -242,10 +256,11 @@ class _Run:
         where = ctypes.c_void_p()
         L = _lib.load()
         ops = self.ex.ops
-        _lib.check(L.ftx_spvcnn_train_fwd(_ptr(self.layers), _ptr(self.tl), len(self.layers), _ptr(ops), len(ops), _ptr(self.rows), _ptr(self.maps),
-                                          len(self.maps), _ptr(self.pvs), len(self.pvs), _ptr(self.routes), _ptr(self.groutes), seg, seg, x.data_ptr(),
-                                          _lib.ptr(addend) if seg == 1 else None, _lib.ptr(addend) if seg == 2 else None, self.base,
-                                          self.arena.shape[0], _lib.ptr(out), ctypes.byref(where), spf._stream_scratch()), "ftx_spvcnn_train_fwd")
+        entry, rng = ("ftx_spvcnn_train_fwd", ()) if self.rng is None else ("ftx_spvcnn_train_fwd_rng", self.rng)
+        _lib.check(getattr(L, entry)(_ptr(self.layers), _ptr(self.tl), len(self.layers), _ptr(ops), len(ops), _ptr(self.rows), _ptr(self.maps),
+                                     len(self.maps), _ptr(self.pvs), len(self.pvs), _ptr(self.routes), _ptr(self.groutes), seg, seg, x.data_ptr(),
+                                     _lib.ptr(addend) if seg == 1 else None, _lib.ptr(addend) if seg == 2 else None, self.base,
+                                     self.arena.shape[0], _lib.ptr(out), ctypes.byref(where), spf._stream_scratch(), *rng), entry)
         self.forward_done = seg
         if last:
             self.backward_next = seg
@@ -267,10 +282,11 @@ class _Run:
         L = _lib.load()
         ops = self.ex.ops
         self.backward_next = -1       # whatever happens below, this run is consumed from here
-        _lib.check(L.ftx_spvcnn_train_bwd(_ptr(self.layers), _ptr(self.tl), len(self.layers), _ptr(ops), len(ops), _ptr(self.rows), _ptr(self.maps),
-                                          len(self.maps), _ptr(self.pvs), _ptr(self.tpvs), len(self.pvs), _ptr(self.routes), _ptr(self.groutes), seg, seg,
-                                          x.data_ptr(), grad_out.data_ptr(), self.base, self.arena.shape[0], ctypes.byref(where), spf._stream_scratch()),
-                   "ftx_spvcnn_train_bwd")
+        entry, rng = ("ftx_spvcnn_train_bwd", ()) if self.rng is None else ("ftx_spvcnn_train_bwd_rng", self.rng)
+        _lib.check(getattr(L, entry)(_ptr(self.layers), _ptr(self.tl), len(self.layers), _ptr(ops), len(ops), _ptr(self.rows), _ptr(self.maps),
+                                     len(self.maps), _ptr(self.pvs), _ptr(self.tpvs), len(self.pvs), _ptr(self.routes), _ptr(self.groutes), seg, seg,
+                                     x.data_ptr(), grad_out.data_ptr(), self.base, self.arena.shape[0], ctypes.byref(where), spf._stream_scratch(), *rng),
+                   entry)
         self.backward_next = seg - 1
         grads = [g.view(e[3]) if len(e[3]) > 1 else g for g, e in zip(torch.split(flat, sp["sizes"]), sp["entries"])]
         gin = None

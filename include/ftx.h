@@ -657,6 +657,7 @@ int ftx_resize_bilinear_u8(const uint8_t *src, int64_t frame_stride, int64_t pit
 #define FTX_SPVCNN_OP_CONCAT 5
 #define FTX_SPVCNN_OP_ADD 6
 #define FTX_SPVCNN_OP_ADD_EXT 7
+#define FTX_SPVCNN_OP_DROPOUT 8 /* the training program's alone, see ftx_spvcnn_train_fwd_rng */
 #define FTX_SPVCNN_ROUTE_EMPTY 0
 #define FTX_SPVCNN_ROUTE_DIRECT 1
 #define FTX_SPVCNN_ROUTE_OSTAT 2
@@ -686,7 +687,8 @@ int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const void *ops_h
  * of 4, 16-byte accesses, n = 0 is a no-op.
  *
  * Tables: layer, op, map, pv, rows_host and routes_host as ftx_spvcnn_eval reads them (records unchanged), except that segments are
- * numbered 0 .. 7 without a gap (Dropout is the caller's: a segment ends where one follows) and every level needs at least one row.
+ * numbered 0 .. 7 without a gap and every level needs at least one row.  Dropout is either the caller's (a segment ends where one
+ * follows, and the caller hands the next segment what its Dropout returned) or an op of the program (FTX_SPVCNN_OP_DROPOUT, below).
  *   grad_routes_host: int32[n_ops], for every CONV_BN op with kvol > 1 whose input needs a gradient how the data gradient runs:
  *     FTX_SPVCNN_ROUTE_EMPTY (zero fill), _DIRECT or _PAIRS, the caller's choice as in routes_host (functional._conv_route(grad=True)).
  *     An op that reads FTX_SPVCNN_SLOT_INPUT computes no data gradient.
@@ -707,13 +709,55 @@ int ftx_spvcnn_eval(const void *layers_host, int32_t n_layers, const void *ops_h
  * temporaries: nothing the backward reads is written again while the caller keeps the arena.  The caller keeps it, unchanged, from the
  * first forward call of a step to its last backward call and runs the backward of the segments in descending order.
  * Every table is validated before the first launch.  No host synchronisation, no allocation, no state kept beyond the call; the
- * stream's ticket buffer (ftx_stream_scratch_attach) is the caller's as for the per-op entry points. */
+ * stream's ticket buffer (ftx_stream_scratch_attach) is the caller's as for the per-op entry points.
+ *
+ * Dropout as an op.  FTX_SPVCNN_OP_DROPOUT (training program only; ftx_spvcnn_eval refuses it: Dropout is the identity there) works in
+ * place on an arena slot that no op has read yet, like ADD_EXT: dst == src, level / channels those of the slot, layer = the site
+ * number s >= 0, reserved0 = the IEEE bits of p (0 <= p < 1).  The forward issues ftx_dropout (below) over the slot's rows x channels
+ * elements with call = call_base + s and elem0 = 0; the backward issues the same call on the slot's gradient buffer in place, so the op
+ * sends no gradient anywhere and adds no region to the arena.  A slot whose gradient is another buffer's (an operand of ADD, the result
+ * of a segment) is FTX_EINVAL.  (seed, call_base) are arguments of ftx_spvcnn_train_fwd_rng / ftx_spvcnn_train_bwd_rng, which are
+ * otherwise ftx_spvcnn_train_fwd / _bwd; nothing is kept between calls, so the backward is given the pair its forward was given.  The
+ * plain entries refuse a program that holds the op before their first launch.  With the op after the two voxelisations that feed
+ * SPVCNN's Dropouts the training program runs in the eval program's three segments. */
 int ftx_rows_split(const float *in, int64_t n, int32_t ca, int32_t cb, float *a, float *b, void *stream);
 int32_t ftx_spvcnn_train_layer_bytes(void);
 int32_t ftx_spvcnn_train_pv_bytes(void);
 size_t ftx_spvcnn_train_arena_bytes(const void *layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host);
 int ftx_spvcnn_train_fwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, float **seg_out, void *stream);
 int ftx_spvcnn_train_bwd(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, const void *train_pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in, void *stream);
+int ftx_spvcnn_train_fwd_rng(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in, const float *add_early, const float *add_middle, void *arena, size_t arena_bytes, float *out, float **seg_out, void *stream, uint64_t seed, uint64_t call_base);
+int ftx_spvcnn_train_bwd_rng(const void *layers_host, const void *train_layers_host, int32_t n_layers, const void *ops_host, int32_t n_ops, const int64_t *rows_host, const void *maps_host, int32_t n_maps, const void *pvs_host, const void *train_pvs_host, int32_t n_pvs, const int32_t *routes_host, const int32_t *grad_routes_host, int32_t first_segment, int32_t last_segment, const float *seg_in, const float *grad_out, void *arena, size_t arena_bytes, float **grad_in, void *stream, uint64_t seed, uint64_t call_base);
+
+/* ---- counter-based Dropout ----
+ * y[i] = x[i] * (keep(i) ? scale : 0.0f), one fp32 multiply per element: a product, not a select, so NaN or Inf in a dropped element
+ * gives NaN, as torch's input * mask * scale does.  The mask is a pure function of (seed, call, logical element index); it does not
+ * depend on the launch geometry, on the device or on any library version, and it is never stored: the backward is the same call on
+ * the gradient (dx = dy * mask * scale).
+ *
+ * The random stream (the contract; tests/dropout_ref.py restates it in numpy):
+ *   generator  Philox4x32-10: multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on word 2), key increments 0x9E3779B9 and
+ *              0xBB67AE85, ten rounds, the key bumped between rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3")
+ *   key        (seed & 0xffffffff, seed >> 32)
+ *   element    g = elem0 + i (uint64, wrapping), i the index into the buffer of this call; block q = g >> 2, lane j = g & 3
+ *   counter    (q & 0xffffffff, q >> 32, call & 0xffffffff, call >> 32)
+ *   u          word j of the ten-round output
+ *   threshold  thr = (uint32) floor((double) p * 2^32), scale = (float) (1.0 / (1.0 - (double) p)), both computed on the host
+ *   rule       keep iff u >= thr; p = 0 keeps everything with scale 1 and returns x bit for bit
+ * elem0 lets a tensor that is processed in pieces take the mask of the whole.  `call` numbers the draws of one seed: two calls with
+ * the same (seed, call) draw the same mask.  seed and call are by value, so a launch captured into a HIP graph repeats its mask on
+ * every replay.
+ *
+ * ftx_dropout: x, y (n) float32, 4-byte aligned; y == x (in place) is allowed, any other overlap is FTX_EINVAL.  0 <= p < 1, anything
+ * else (NaN included) is FTX_EINVAL before a launch.  n = 0 launches nothing.  Exactly n elements are written; no allocation, no
+ * synchronisation.  Where the logical index is a multiple of four at a 16-byte boundary of both buffers (elem0 % 4 == 0 and aligned
+ * pointers is the common case) four consecutive elements share one Philox block and one 16-byte load and store; the elements in
+ * front of and behind that range, and every element of a buffer aligned otherwise, take a scalar path with the same bits.
+ * ftx_dropout_mask: keep (n) uint8, 1 = kept, 0 = dropped, of the same stream.
+ * ftx_dropout_sweep_elements: the elements one sweep of the capped grid covers on the 16-byte path (a larger n grid-strides). */
+int64_t ftx_dropout_sweep_elements(void);
+int ftx_dropout(const float *x, int64_t n, float p, uint64_t seed, uint64_t call, uint64_t elem0, float *y, void *stream);
+int ftx_dropout_mask(int64_t n, float p, uint64_t seed, uint64_t call, uint64_t elem0, uint8_t *keep, void *stream);
 
 /* ---- native index build of the SPVCNN LiDAR branch: from raw points to the batch tables ftx_spvcnn_eval reads ----
  * Everything of a batch that depends on its coordinates only (SPVCNN._index_steps(ahead=True) in the Python package): the voxel sets of

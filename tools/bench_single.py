@@ -4,6 +4,8 @@ usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/s
        python tools/bench_single.py --image-stn [--steps 60] [--out profiles/image_stn_steps.json]   # only: ImageSeg beside ImageSegBilinear
        python tools/bench_single.py --native-index-ab [--steps 20]     # LidarSeg steps, native index build off / on, alternating windows
        python tools/bench_single.py --native-train-ab [--steps 20] [--ab-model LidarSeg|middle]   # the same for the training executor
+       python tools/bench_single.py --native-train-ab --dropout [--steps 20]   # LidarSeg with the training executor: torch's Dropout and five
+                                                                               # segments against the library's Dropout and three; then the kernel
        python tools/bench_single.py --native-image-train-ab [--steps 20]   # the ViT trunk in training: HIP graphs / eager / the native training executor
        python tools/bench_single.py --native-train-steps on|off --steps N     # N untimed batch-1 steps, to count launches under a kernel trace
        python tools/bench_single.py --lidar-split [--steps 20] [--out profiles/spconv_split_steps.json]   # LidarSeg steps, default against lidar_split
@@ -88,9 +90,9 @@ def _graph_nodes(t):
     return len(seen)
 
 
-def _switch_ab(switch, batch, steps, warmup, windows=5, model_kind="LidarSeg"):
-    """Step time with one switch of the SPVCNN (`set_<switch>`) off and on: two models from one seed in one process, windows of `steps`
-    steps alternating between them; median (min..max) ms per step, and per arm `host_issue_ms` (wall clock of the loop before the
+def _switch_ab(switch, batch, steps, warmup, windows=5, model_kind="LidarSeg", both=()):
+    """Step time with one switch of the SPVCNN (`set_<switch>`) off and on (the switches of `both` on in either arm): two models from one
+    seed in one process, windows of `steps` steps alternating between them; median (min..max) ms per step, and per arm `host_issue_ms` (wall clock of the loop before the
     synchronise, per step: an UPPER bound on the issue time, since it includes the blocking host reads of an index build that the
     prefetch did not finish), the autograd nodes under the LiDAR logits and the peak of torch's allocator above what was resident."""
     import time
@@ -104,6 +106,8 @@ def _switch_ab(switch, batch, steps, warmup, windows=5, model_kind="LidarSeg"):
         torch.manual_seed(0)
         model = build_model(cfg)[0].cuda().train()
         nets[mode] = model.backbone if model_kind == "LidarSeg" else model.lidar_backbone
+        for other in both:
+            getattr(nets[mode], "set_" + other)(True)
         getattr(nets[mode], "set_" + switch)(mode == "on")
         arms[mode] = TrainStep(cfg, model)
     info = {m: {} for m in arms}
@@ -142,9 +146,13 @@ def _switch_ab(switch, batch, steps, warmup, windows=5, model_kind="LidarSeg"):
     for m in arms:
         out[m] = dict(info[m], host_issue_ms=spread(info[m]["host_issue_ms"]))
     tr = getattr(nets["on"], "_native_tr", None)
-    if switch == "native_train" and tr:
+    if (switch == "native_train" or "native_train" in both) and tr:
         out["on"]["arena_bytes"] = int(tr.last_arena_bytes)
+        out["on"]["segments"] = int(tr.tp.n_segments)
+    if both:
+        out["on_in_both_arms"] = list(both)
     out["every_on_window_beats_every_off_window"] = bool(max(ms["on"]) < min(ms["off"]))
+    out["every_off_window_beats_every_on_window"] = bool(max(ms["off"]) < min(ms["on"]))
     return out
 
 
@@ -188,6 +196,46 @@ def native_index_ab(batch, steps, warmup, windows=5):
 def native_train_ab(batch, steps, warmup, windows=5, model_kind="LidarSeg"):
     """Step time with the native training executor (SPVCNN.set_native_train) off and on."""
     return _switch_ab("native_train", batch, steps, warmup, windows, model_kind)
+
+
+def native_dropout_ab(batch, steps, warmup, windows=5):
+    """LidarSeg step time with the training executor on in both arms: torch's Dropout between five segments (off) against the library's
+    Dropout as an op of three segments (SPVCNN.set_native_dropout, on).  A claim of faster or slower holds only where the windows do
+    not overlap (the two `every_..._window_beats_...` flags); otherwise no difference is shown."""
+    return _switch_ab("native_dropout", batch, steps, warmup, windows, "LidarSeg", both=("native_train",))
+
+
+def dropout_kernel_times(calls=CALLS, windows=WINDOWS):
+    """HIP-event time of ftx_dropout (functional.dropout outside autograd, out of place) beside torch.nn.functional.dropout on the same
+    tensors: the two Dropout sites of a KITTI-shaped batch of 4 (rows of the stride-16 level x 256 and of the stride-4 level x 128
+    channels), p = 0.3, windows of `calls` eager calls alternating between the two; us per call, median (min..max)."""
+    import numpy as np
+    import torch.nn.functional as F
+    from fusiontransformer_amd import functional as spf
+    from fusiontransformer_amd.data.synth import make_batch
+    coords = make_batch([1000 * 0 + i for i in range(4)])["coords"]
+    rows = lambda stride: len(np.unique(np.concatenate([coords[:, :3] // stride, coords[:, 3:]], 1), axis=0))
+    out = {"what": "dropout kernel", "p": 0.3, "calls_per_window": calls, "windows": windows, "unit": "us per call", "sites": []}
+    for site, (stride, ch) in enumerate(((16, 256), (4, 128))):
+        x = torch.randn(rows(stride), ch, device="cuda")
+        variants = {"ftx_dropout": lambda c: spf.dropout(x, 0.3, 1, c), "torch_dropout": lambda c: F.dropout(x, 0.3, True)}
+        us = {k: [] for k in variants}
+        with torch.no_grad():
+            for w in range(windows + 1):          # the first window warms up
+                for name, fn in variants.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for c in range(calls):
+                        fn(c)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if w:
+                        us[name].append(e0.elapsed_time(e1) * 1e3 / calls)
+        r = {"site": site, "shape": list(x.shape), "bytes_moved": 8 * x.numel()}
+        for name, v in us.items():
+            r[name] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+        out["sites"].append(r)
+    return out
 
 
 def native_image_train_ab(batch, steps, warmup, windows=5, model_kind="ImageSegBilinear"):
@@ -366,6 +414,8 @@ def main():
                     help="with --image-stn: what runs ImageSeg's localisation nets (cfg.MODEL.stn_loc_impl); both = one after the other")
     ap.add_argument("--native-index-ab", action="store_true", help="only: LidarSeg step time with SPVCNN.set_native_index off / on, batch 1 and 4")
     ap.add_argument("--native-train-ab", action="store_true", help="only: step time with SPVCNN.set_native_train off / on, batch 1 and 4")
+    ap.add_argument("--dropout", action="store_true", help="with --native-train-ab: the executor on in both arms, torch's Dropout / five segments "
+                                                           "against SPVCNN.set_native_dropout / three segments, batch 1 and 4; then the kernel's time")
     ap.add_argument("--ab-model", default="LidarSeg", choices=["LidarSeg", "middle"], help="the model of --native-train-ab")
     ap.add_argument("--native-image-train-ab", action="store_true",
                     help="only: ImageSegBilinear and middle-fusion step time, vit_linear_impl=ftx_split, trunk as HIP graphs / eager / native training "
@@ -375,6 +425,11 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_single: needs a GPU (there is no fallback)")
+    if args.native_train_ab and args.dropout:
+        for batch in (1, 4):
+            print(json.dumps(native_dropout_ab(batch, args.steps, args.warmup)), flush=True)
+        print(json.dumps(dropout_kernel_times()), flush=True)
+        return
     if args.native_train_ab:
         for batch in (1, 4):
             print(json.dumps(native_train_ab(batch, args.steps, args.warmup, model_kind=args.ab_model)), flush=True)
