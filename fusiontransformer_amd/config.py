@@ -67,7 +67,14 @@ def get_cfg_defaults() -> CfgNode:
             # the LiDAR branch's Dropout from the library's counter-based stream instead of torch's (SPVCNN.set_native_dropout)
             "lidar_native_dropout": False,
         },
-        "OPTIMIZER": {"TYPE": "", "BASE_LR": 0.001, "WEIGHT_DECAY": 0.0, "Adam": {"betas": (0.9, 0.999)}},
+        # OPTIMIZER.<TYPE> is passed to the optimizer as keyword arguments (common/solver/build.py:13-18).  MAX_GRAD_NORM > 0: max-norm
+        # gradient clipping fused into the step of the package's own optimizers; native: "SGD" / "AdamW" from fusiontransformer_amd.optim
+        # instead of torch.optim ("Adam" always is, on the GPU)
+        "OPTIMIZER": {"TYPE": "", "BASE_LR": 0.001, "WEIGHT_DECAY": 0.0, "SGD": {"momentum": 0.9, "dampening": 0.0},
+                      "Adam": {"betas": (0.9, 0.999)}, "MAX_GRAD_NORM": 0.0, "native": False},
+        # common/config/base.py:61-75; trainer.build_scheduler
+        "SCHEDULER": {"TYPE": "", "MAX_EPOCH": 1, "CLIP_LR": 0.0, "StepLR": {"step_size": 0, "gamma": 0.1},
+                      "MultiStepLR": {"milestones": (), "gamma": 0.1}},
         "TRAIN": {"BATCH_SIZE": 0, "CLASS_WEIGHTS": [], "FusionTransformer": {"lambda_xm": 0.0}},
         "DATALOADER": {"NUM_WORKERS": 0, "DROP_LAST": True},
     })

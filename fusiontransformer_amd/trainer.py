@@ -49,22 +49,100 @@ def fusion_losses(preds, seg_label, class_weights, lambda_xm, dual_head, mix="ad
 
 
 def build_optimizer(cfg, model):
-    """common/solver/build.py:7-20: getattr(torch.optim, TYPE)(params, lr, weight_decay)."""
+    """common/solver/build.py:7-20: getattr(torch.optim, TYPE)(params, lr, weight_decay, **cfg.OPTIMIZER.<TYPE>).
+
+    On the GPU "Adam" is fusiontransformer_amd.optim.Adam (torch.optim.Adam's rule and state layout, one libftx launch), and
+    cfg.OPTIMIZER.native routes "SGD" and "AdamW" to the package's own classes too.  cfg.OPTIMIZER.MAX_GRAD_NORM > 0 asks for max-norm
+    gradient clipping fused into the step (optim.py): it implies `native` for those two and is an error for every other TYPE."""
+    opt = cfg.OPTIMIZER
     params = [p for p in model.parameters() if p.requires_grad]
-    kwargs = dict(lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY)
+    kwargs = dict(lr=opt.BASE_LR, weight_decay=opt.WEIGHT_DECAY, **dict(opt.get(opt.TYPE) or {}))
+    max_norm = float(opt.get("MAX_GRAD_NORM", 0.0) or 0.0)
     on_gpu = bool(params) and params[0].is_cuda
-    if cfg.OPTIMIZER.TYPE == "Adam" and on_gpu:
-        from .optim import Adam      # torch.optim.Adam's rule and state layout, stepped by one libftx launch (csrc/ftx_optim.hip)
-        return Adam(params, **kwargs)
-    if cfg.OPTIMIZER.TYPE == "AdamW" and on_gpu:
-        kwargs["fused"] = True  # same update rule, one multi-tensor kernel instead of ~10 passes over 108 M parameters
-    return getattr(torch.optim, cfg.OPTIMIZER.TYPE)(params, **kwargs)
+    own = opt.TYPE == "Adam" and (on_gpu or max_norm > 0) or opt.TYPE in ("SGD", "AdamW") and (bool(opt.get("native", False)) or max_norm > 0)
+    if max_norm > 0 and not own:
+        raise ValueError("OPTIMIZER.MAX_GRAD_NORM is supported for TYPE 'Adam', 'AdamW' and 'SGD', not for %r" % (opt.TYPE,))
+    if own:
+        from . import optim      # torch.optim's rules and state layouts, stepped by one libftx launch each (csrc/ftx_optim.hip)
+        if max_norm > 0:
+            kwargs["max_grad_norm"] = max_norm
+        return getattr(optim, opt.TYPE)(params, **kwargs)
+    if opt.TYPE == "AdamW" and on_gpu:
+        kwargs.setdefault("fused", True)  # same update rule, one multi-tensor kernel instead of ~10 passes over 108 M parameters
+    return getattr(torch.optim, opt.TYPE)(params, **kwargs)
+
+
+class WarmupMultiStepLR(torch.optim.lr_scheduler.LRScheduler):
+    """common/solver/lr_scheduler.py:6-50: MultiStepLR behind a warm-up.  While last_epoch < warmup_steps the rate is multiplied by
+    warmup_factor ("constant") or by the line from warmup_factor at step 0 to 1 at warmup_steps ("linear"); throughout,
+    lr = base_lr * warm-up * gamma ** (number of milestones <= last_epoch)."""
+
+    def __init__(self, optimizer, milestones, gamma=0.1, warmup_factor=0.1, warmup_steps=1, warmup_method="linear", last_epoch=-1):
+        if list(milestones) != sorted(milestones):
+            raise ValueError("milestones must be increasing, got %r" % (milestones,))
+        if warmup_method not in ("constant", "linear"):
+            raise ValueError("warmup_method must be 'constant' or 'linear', got %r" % (warmup_method,))
+        self.milestones, self.gamma = list(milestones), gamma
+        self.warmup_factor, self.warmup_steps, self.warmup_method = warmup_factor, warmup_steps, warmup_method
+        super().__init__(optimizer, last_epoch)
+
+    def get_lr(self):
+        import bisect
+        warm = 1
+        if self.last_epoch < self.warmup_steps:
+            if self.warmup_method == "constant":
+                warm = self.warmup_factor
+            else:
+                alpha = float(self.last_epoch) / self.warmup_steps
+                warm = self.warmup_factor * (1 - alpha) + alpha
+        decay = self.gamma ** bisect.bisect_right(self.milestones, self.last_epoch)
+        return [base * warm * decay for base in self.base_lrs]
+
+
+class ClipLR:
+    """common/solver/lr_scheduler.py:53-75, kept faithful: what `get_lr()` REPORTS is max(min_lr, lr); everything else -- `step()`,
+    `state_dict()`, `last_epoch`, ... -- is the wrapped scheduler's.  So the optimizer's own rate follows the wrapped scheduler and is
+    NOT clipped; a caller who wants the rate itself bounded has to bound it in the scheduler."""
+
+    def __init__(self, scheduler, min_lr=1e-5):
+        if not isinstance(scheduler, torch.optim.lr_scheduler.LRScheduler):
+            raise TypeError("ClipLR wraps a torch.optim.lr_scheduler.LRScheduler")
+        self.scheduler = scheduler
+        self.min_lr = min_lr
+
+    def get_lr(self):
+        return [max(self.min_lr, lr) for lr in self.scheduler.get_lr()]
+
+    def __getattr__(self, name):
+        if name == "scheduler":      # not set yet (unpickling): nothing to forward to
+            raise AttributeError(name)
+        return getattr(self.scheduler, name)
+
+
+def build_scheduler(cfg, optimizer):
+    """common/solver/build.py:23-41: '' builds nothing (with a warning); a name in torch.optim.lr_scheduler is built with
+    cfg.SCHEDULER.<TYPE> as keyword arguments, so is this module's WarmupMultiStepLR; CLIP_LR > 0 wraps the result in ClipLR."""
+    import warnings
+    sch = cfg.SCHEDULER
+    name = sch.TYPE
+    if name == "":
+        warnings.warn("No scheduler is built.")
+        return None
+    kind = WarmupMultiStepLR if name == "WarmupMultiStepLR" else getattr(torch.optim.lr_scheduler, name, None)
+    if kind is None:
+        raise ValueError("Unsupported type of scheduler: %r" % (name,))
+    scheduler = kind(optimizer, **dict(sch.get(name) or {}))
+    if sch.get("CLIP_LR", 0.0) > 0.0:
+        scheduler = ClipLR(scheduler, min_lr=sch.CLIP_LR)
+    return scheduler
 
 
 class TrainStep:
-    def __init__(self, cfg, model, optimizer=None, metrics=None, grad_reducer=None, loss_mix="additive"):
+    def __init__(self, cfg, model, optimizer=None, metrics=None, grad_reducer=None, loss_mix="additive", scheduler=None):
         """loss_mix="additive": SemanticTrainer.train_step (the single-process trainer); "torchpack": the DDP trainer's mix and its
-        default class weights (SemanticTorchpackTrainer.py:28-32,70-106) -- the one BASELINE configs[3] / [4] follow."""
+        default class weights (SemanticTorchpackTrainer.py:28-32,70-106) -- the one BASELINE configs[3] / [4] follow.
+        scheduler (build_scheduler's result, optional): stepped once per training step, after the optimizer -- the reference's
+        per-iteration placement (SemanticTrainer.py:202-217)."""
         if loss_mix not in ("additive", "torchpack"):
             raise ValueError("loss_mix must be 'additive' or 'torchpack'")
         self.cfg, self.model, self.loss_mix = cfg, model, loss_mix
@@ -85,6 +163,7 @@ class TrainStep:
             metrics = (metrics,)       # build_model returns one bare SegIoU for the single-modality models
         self.metrics = metrics or ()
         self.grad_reducer = grad_reducer
+        self.scheduler = scheduler
         self.fused_loss = True
         self.prefetch_wait = False     # next_batch: start its index build without blocking this thread (SPVCNN.prepare(wait=False))
         self.prefetch_budget_ms = 1.5  # ... then poll its host reads this long at most
@@ -180,6 +259,8 @@ class TrainStep:
             from .models._fusion_common import prepare_batch
             prepare_batch(self.model, next_batch, ready=ready, wait=self.prefetch_wait)
         self.optimizer.step()
+        if self.scheduler is not None:
+            self.scheduler.step()
         if next_batch is not None and not self.prefetch_wait:
             # Small batches: the build's host reads arrive within a fraction of a millisecond, so a short bounded poll gets the whole
             # build issued before the next forward starts (batch 1: 14.9 -> 13.8 ms per step).  Large batches: they do not -- the small

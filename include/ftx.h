@@ -386,6 +386,38 @@ int32_t ftx_adam_chunk_elements(void);
 int32_t ftx_adam_tensor_bytes(void);
 int ftx_adam_step(const void *table, const int32_t *chunk_tensor, const int64_t *chunk_offset, int32_t n_chunks, double beta1, double beta2, float eps, float weight_decay, void *stream);
 
+/* ---- the rest of the solver: AdamW, SGD and max-norm gradient clipping, over the same table and chunk map ----
+ * Every entry below reads records of ftx_adam_tensor_bytes() bytes and the chunk_tensor / chunk_offset map of ftx_adam_step; a record
+ * whose grad is NULL is skipped by the update rules and counts as zeros in the norm.
+ *
+ * grad_scale (device, one float, may be NULL): every gradient element is replaced by g * *grad_scale (one rounding) before anything
+ * else.  NULL, or a device 1.0f, leaves the bits of the unscaled entry.  It is read on the device by the launch itself: pass
+ * out + 1 of ftx_grad_norm_finalize and no value crosses to the host between the norm and the update.  The gradients in memory
+ * are NOT rewritten.
+ *
+ * ftx_adam_step_scaled: ftx_adam_step with grad_scale.
+ * ftx_adamw_step: torch.optim.AdamW.  Same record as Adam; per element p *= (float)(1 - lr * weight_decay) (formed in double), then
+ *   Adam's update without the L2 term.  step_size in the record already holds lr / (1 - beta1^t); lr is passed for the decay alone.
+ * ftx_sgd_step: torch.optim.SGD.  The record's fields are read as
+ *   float *param; float *momentum_buffer (NULL when momentum == 0); void *unused; const float *grad; int64 numel; int32 first; int32 pad.
+ *   g += wd*p; buf = first ? g : momentum*buf + (1 - dampening)*g; g = nesterov ? g + momentum*buf : buf; p -= lr*g.
+ *   first != 0 marks a tensor's first step WITH a gradient: the buffer is written and not read (it may be uninitialised).  The caller
+ *   keeps `first` set for a tensor until a step in which it had a gradient.  momentum == 0 reads and writes no buffer.  With
+ *   momentum != 0 a record whose buffer is NULL is skipped.  nesterov needs momentum > 0 and dampening == 0, as in torch.
+ *
+ * ftx_grad_sumsq: partial[c] (n_chunks float64, every element written by every launch) = the sum of the squares of chunk c's gradient
+ *   elements, each squared and accumulated in float64 in an order that depends on (chunk offset, position in the chunk) only -- not
+ *   on the gradient's alignment; 0.0 for a chunk of a tensor without a gradient.  Several tables (parameter groups) write consecutive
+ *   ranges of one partial buffer.  No atomics: two launches on the same input give the same bits.
+ * ftx_grad_norm_finalize: one block sums the partials in float64 in an order fixed by n_partials and writes two floats:
+ *   out[0] = (float)sqrt(total), out[1] = min(1, max_norm / (out[0] + 1e-6f)) in float32 -- torch.nn.utils.clip_grad_norm_ with
+ *   error_if_nonfinite=False: a NaN norm gives a NaN coefficient, an infinite norm 0.  n_partials == 0: (0, 1).  max_norm > 0. */
+int ftx_adam_step_scaled(const void *table, const int32_t *chunk_tensor, const int64_t *chunk_offset, int32_t n_chunks, double beta1, double beta2, float eps, float weight_decay, const float *grad_scale, void *stream);
+int ftx_adamw_step(const void *table, const int32_t *chunk_tensor, const int64_t *chunk_offset, int32_t n_chunks, double beta1, double beta2, float eps, double lr, double weight_decay, const float *grad_scale, void *stream);
+int ftx_sgd_step(const void *table, const int32_t *chunk_tensor, const int64_t *chunk_offset, int32_t n_chunks, double lr, double momentum, double dampening, double weight_decay, int32_t nesterov, const float *grad_scale, void *stream);
+int ftx_grad_sumsq(const void *table, const int32_t *chunk_tensor, const int64_t *chunk_offset, int32_t n_chunks, double *partial, void *stream);
+int ftx_grad_norm_finalize(const double *partial, int64_t n_partials, float max_norm, float *out, void *stream);
+
 /* ---- LayerNorm of the ViT blocks, fused with the residual add in front of it (timm Block.forward: models/transformers.py:16-45) ----
  * forward: s = x + y (y may be NULL: then s_out is not written and s = x), h = (s - mean) * rstd * gamma + beta over rows of c floats,
  * c in {256, 512, 768, 1024}; mean / rstd (rows) are outputs for the backward.  y_bias (c, may be NULL): y is the output of a Linear
