@@ -187,6 +187,16 @@ SIGNATURES = {
     "ftx_vit_tap_stem_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ftx_vit_tap_stem_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ftx_rows_add_bias": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "ftx_vit_patch_embed_bwd_split_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "ftx_vit_patch_embed_bwd_bf16_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "ftx_vit_patch_embed_bwd_split": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ftx_vit_patch_embed_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ftx_vit_tap_stem_train_fwd_split": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_vit_tap_stem_train_fwd_bf16": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ftx_vit_tap_stem_bwd_split_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "ftx_vit_tap_stem_bwd_bf16_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "ftx_vit_tap_stem_bwd_split": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ftx_vit_tap_stem_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ftx_vit_model_bytes": (_i32, []),
     "ftx_vit_block_bytes": (_i32, []),
     "ftx_vit_tap_bytes": (_i32, []),

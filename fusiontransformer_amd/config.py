@@ -66,6 +66,8 @@ def get_cfg_defaults() -> CfgNode:
             "lidar_bf16": False, "lidar_split": False,
             # the LiDAR branch's Dropout from the library's counter-based stream instead of torch's (SPVCNN.set_native_dropout)
             "lidar_native_dropout": False,
+            # the ViT's patch embedding and tap stems in training on the library's own forms (Image2DTransformer.set_native_stems)
+            "image_native_stems": False,
         },
         # OPTIMIZER.<TYPE> is passed to the optimizer as keyword arguments (common/solver/build.py:13-18).  MAX_GRAD_NORM > 0: max-norm
         # gradient clipping fused into the step of the package's own optimizers; native: "SGD" / "AdamW" from fusiontransformer_amd.optim

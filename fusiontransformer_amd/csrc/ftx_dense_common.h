@@ -10,9 +10,11 @@
 // The kernels do not ask which family they serve.  What needs a single definition (the rules, dense_wgrad_reduce_kernel,
 // dense_tokens_head_kernel, the plain entries) is defined in ftx_dense_common.hip.
 //
-// Where the rows of A live and what happens to a finished sum is a policy of the GEMM kernel (DenseRows, DensePatches, DenseTapRows
-// below): the tile rule, the staging, the MFMA order and the reduction order do not depend on it, so a form returns the bits of the
-// plain entry run on a materialised copy of its A.
+// Where the rows of A live and what happens to a finished sum is a policy of the GEMM kernel (DenseRows, DensePatches, DenseTapRows,
+// DenseTapReluRows, DenseStripFold below): the tile rule, the staging, the MFMA order and the reduction order do not depend on it, so a
+// form returns the bits of the plain entry run on a materialised copy of its A.  The weight-gradient kernel takes the same kind of
+// policy for each of its two operands (the same forms, and DenseReluMaskedRows); the training forms of the patch embedding and the tap
+// stems are built from them.
 #pragma once
 #include "ftx_bn_eval_op.h"
 #include "ftx_common.h"
@@ -119,6 +121,76 @@ struct DenseTapRows {
     *(float4 *)&out[m * N + n] = make_float4(o[0], o[1], o[2], o[3]);
   }
 };
+
+// The tap stem in training: DenseTapRows' rows, and the epilogue stops behind the ReLU: rows (b G, N) = ReLU(sum + bias).  The batch
+// statistics of the BatchNorm behind it need every row, so it stays a pass of its own (ftx_bn_train_fwd on `rows`).
+struct DenseTapReluRows {
+  const float *tokens;
+  int K, G, T0;
+  __device__ const float *row(int64_t r) const {
+    const int64_t f = r / G;
+    return tokens + (f * (T0 + G) + T0 + (r - f * G)) * K;
+  }
+  __device__ int64_t koff(int k) const { return k; }
+  template <int EPI>
+  __device__ void store(float4 v, int64_t m, int n, int N, const float *__restrict__ bias, const float *__restrict__, float *__restrict__ out,
+                        float *__restrict__) const {
+    const float4 b = *(const float4 *)&bias[n];
+    float o[4] = {v.x + b.x, v.y + b.y, v.z + b.z, v.w + b.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = o[e] < 0.f ? 0.f : o[e];   // nn.ReLU: NaN stays NaN
+    *(float4 *)&out[m * N + n] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+};
+
+// The patch embedding's image gradient: A is the gradient of the tokens (b, T0 + G, K) behind its T0 leading rows (the strip), the sum
+// is row (frame, gy, gx), column n = (c, py, px) of the unfold's gradient.  The patches do not overlap, so the fold is a permuted
+// store: out = dimg (b, C, H, W), every pixel written exactly once, P % 4 == 0 keeps a float4 inside one px run.
+struct DenseStripFold {
+  const float *dtokens;
+  int K, C, H, W, P, gw, G, T0;
+  __device__ const float *row(int64_t r) const {
+    const int64_t f = r / G;
+    return dtokens + (f * (T0 + G) + T0 + (r - f * G)) * K;
+  }
+  __device__ int64_t koff(int k) const { return k; }
+  template <int EPI>
+  __device__ void store(float4 v, int64_t m, int n, int, const float *__restrict__, const float *__restrict__, float *__restrict__ out,
+                        float *__restrict__) const {
+    const int64_t f = m / G;
+    const int g = (int)(m - f * G), gy = g / gw, gx = g - gy * gw;
+    const int c = n / (P * P), rem = n - c * P * P, py = rem / P, px = rem - py * P;
+    *(float4 *)&out[((f * C + c) * H + (int64_t)gy * P + py) * W + gx * P + px] = v;
+  }
+};
+
+// ---------------------------------------------------------------------------------------
+// device: the operand forms of the weight-gradient kernel.  Both operands are read along their channels, row r of the reduction at a
+// time; a form answers row(r) (r < M, already clamped) and koff(c), the offset of channel c (a multiple of 4, four contiguous floats)
+// from that start.  The A-forms above serve: DenseRows is the plain (M, channels) matrix, DensePatches the unfold of an image (X of
+// the patch embedding), DenseTapRows the rows of a (b, T0 + G, channels) buffer behind the T0 leading rows of every frame (X of the
+// tap stem, G of the patch embedding).  dense_load4 is the one read; a form may give it an overload.
+// ---------------------------------------------------------------------------------------
+template <class Form>
+__device__ inline float4 dense_load4(const Form &f, int64_t r, int c) {
+  return *(const float4 *)(f.row(r) + f.koff(c));
+}
+
+// G of the tap stem: the gradient of the BatchNorm's input, (M, N) plain rows, times the ReLU's mask taken from the saved output Y
+// (M, N).  A select, not a product: g where y > 0, else 0 (also where y is NaN), so the sums are those of the plain entry run on the
+// materialised masked gradient (dense_relu_mask_kernel writes that one for the bias gradient and the data gradient).
+struct DenseReluMaskedRows {
+  const float *G, *Y;
+  int N;
+  __device__ const float *row(int64_t r) const { return G + r * N; }
+  __device__ int64_t koff(int c) const { return c; }
+};
+__device__ inline float4 dense_relu_mask4(float4 g, float4 y) {
+  return make_float4(y.x > 0.f ? g.x : 0.f, y.y > 0.f ? g.y : 0.f, y.z > 0.f ? g.z : 0.f, y.w > 0.f ? g.w : 0.f);
+}
+__device__ inline float4 dense_load4(const DenseReluMaskedRows &f, int64_t r, int c) {
+  return dense_relu_mask4(*(const float4 *)&f.G[r * f.N + c], *(const float4 *)&f.Y[r * f.N + c]);
+}
 
 // ---------------------------------------------------------------------------------------
 // host: the rules, functions of the shape alone (ftx_dense_*_tile reports them)
@@ -343,10 +415,11 @@ __global__ __launch_bounds__(256, P::MIN_BLOCKS) void dense_gemm_kernel(const AF
 // write (the register stage of pairs_wgrad_bf16_kernel).  Rows past the split are zeroed on the block-uniform last step.
 // A split count of 1 writes dW directly; otherwise each split writes its own (N x K) partial and dense_wgrad_reduce_kernel adds them.
 // ---------------------------------------------------------------------------------------
-template <class P>
-__global__ __launch_bounds__(256, P::MIN_BLOCKS) void dense_wgrad_kernel(const float *__restrict__ G, const float *__restrict__ X, int64_t M, int N,
-                                                                         int K, int64_t split_len, float *__restrict__ part,
-                                                                         float *__restrict__ dW) {
+// GF and XF say where the rows of G and X live (the forms above); nothing else here depends on them, so every pair of forms sums the
+// same products in the same order as the plain entry on materialised operands.
+template <class P, class GF, class XF>
+__global__ __launch_bounds__(256, P::MIN_BLOCKS) void dense_wgrad_kernel(const GF gf, const XF xf, int64_t M, int N, int K, int64_t split_len,
+                                                                         float *__restrict__ part, float *__restrict__ dW) {
   constexpr int T = kDenseDwTile;
   constexpr int ITEMS = DenseStage<P>::pair_items(T);   // (row pair, float4) items per thread and operand
   constexpr int IMG = T * P::STRIDE;
@@ -388,8 +461,8 @@ __global__ __launch_bounds__(256, P::MIN_BLOCKS) void dense_wgrad_kernel(const f
       for (int h = 0; h < 2; ++h) {
         int64_t r = r0 + 2 * rp[q] + h;
         r = r < M ? r : M - 1;
-        rg[q][h] = *(const float4 *)&G[r * N + gcol[q]];
-        rx[q][h] = *(const float4 *)&X[r * K + xcol[q]];
+        rg[q][h] = dense_load4(gf, r, gcol[q]);
+        rx[q][h] = dense_load4(xf, r, xcol[q]);
       }
   };
   auto store_step = [&](int64_t r0) {
@@ -512,15 +585,16 @@ int dense_gemm_entry(const float *A, const float *W, int32_t w_kn, const float *
   return check_launch(me);
 }
 
-// A GEMM on a form other than DenseRows: W (n, k) as nn.Linear stores it, the form's own epilogue, the tile of dense_gemm_tile(m, n).
-template <class F, class Form>
+// A GEMM on a form other than DenseRows: W (n, k) as nn.Linear stores it (or, WKN, stored (k, n): a data gradient), the form's own
+// epilogue, the tile of dense_gemm_tile(m, n).
+template <class F, class Form, int EPI = FTX_EPI_BIAS, bool WKN = false>
 void dense_launch_form(const Form &form, const DenseGemmArgs &a, hipStream_t st) {
   int mi, ni;
   dense_gemm_tile(a.M, a.N, &mi, &ni);
   const dim3 grid((unsigned)ceil_div(a.N, 64 * ni), (unsigned)ceil_div(a.M, 64 * mi));
-  if (mi == 2) dense_launch<F, 2, 2, FTX_EPI_BIAS, false>(grid, st, form, a);
-  else if (ni == 2) dense_launch<F, 1, 2, FTX_EPI_BIAS, false>(grid, st, form, a);
-  else dense_launch<F, 1, 1, FTX_EPI_BIAS, false>(grid, st, form, a);
+  if (mi == 2) dense_launch<F, 2, 2, EPI, WKN>(grid, st, form, a);
+  else if (ni == 2) dense_launch<F, 1, 2, EPI, WKN>(grid, st, form, a);
+  else dense_launch<F, 1, 1, EPI, WKN>(grid, st, form, a);
 }
 
 // tokens[f][0] = cls + pos[0], tokens[f][1] = dist + pos[1] (T0 = 2): the rows in front of the patches (dense_tokens_head_kernel)
@@ -572,6 +646,17 @@ int dense_tap_stem_entry(const float *tokens, const float *W, const float *bias,
   return check_launch(me);
 }
 
+// The weight gradient on a pair of forms, m >= 1 rows: the split rule of dense_wgrad_split_len(m, n, k); `part` holds
+// dense_wgrad_partial_bytes of it (unused with one split).
+template <class F, class GF, class XF>
+void dense_wgrad_launch(const GF &gf, const XF &xf, int64_t m, int n, int k, float *dW, float *part, hipStream_t st) {
+  int splits;
+  const int64_t len = dense_wgrad_split_len(m, n, k, &splits);
+  const dim3 grid((unsigned)ceil_div(k, kDenseDwTile), (unsigned)ceil_div(n, kDenseDwTile), (unsigned)splits);
+  dense_wgrad_kernel<F, GF, XF><<<grid, 256, 0, st>>>(gf, xf, m, n, k, len, part, dW);
+  if (splits > 1) dense_wgrad_reduce(part, splits, (int64_t)n * k / 4, dW, st);
+}
+
 // A split count of 1 writes dW directly; otherwise each split writes its own (N x K) partial into the workspace and they are added in
 // split order.
 template <class F>
@@ -594,13 +679,151 @@ int dense_wgrad_entry(const float *G, const float *X, int64_t m, int32_t n, int3
   }
   FTX_REQUIRE(G && X, "%s: null pointer", me);
   int splits;
-  const int64_t len = dense_wgrad_split_len(m, n, k, &splits);
+  dense_wgrad_split_len(m, n, k, &splits);
   const size_t need = dense_wgrad_partial_bytes(splits, n, k);
   if (need > 0 && (!workspace || workspace_bytes < need)) return workspace_short(me, workspace_bytes, need);
-  float *part = (float *)workspace;
-  const dim3 grid((unsigned)ceil_div(k, kDenseDwTile), (unsigned)ceil_div(n, kDenseDwTile), (unsigned)splits);
-  dense_wgrad_kernel<F><<<grid, 256, 0, st>>>(G, X, m, n, k, len, part, dW);
-  if (splits > 1) dense_wgrad_reduce(part, splits, (int64_t)n * k / 4, dW, st);
+  dense_wgrad_launch<F>(DenseRows{G, n}, DenseRows{X, k}, m, n, k, dW, (float *)workspace, st);
+  return check_launch(me);
+}
+
+// ---------------------------------------------------------------------------------------
+// host: the training forms of the patch embedding and the tap stems (include/ftx.h states the contracts).  Each entry validates all
+// of its arguments, its workspace included, before its first launch; the pieces of a workspace start on 256-byte boundaries.
+// ---------------------------------------------------------------------------------------
+// dpos (t0 + g, dim) = the sum over the frames, ascending, of dtokens (b, t0 + g, dim); rows 0 and 1 also to dcls and ddist
+void dense_frames_sum(const float *dtokens, int b, int t0, int g, int dim, float *dpos, float *dcls, float *ddist, hipStream_t st);
+// gm (m, n) = g where y > 0, else 0: DenseReluMaskedRows, materialised
+void dense_relu_mask(const float *g, const float *y, int64_t elems, float *gm, hipStream_t st);
+// dtokens (b, t0 + g, dim): rows t0.. of every frame from src (b g, dim), the t0 leading rows zero
+void dense_strip_store(const float *src, int b, int t0, int g, int dim, float *dtokens, hipStream_t st);
+
+struct PatchBwdWorkspace {
+  int64_t partial, colsum, end;
+};
+inline PatchBwdWorkspace dense_patch_bwd_workspace(int64_t b, int64_t g, int dim, int k) {
+  Offsets256 o;
+  int splits;
+  dense_wgrad_split_len(b * g, dim, k, &splits);
+  PatchBwdWorkspace w;
+  w.partial = o.take((int64_t)dense_wgrad_partial_bytes(splits, dim, k));
+  w.colsum = o.take((int64_t)ftx_colsum_workspace_bytes(g, dim));
+  w.end = o.end > 256 ? o.end : 256;
+  return w;
+}
+size_t dense_patch_bwd_workspace_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int32_t p, int32_t dim);
+
+// ftx_vit_patch_embed_bwd_<family>
+template <class F>
+int dense_patch_embed_bwd_entry(const float *dtokens, const float *img, const float *W, int32_t b, int32_t c, int32_t h, int32_t w, int32_t p,
+                                int32_t dim, int32_t t0, float *dW, float *dbias, float *dcls, float *ddist, float *dpos, float *dimg,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+  const char *me = F::patch_bwd_name;
+  FTX_REQUIRE(b >= 1 && c >= 1 && h >= 1 && w >= 1 && p >= 1 && dim >= 4, "%s: bad size (b=%d c=%d h=%d w=%d patch=%d dim=%d)", me, b, c, h, w, p, dim);
+  FTX_REQUIRE(t0 == 1 || t0 == 2, "%s: t0 must be 1 or 2 (t0=%d)", me, t0);
+  FTX_REQUIRE(p % 4 == 0, "%s: patch must be a multiple of 4 (patch=%d)", me, p);
+  FTX_REQUIRE(h % p == 0 && w % p == 0, "%s: the image must be whole patches (h=%d w=%d patch=%d)", me, h, w, p);
+  FTX_REQUIRE(dim % 4 == 0, "%s: dim must be a multiple of 4 (dim=%d)", me, dim);
+  const int64_t k = (int64_t)c * p * p, g = (int64_t)(h / p) * (w / p);
+  FTX_REQUIRE(k % kDenseGranule == 0, "%s: c * patch * patch must be a multiple of %d (%lld)", me, kDenseGranule, (long long)k);
+  FTX_REQUIRE(!dimg || dim % kDenseGranule == 0, "%s: dim must be a multiple of %d for the image gradient (dim=%d)", me, kDenseGranule, dim);
+  FTX_REQUIRE((int64_t)b * g <= 0x7fffffff / 2 && k * dim <= 0x7fffffff / 8 && (int64_t)b * c * h * w <= 0x7fffffff && (g + t0) * dim <= 0x7fffffff,
+              "%s: too large", me);
+  FTX_REQUIRE(dtokens && img && dW && dbias && dcls && dpos && workspace, "%s: null pointer", me);
+  FTX_REQUIRE(ddist || t0 == 1, "%s: null pointer (ddist with t0 = 2)", me);
+  FTX_REQUIRE(W || !dimg, "%s: null pointer (W with dimg)", me);
+  FTX_REQUIRE(aligned16(dtokens) && aligned16(img) && aligned16(W) && aligned16(dW) && aligned16(dbias) && aligned16(dcls) && aligned16(ddist) &&
+                  aligned16(dpos) && aligned16(dimg) && aligned16(workspace),
+              "%s: pointers must be 16-byte aligned", me);
+  const PatchBwdWorkspace ws = dense_patch_bwd_workspace(b, g, dim, (int)k);
+  if (workspace_bytes < (size_t)ws.end) return workspace_short(me, workspace_bytes, (size_t)ws.end);
+  const hipStream_t st = (hipStream_t)stream;
+  char *base = (char *)workspace;
+  const int64_t m = (int64_t)b * g;
+  // dW = dY^T unfold(img): G the strip rows of dtokens, X the unfold
+  const DenseTapRows gform = {dtokens, nullptr, nullptr, nullptr, nullptr, 0.f, dim, (int)g, t0};
+  const DensePatches xform = {img, nullptr, c, h, w, p, w / p, (int)g, t0};
+  dense_wgrad_launch<F>(gform, xform, m, dim, (int)k, dW, (float *)(base + ws.partial), st);
+  // dpos, dcls, ddist, then dbias = the column sums of dpos' patch rows
+  dense_frames_sum(dtokens, b, t0, (int)g, dim, dpos, dcls, ddist, st);
+  const int rc = ftx_colsum(dpos + (int64_t)t0 * dim, g, dim, dbias, base + ws.colsum, (size_t)(ws.end - ws.colsum), stream);
+  if (rc != FTX_OK) return rc;
+  if (dimg) {   // dimg = fold(dY W)
+    const DenseStripFold form = {dtokens, dim, c, h, w, p, w / p, (int)g, t0};
+    const DenseGemmArgs a = {nullptr, W, nullptr, nullptr, m, (int)k, dim, dimg, nullptr};
+    dense_launch_form<F, DenseStripFold, FTX_EPI_NONE, true>(form, a, st);
+  }
+  return check_launch(me);
+}
+
+// ftx_vit_tap_stem_train_fwd_<family>: rows (b g, co) = ReLU(tokens[:, t0:] W^T + bias)
+template <class F>
+int dense_tap_stem_train_fwd_entry(const float *tokens, const float *W, const float *bias, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co,
+                                   float *rows, void *stream) {
+  const char *me = F::tap_fwd_name;
+  FTX_REQUIRE(b >= 0 && g >= 1 && dim >= kDenseGranule && co >= 4, "%s: bad size (b=%d g=%d dim=%d co=%d)", me, b, g, dim, co);
+  FTX_REQUIRE(t0 >= 0 && t0 <= 2, "%s: t0 must be 0, 1 or 2 (t0=%d)", me, t0);
+  FTX_REQUIRE(dim % kDenseGranule == 0, "%s: dim must be a multiple of %d (dim=%d)", me, kDenseGranule, dim);
+  FTX_REQUIRE(co % 4 == 0, "%s: co must be a multiple of 4 (co=%d)", me, co);
+  FTX_REQUIRE((int64_t)b * (g + t0) <= 0x7fffffff / 2 && (int64_t)co * dim <= 0x7fffffff, "%s: too large", me);
+  if (b == 0) return FTX_OK;
+  FTX_REQUIRE(tokens && W && bias && rows, "%s: null pointer", me);
+  FTX_REQUIRE(aligned16(tokens) && aligned16(W) && aligned16(bias) && aligned16(rows), "%s: pointers must be 16-byte aligned", me);
+  const DenseTapReluRows form = {tokens, dim, g, t0};
+  const DenseGemmArgs a = {nullptr, W, bias, nullptr, (int64_t)b * g, co, dim, rows, nullptr};
+  dense_launch_form<F>(form, a, (hipStream_t)stream);
+  return check_launch(me);
+}
+
+struct TapBwdWorkspace {
+  int64_t masked, product, partial, colsum, end;
+};
+inline TapBwdWorkspace dense_tap_bwd_workspace(int64_t b, int64_t g, int dim, int co) {
+  Offsets256 o;
+  int splits;
+  dense_wgrad_split_len(b * g, co, dim, &splits);
+  TapBwdWorkspace w;
+  w.masked = o.take((int64_t)sizeof(float) * b * g * co);
+  w.product = o.take((int64_t)sizeof(float) * b * g * dim);
+  w.partial = o.take((int64_t)dense_wgrad_partial_bytes(splits, co, dim));
+  w.colsum = o.take((int64_t)ftx_colsum_workspace_bytes(b * g, co));
+  w.end = o.end > 256 ? o.end : 256;
+  return w;
+}
+size_t dense_tap_bwd_workspace_bytes(int32_t b, int32_t g, int32_t dim, int32_t co);
+
+// ftx_vit_tap_stem_bwd_<family>
+template <class F>
+int dense_tap_stem_bwd_entry(const float *drows, const float *rows, const float *tokens, const float *W, int32_t b, int32_t g, int32_t t0, int32_t dim,
+                             int32_t co, float *dW, float *dbias, float *dtokens, void *workspace, size_t workspace_bytes, void *stream) {
+  const char *me = F::tap_bwd_name;
+  FTX_REQUIRE(b >= 1 && g >= 1 && dim >= kDenseGranule && co >= 4, "%s: bad size (b=%d g=%d dim=%d co=%d)", me, b, g, dim, co);
+  FTX_REQUIRE(t0 >= 0 && t0 <= 2, "%s: t0 must be 0, 1 or 2 (t0=%d)", me, t0);
+  FTX_REQUIRE(dim % kDenseGranule == 0, "%s: dim must be a multiple of %d (dim=%d)", me, kDenseGranule, dim);
+  FTX_REQUIRE(co % 4 == 0, "%s: co must be a multiple of 4 (co=%d)", me, co);
+  FTX_REQUIRE((int64_t)b * (g + t0) <= 0x7fffffff / 2 && (int64_t)co * dim <= 0x7fffffff / 8 && (int64_t)b * (g + t0) * dim <= ((int64_t)1 << 40),
+              "%s: too large", me);
+  FTX_REQUIRE(drows && rows && tokens && W && dW && dbias && dtokens && workspace, "%s: null pointer", me);
+  FTX_REQUIRE(aligned16(drows) && aligned16(rows) && aligned16(tokens) && aligned16(W) && aligned16(dW) && aligned16(dbias) && aligned16(dtokens) &&
+                  aligned16(workspace),
+              "%s: pointers must be 16-byte aligned", me);
+  const TapBwdWorkspace ws = dense_tap_bwd_workspace(b, g, dim, co);
+  if (workspace_bytes < (size_t)ws.end) return workspace_short(me, workspace_bytes, (size_t)ws.end);
+  const hipStream_t st = (hipStream_t)stream;
+  char *base = (char *)workspace;
+  const int64_t m = (int64_t)b * g;
+  float *gm = (float *)(base + ws.masked), *prod = (float *)(base + ws.product);
+  // dW = (masked drows)^T tokens[:, t0:]: the mask in G's load, the strip in X's rows
+  const DenseReluMaskedRows gform = {drows, rows, co};
+  const DenseTapRows xform = {tokens, nullptr, nullptr, nullptr, nullptr, 0.f, dim, g, t0};
+  dense_wgrad_launch<F>(gform, xform, m, co, dim, dW, (float *)(base + ws.partial), st);
+  // the masked gradient once in memory: dbias = its column sums, and the rows GEMM reads it
+  dense_relu_mask(drows, rows, m * co, gm, st);
+  int rc = ftx_colsum(gm, m, co, dbias, base + ws.colsum, (size_t)(ws.end - ws.colsum), stream);
+  if (rc != FTX_OK) return rc;
+  // dtokens[:, t0:] = masked drows . W  (reduction co: the rows GEMM, which takes any multiple of 4), then the strip store
+  rc = F::rows_gemm(gm, m, W, 0, nullptr, co, dim, prod, stream);
+  if (rc != FTX_OK) return rc;
+  dense_strip_store(prod, b, t0, g, dim, dtokens, st);
   return check_launch(me);
 }
 

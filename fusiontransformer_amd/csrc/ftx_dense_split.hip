@@ -22,6 +22,10 @@ using namespace ftx;
 struct DenseSplit {
   static constexpr const char *gemm_name = "ftx_dense_gemm_split", *wgrad_name = "ftx_dense_wgrad_split";
   static constexpr const char *patch_name = "ftx_vit_patch_embed_split", *tap_name = "ftx_vit_tap_stem_split";
+  static constexpr const char *patch_bwd_name = "ftx_vit_patch_embed_bwd_split", *tap_fwd_name = "ftx_vit_tap_stem_train_fwd_split";
+  static constexpr const char *tap_bwd_name = "ftx_vit_tap_stem_bwd_split";
+  // the rows GEMM of the family's mode: the tap stem's data gradient, whose reduction (co = 96) is no multiple of kDenseGranule
+  static constexpr auto rows_gemm = &ftx_rows_gemm_split;
 
   // LDS: three bf16 images per operand.  The stage is 32 reduction elements deep with a 40-element (80 B) row stride: 6 x 128 x 80 B
   // = 61 440 B at the 128 x 128 tile, under the 64 KB a static __shared__ array may take without a function attribute, two blocks per CU.
@@ -74,6 +78,32 @@ extern "C" int ftx_vit_tap_stem_split(const float *tokens, const float *W, const
                                     const float *running_mean, const float *running_var, float eps, int32_t b, int32_t g, int32_t t0, int32_t dim,
                                     int32_t co, float *out, void *stream) {
   return dense_tap_stem_entry<DenseSplit>(tokens, W, bias, gamma, beta, running_mean, running_var, eps, b, g, t0, dim, co, out, stream);
+}
+
+extern "C" size_t ftx_vit_patch_embed_bwd_split_workspace_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim) {
+  return dense_patch_bwd_workspace_bytes(b, c, h, w, patch, dim);
+}
+
+extern "C" int ftx_vit_patch_embed_bwd_split(const float *dtokens, const float *img, const float *W, int32_t b, int32_t c, int32_t h, int32_t w,
+                                           int32_t patch, int32_t dim, int32_t t0, float *dW, float *dbias, float *dcls, float *ddist, float *dpos,
+                                           float *dimg, void *workspace, size_t workspace_bytes, void *stream) {
+  return dense_patch_embed_bwd_entry<DenseSplit>(dtokens, img, W, b, c, h, w, patch, dim, t0, dW, dbias, dcls, ddist, dpos, dimg, workspace, workspace_bytes,
+                                              stream);
+}
+
+extern "C" int ftx_vit_tap_stem_train_fwd_split(const float *tokens, const float *W, const float *bias, int32_t b, int32_t g, int32_t t0, int32_t dim,
+                                              int32_t co, float *rows, void *stream) {
+  return dense_tap_stem_train_fwd_entry<DenseSplit>(tokens, W, bias, b, g, t0, dim, co, rows, stream);
+}
+
+extern "C" size_t ftx_vit_tap_stem_bwd_split_workspace_bytes(int32_t b, int32_t g, int32_t dim, int32_t co) {
+  return dense_tap_bwd_workspace_bytes(b, g, dim, co);
+}
+
+extern "C" int ftx_vit_tap_stem_bwd_split(const float *drows, const float *rows, const float *tokens, const float *W, int32_t b, int32_t g, int32_t t0,
+                                        int32_t dim, int32_t co, float *dW, float *dbias, float *dtokens, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+  return dense_tap_stem_bwd_entry<DenseSplit>(drows, rows, tokens, W, b, g, t0, dim, co, dW, dbias, dtokens, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ftx_dense_wgrad_split_workspace_bytes(int64_t m, int32_t n, int32_t k) { return dense_wgrad_workspace_bytes(m, n, k); }

@@ -1737,6 +1737,39 @@ def vit_mlp(x, w1, b1, w2, b2=None, mode="bf16"):
     return _LinearFn.apply(torch.nn.functional.gelu(_LinearFn.apply(x, w1, b1, lib_bf16)), w2, b2, lib_bf16)
 
 
+# ---------------------------------------------------------------- patch embedding and tap stems of the ViT in training
+def _dense_mode(mode, who):
+    if mode not in _DENSE_MODES:
+        raise ValueError(f"{who} mode must be 'bf16' or 'split', got {mode!r}")
+    return mode
+
+
+def vit_patch_embed_supported(img, weight):
+    """True when ftx_vit_patch_embed_* and its backward take this embedding: fp32 CUDA tensors, a square patch that is a multiple of 4,
+    c patch patch and the width multiples of 64, whole patches."""
+    from .vit_stems import vit_patch_embed_supported as supported
+    return supported(img, weight)
+
+
+def vit_patch_embed(img, weight, bias, cls, dist, pos, mode="split"):
+    """The ViT's embedding as one node: tokens (b, t0 + g, dim) = [cls + pos[0], (dist + pos[1]), unfold(img) W^T + bias + pos[t0:]] for
+    img (b, c, h, w), weight (dim, c, patch, patch) as nn.Conv2d keeps it, cls / dist (dim elements in any shape; dist None: t0 = 1) and
+    pos ((t0 + g) dim elements), on the dense GEMM kernels of `mode` ("split" | "bf16", include/ftx.h).  Differentiable in every
+    operand; the image gradient is computed only when img asks for it.  The bias gradient is ftx_colsum of the patch rows of d pos (the
+    frames summed first): reproducible, and not the bits of a column sum over all b g rows."""
+    from .vit_stems import _VitPatchEmbed
+    return _VitPatchEmbed.apply(img, weight, bias, cls, dist, pos, _dense_mode(mode, "vit_patch_embed"))
+
+
+def vit_tap_stem(tokens, weight, bias, t0=0, mode="split"):
+    """The Conv1x1 -> ReLU of a tap stem on the token grid in training: rows (b g, co) = ReLU(tokens[:, t0:] W^T + bias) for tokens
+    (b, t0 + g, dim) WITH their t0 leading (cls / dist) rows -- they are skipped by addressing, in the forward and in both gradients, and
+    the gradient of the tokens comes back whole with those rows zero.  weight (co, dim) or (co, dim, 1, 1).  The BatchNorm behind it is
+    functional.batch_norm on the rows.  mode "split" | "bf16" (include/ftx.h: ftx_vit_tap_stem_train_fwd_*, ftx_vit_tap_stem_bwd_*)."""
+    from .vit_stems import _VitTapStem
+    return _VitTapStem.apply(tokens, weight, bias, t0, _dense_mode(mode, "vit_tap_stem"))
+
+
 # ---------------------------------------------------------------- fused sample_down
 class _SampleDown(torch.autograd.Function):
     @staticmethod

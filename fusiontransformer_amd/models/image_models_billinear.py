@@ -74,11 +74,18 @@ class BilinearModule(nn.Module):
         bump_step_counter(bn)
         return spf.resample_nearest(x, self.size)
 
-    def forward_tokens(self, tokens, grid_hw):
-        """tokens (B, gh*gw, Cin) -> stem on the token grid -> (B, gh, gw, Cout) channels-last."""
-        B, T, E = tokens.shape
+    def forward_tokens(self, tokens, grid_hw, t0=0, mode=None):
+        """tokens (B, gh*gw, Cin) -> stem on the token grid -> (B, gh, gw, Cout) channels-last.
+        mode "split" | "bf16" (Image2DTransformer.set_native_stems engaged): tokens are (B, t0 + gh*gw, Cin) WITH their t0 leading
+        rows, and Conv1x1 -> ReLU and its backward run as functional.vit_tap_stem, which skips those rows by addressing."""
         conv, bn = self.stem[0], self.stem[2]
-        rows = F.relu(F.linear(tokens.reshape(B * T, E), conv.weight.view(conv.out_channels, E), conv.bias))
+        if mode is not None and conv.bias is None:
+            tokens, mode = tokens[:, t0:], None
+        B, T, E = tokens.shape
+        if mode is not None:
+            rows = spf.vit_tap_stem(tokens, conv.weight, conv.bias, t0=t0, mode=mode)
+        else:
+            rows = F.relu(F.linear(tokens.reshape(B * T, E), conv.weight.view(conv.out_channels, E), conv.bias))
         bump_step_counter(bn)
         rows = spf.batch_norm(rows, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps)
         return rows.view(B, grid_hw[0], grid_hw[1], conv.out_channels)
@@ -117,7 +124,7 @@ class Net2DBillinear(nn.Module):
             ckpt = torch.load(kw["IMAGE_PRETRAINED_PATH"], map_location="cpu", weights_only=True)["state_dict"]
             new_state_dict = OrderedDict((k.replace("backbone.", ""), v) for k, v in ckpt.items() if "backbone" in k)
             self.backbone.load_state_dict(new_state_dict)
-        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl, image_native_train
+        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl, image_native_train, image_native_stems
         # Training on the GPU runs the trunk as HIP graphs, one per tapped segment (transformers.py): ~500 kernel launches
         # per step become 4 graph launches, which takes 7 ms off the host side of a step (batch 4: the host issue time
         # drops from ~24 to ~17 ms, so the step stays GPU-bound on a slow host; +26-30 % frames/s at batch 1-2).
@@ -189,6 +196,16 @@ class Net2DBillinear(nn.Module):
         """Why the last forward did not run the native training executor; None when it did."""
         return self.backbone.native_train_reason()
 
+    def set_native_stems(self, on=True):
+        """cfg.MODEL.image_native_stems: the patch embedding and the tap stems on the library's training forms
+        (Image2DTransformer.set_native_stems; functional.vit_patch_embed, functional.vit_tap_stem).  Independent of set_native_train."""
+        self.backbone.set_native_stems(on)
+        return self
+
+    def native_stems_reason(self):
+        """Why the last forward did not run the native stems; None when it did."""
+        return self.backbone.native_stems_reason()
+
     def _native_executor(self, img):
         """The executor when this forward is one it runs (see set_native_eval), else None (and the reason is kept)."""
         why = None
@@ -230,14 +247,19 @@ class Net2DBillinear(nn.Module):
             raise ValueError("lift_size must be positive")
         return h, w
 
-    def get_img_feats(self, img_indices, block_id: str, image_shape: tuple, backbone_output: Dict, lift_ctx=None, lift_size=None):
+    def get_img_feats(self, img_indices, block_id: str, image_shape: tuple, backbone_output: Dict, lift_ctx=None, lift_size=None, stems=None):
         """reference image_models_billinear.py:88-126 -> (sum N, 96).
 
         `lift_ctx` is a dict that lives for ONE forward: the taps of that forward share the sort of the points by
-        source cell (the lift's atomic-free backward) through it.  Nothing about a batch is kept on the module."""
+        source cell (the lift's atomic-free backward) through it.  Nothing about a batch is kept on the module.
+        `stems`: the mode of the native stems when they run this forward; the tokens then come with their leading cls / dist rows
+        (forward_blocks(full_tokens=True))."""
         x = backbone_output[block_id]
         g = 384 // 16
-        grid = self.up[block_id].forward_tokens(x, (g, g))
+        if stems is None:
+            grid = self.up[block_id].forward_tokens(x, (g, g))      # the call as it always was
+        else:
+            grid = self.up[block_id].forward_tokens(x, (g, g), t0=self.backbone.num_tokens, mode=stems)
         idx, frame = pack_img_indices(img_indices, x.device)
         H, W = self._lift_hw(image_shape, lift_size)
         seg = None
@@ -266,19 +288,21 @@ class Net2DBillinear(nn.Module):
         x = self.sample_down(img)
         if on_step is not None:
             on_step()
+        stems = self.backbone.native_stems_mode(x)      # None: the switch is off or does not engage (native_stems_reason())
         middle = {}
 
         def tap(i, tokens):
             if self.middle_feat_block_number is not None and str(i) == self.middle_feat_block_number and self.middle_feat_block_number in self.up:
                 middle["feats"] = self.get_img_feats(img_indices, self.middle_feat_block_number, img.shape, {self.middle_feat_block_number: tokens},
-                                                        lift_ctx=lift_ctx, lift_size=lift_size)
+                                                        lift_ctx=lift_ctx, lift_size=lift_size, stems=stems)
                 if on_middle is not None:
                     on_middle(middle["feats"])
             if on_step is not None:
                 on_step()
 
-        backbone_output = self.backbone.forward_blocks(x, on_block=tap)
-        late_feats = self.get_img_feats(img_indices, self.late_feat_block_number, img.shape, backbone_output, lift_ctx=lift_ctx, lift_size=lift_size)
+        backbone_output = self.backbone.forward_blocks(x, on_block=tap, full_tokens=stems is not None)
+        late_feats = self.get_img_feats(img_indices, self.late_feat_block_number, img.shape, backbone_output, lift_ctx=lift_ctx, lift_size=lift_size,
+                                        stems=stems)
         x = spf.linear(late_feats, self.linear.weight, self.linear.bias)
         preds = {"img_feats": late_feats, "img_seg_logit": x}
         if self.dual_head:

@@ -58,7 +58,7 @@ class Net2DSeg(nn.Module):
             ckpt = torch.load(kw["IMAGE_PRETRAINED_PATH"], map_location="cpu", weights_only=True)["state_dict"]
             new_state_dict = OrderedDict((k.replace("backbone.", ""), v) for k, v in ckpt.items() if "backbone" in k)
             self.backbone.load_state_dict(new_state_dict)
-        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl, image_native_train
+        self.backbone.set_switches(kw)      # attn_impl, vit_bf16, vit_linear_impl, image_native_train, image_native_stems
         # parameters that can never receive a gradient: the final `norm` (forward_blocks never applies it) and blocks past the last tap
         for p in self.backbone.norm.parameters():
             p.requires_grad_(False)
@@ -98,6 +98,16 @@ class Net2DSeg(nn.Module):
     def native_train_reason(self):
         """Why the last forward did not run the native training executor; None when it did."""
         return self.backbone.native_train_reason()
+
+    def set_native_stems(self, on=True):
+        """cfg.MODEL.image_native_stems: the patch embedding on the library's training forms (Image2DTransformer.set_native_stems); the
+        resampled image carries a gradient here, so the embedding's backward also writes the image gradient through the fold."""
+        self.backbone.set_native_stems(on)
+        return self
+
+    def native_stems_reason(self):
+        """Why the last forward did not run the native patch embedding; None when it did."""
+        return self.backbone.native_stems_reason()
 
     def get_img_feats(self, img_indices, block_id: str, image_shape: tuple, backbone_output: Dict):
         """reference image_models_stn.py:63-100 -> (sum N, feat_channels): the rows the reference picks out of the map that

@@ -352,13 +352,14 @@ class Image2DTransformer(nn.Module):
             blk.attn.attn_impl = impl
 
     def set_switches(self, kw):
-        """The three switches above and set_native_train from an image model's backbone_2d_kwargs (cfg.MODEL.attn_impl / vit_bf16 /
-        vit_linear_impl / image_native_train)."""
+        """The three switches above, set_native_train and set_native_stems from an image model's backbone_2d_kwargs (cfg.MODEL.attn_impl
+        / vit_bf16 / vit_linear_impl / image_native_train / image_native_stems)."""
         self.set_attention_impl(kw.get("attn_impl", "ftx"))
         if kw.get("vit_bf16", False):
             self.set_bf16(True)   # BASELINE configs[4] "bf16 forward"; default is fp32 like the reference
         self.set_linear_impl(kw.get("vit_linear_impl", "library"))
         self.set_native_train(bool(kw.get("image_native_train", False)))      # cfg.MODEL.image_native_train
+        self.set_native_stems(bool(kw.get("image_native_stems", False)))      # cfg.MODEL.image_native_stems
 
     # ---- native training executor of the trunk -------------------------------------------------------------
     image_native_train = False
@@ -416,7 +417,7 @@ class Image2DTransformer(nn.Module):
         self.__dict__["_native_tr_reason"] = why
         return self.__dict__["_native_tr"] if why is None else None
 
-    def _forward_native_train(self, ex, x, on_block):
+    def _forward_native_train(self, ex, x, on_block, full_tokens=False):
         """forward_blocks through the training executor: `_embed` here, then one node per segment.  As on the graphed path only segment
         ends exist as tensors: the taps' outputs with `graph_taps` set, every block's without."""
         # as after an eager pass (forward_blocks): a capture attempted behind a backward through these parameters aborts the process
@@ -429,12 +430,73 @@ class Image2DTransformer(nn.Module):
             x = ex.segment(x, first, e)
             first = e + 1
             if taps is None or e in taps:
-                outputs[str(e)] = x[:, self.num_tokens:, :] if self.remove_tokens_outputs else x
+                outputs[str(e)] = self._tap_view(x, full_tokens)
                 if on_block is not None:
                     on_block(e, outputs[str(e)])
         return outputs
 
+    # ---- patch embedding and tap stems on the library's kernels in training ---------------------------------
+    image_native_stems = False
+
+    def set_native_stems(self, on=True):
+        """Opt-in library path for the two places where the image branch still leaves the library in training (cfg.MODEL.
+        image_native_stems): the patch embedding (`_embed`: unfold copy, GEMM, + pos, the cls / dist rows and their gradients become
+        functional.vit_patch_embed, one node on ftx_vit_patch_embed_* / ftx_vit_patch_embed_bwd_*) and, in Net2DBillinear, the tap stems
+        (functional.vit_tap_stem).  It engages in training mode with gradients enabled on float32 CUDA tensors, exactly where the native
+        image executors engage: every live block runs the linears the library owns (vit_linear_impl "ftx_split", or "ftx" with
+        set_bf16), whose mode the stems take.  Anything else takes the existing path exactly as with the switch off, and
+        native_stems_reason() says why.  Independent of set_native_train and of the HIP graphs (the nodes are capturable)."""
+        self.image_native_stems = bool(on)
+        if not on:
+            self.__dict__["_native_stems_reason"] = "the switch is off"
+        return self
+
+    def native_stems_reason(self):
+        """Why the last embedding did not run on the library's training forms; None when it did."""
+        return self.__dict__.get("_native_stems_reason", "the switch is off")
+
+    def native_stems_mode(self, x):
+        """The mode ("split" | "bf16") of functional.vit_patch_embed / vit_tap_stem when a forward on the image x is one the native
+        stems run (see set_native_stems), else None (and the reason is kept)."""
+        why, mode = None, None
+        if not self.image_native_stems:
+            why = "the switch is off"
+        elif not self.training:
+            why = "eval mode"
+        elif not torch.is_grad_enabled():
+            why = "gradients are disabled"
+        elif not x.is_cuda or x.dtype != torch.float32:
+            why = "the input is not a float32 tensor on the GPU"
+        else:
+            live = [b for i, b in enumerate(self.blocks) if self.last_block is None or i <= self.last_block]
+            routes = {linear_route(lin) for b in live for lin in block_linears(b)}
+            pe = self.patch_embed
+            if len(routes) != 1 or next(iter(routes)) not in OWN_ROUTES:
+                impl, bf16 = linear_switches(live[0].attn.qkv) if live else ("library", False)
+                why = ("vit_linear_impl is %r%s: the stems take the mode of the trunk's own linears ('ftx_split', or 'ftx' with set_bf16)"
+                       % (impl, "" if impl != "ftx" or bf16 else " without set_bf16"))
+            elif pe.proj.bias is None or not isinstance(pe.norm, nn.Identity) or self.pos_drop.p != 0.0:
+                why = "the patch embedding has no bias, a norm or a dropout"
+            else:
+                from .. import functional as spf
+                if not spf.vit_patch_embed_supported(x, pe.proj.weight):
+                    why = "the kernels do not take this embedding (patch % 4, c patch patch % 64, dim % 64, whole patches)"
+                else:
+                    mode = next(iter(routes))
+        self.__dict__["_native_stems_reason"] = why
+        return mode
+
+    def _tap_view(self, t, full_tokens=False):
+        """A block's output as the caller gets it: without the cls / dist rows when `remove_tokens_outputs` is set and the caller
+        did not ask for the whole tokens."""
+        return t[:, self.num_tokens:, :] if self.remove_tokens_outputs and not full_tokens else t
+
     def _embed(self, x):
+        mode = self.native_stems_mode(x)
+        if mode is not None:
+            from .. import functional as spf
+            pe = self.patch_embed
+            return self.pos_drop(spf.vit_patch_embed(x, pe.proj.weight, pe.proj.bias, self.cls_token, self.dist_token, self.pos_embed, mode=mode))
         x = self.patch_embed(x)
         b = x.shape[0]
         cls_token = _over_batch(self.cls_token, b)
@@ -444,24 +506,26 @@ class Image2DTransformer(nn.Module):
             x = torch.cat((cls_token, _over_batch(self.dist_token, b), x), dim=1)
         return self.pos_drop(x + _over_batch(self.pos_embed, b))
 
-    def forward_blocks(self, x: torch.Tensor, on_block=None) -> Dict[str, torch.Tensor]:
+    def forward_blocks(self, x: torch.Tensor, on_block=None, full_tokens=False) -> Dict[str, torch.Tensor]:
         """reference models/transformers.py:16-45: every block's output, cls/dist tokens stripped.
         `on_block(i, tokens)` is called as soon as block i's output exists (used to lift the tapped
         block's features while the remaining blocks are still being issued).
+        `full_tokens`: the outputs keep their leading cls / dist rows whatever `remove_tokens_outputs` says; a caller that skips them
+        by addressing (functional.vit_tap_stem under set_native_stems) asks for that.
 
         With `graph_taps` set (training on the GPU) the trunk runs as one HIP graph per tapped segment --
         forward and backward: the shapes are static, and ~500 kernel launches per step become 2 x 2 graph
         launches.  Only the tapped blocks' outputs are returned then (the model reads no others)."""
         trainer = self._native_trainer(x)
         if trainer is not None:
-            return self._forward_native_train(trainer, x, on_block)
+            return self._forward_native_train(trainer, x, on_block, full_tokens)
         graphed = self._graphed_segments(x)
         if graphed is not None:
             outputs = dict()
             for last, seg, is_tap in graphed:
                 x = seg(x)
                 if is_tap:
-                    outputs[str(last)] = x[:, self.num_tokens:, :] if self.remove_tokens_outputs else x
+                    outputs[str(last)] = self._tap_view(x, full_tokens)
                     if on_block is not None:
                         on_block(last, outputs[str(last)])
             return outputs
@@ -471,7 +535,7 @@ class Image2DTransformer(nn.Module):
             # are copies, so a later replay does not change tensors the caller still holds
             outputs = dict()
             for i, t in infer(x):
-                outputs[str(i)] = t[:, self.num_tokens:, :] if self.remove_tokens_outputs else t
+                outputs[str(i)] = self._tap_view(t, full_tokens)
                 if on_block is not None:
                     on_block(i, outputs[str(i)])
             return outputs
@@ -483,7 +547,7 @@ class Image2DTransformer(nn.Module):
         outputs = dict()
 
         def emit(i, t):
-            outputs[str(i)] = t[:, self.num_tokens:, :] if self.remove_tokens_outputs else t
+            outputs[str(i)] = self._tap_view(t, full_tokens)
             if on_block is not None:
                 on_block(i, outputs[str(i)])
 
@@ -525,7 +589,7 @@ class Image2DTransformer(nn.Module):
         per-block execution switches and the parameters' requires_grad pattern.  Changing any of them selects another graph."""
         grads = tuple(p.requires_grad for p in self.parameters())
         return (tuple(x.shape), x.dtype, bool(x.requires_grad), tuple(self.graph_taps), self.last_block, self.graph_segment_blocks,
-                tuple(block_switches(blk) for blk in self.blocks), grads, torch.cuda.current_device())
+                tuple(block_switches(blk) for blk in self.blocks), grads, torch.cuda.current_device(), bool(self.image_native_stems))
 
     def _graphed_segments(self, x):
         if not self.graph_taps or not self.use_graphs or not x.is_cuda or not self.training or not torch.is_grad_enabled():

@@ -862,6 +862,56 @@ int ftx_vit_tap_stem_split(const float *tokens, const float *W, const float *bia
 int ftx_vit_tap_stem_bf16(const float *tokens, const float *W, const float *bias, const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *out, void *stream);
 int ftx_rows_add_bias(const float *r, const float *p, const float *pb, int64_t n, int32_t c, float *out, void *stream);
 
+/* ---- the patch embedding and the tap stems in training (models/transformers.py:90-100, models/image_models_billinear.py:8-24)
+ *      (csrc/ftx_dense_common.h, csrc/ftx_dense_common.hip) ----
+ * Operand forms of the dense families' weight-gradient kernel and output forms of their GEMM kernel, as the eval forms above are forms
+ * of the GEMM's A: the tile and split rules, the piece split, the accumulator order and the reduction order are those of
+ * ftx_dense_wgrad_<split|bf16> / ftx_dense_gemm_<split|bf16>, so every product below returns the bits of that plain entry run on
+ * materialised operands, followed by the stated store.  Every entry validates all of its arguments, the workspace size included, before
+ * its first launch; none allocates, synchronises the host or uses atomics; all are capturable.  Every pointer 16-byte aligned.
+ * The forward of the patch embedding in training is ftx_vit_patch_embed_<split|bf16> above.
+ *
+ * ftx_vit_patch_embed_bwd_<split|bf16>: from dtokens (b, t0 + g, dim), the gradient of the tokens, and img (b, c, h, w), g = (h / patch)
+ * (w / patch), dY = the rows t0.. of every frame of dtokens (b g rows, never copied):
+ *   dW (dim, c patch patch) = dY^T unfold(img)   the weight gradient with G = the strip rows of dtokens and X = the unfold addressing of
+ *                                                ftx_vit_patch_embed; workspace partials as ftx_dense_wgrad_* for (b g, dim, c patch patch)
+ *   dpos (t0 + g, dim)      = dtokens[0] + dtokens[1] + ... + dtokens[b - 1], fp32, frames ascending
+ *   dcls (dim) = dpos[0];  ddist (dim) = dpos[1] (t0 = 2; ddist may be NULL with t0 = 1)
+ *   dbias (dim)             = ftx_colsum of the g rows dpos[t0 ..]: the frames are summed first (fp32, ascending), the patches second
+ *                             (float64, ftx_colsum's fixed order).  This order is the definition of the bias gradient: it is
+ *                             reproducible and is NOT the column sum of the b g rows of dY.
+ *   dimg (b, c, h, w)       only with dimg != NULL (W (dim, c patch patch) is then required, and dim % 64 == 0): fold(dY W), the data
+ *                             gradient of ftx_dense_gemm_* (w_kn = 1) with A = the strip rows and the output written through the
+ *                             fold: element (row (frame, gy, gx), column (ci, py, px)) to dimg[frame][ci][gy patch + py][gx patch + px].
+ *                             The patches do not overlap: every pixel is written exactly once, nothing is accumulated.
+ * Refused: c patch patch % 64 != 0, patch % 4 != 0, dim % 4 != 0, h or w not whole patches, t0 outside {1, 2}, b < 1, null or
+ * misaligned pointers, workspace_bytes < ftx_vit_patch_embed_bwd_<split|bf16>_workspace_bytes(b, c, h, w, patch, dim).
+ *
+ * ftx_vit_tap_stem_train_fwd_<split|bf16>: rows (b g, co) = ReLU(tokens[:, t0:] W^T + bias), tokens (b, t0 + g, dim), W (co, dim): the
+ * A addressing of ftx_vit_tap_stem_*, the epilogue stops behind the ReLU (x < 0 ? 0 : x, NaN stays NaN).  The sequence of a stem in
+ * training is   ftx_vit_tap_stem_train_fwd -> ftx_bn_train_fwd on rows (b g, co) -> the lift;   backward:   ftx_bn_train_bwd -> its
+ * input gradient is drows of ftx_vit_tap_stem_bwd.  dim % 64 == 0, co % 4 == 0, t0 in {0, 1, 2}; b == 0 returns FTX_OK.
+ *
+ * ftx_vit_tap_stem_bwd_<split|bf16>: from drows (b g, co), the saved rows (b g, co) and tokens; gm = drows where rows > 0, else 0 (a
+ * select: also 0 where rows is NaN):
+ *   dW (co, dim)             = gm^T tokens[:, t0:]   the weight gradient with the mask in G's load and the strip addressing as X
+ *   dbias (co)               = ftx_colsum of gm (b g rows), gm written once to the workspace
+ *   dtokens (b, t0 + g, dim) = rows t0.. of every frame: gm . W; the t0 leading rows: zero.  Fully written.  The product's reduction
+ *                              is co (96), no multiple of the dense GEMM's 64: it runs on the rows GEMM of the mode,
+ *                              ftx_rows_gemm_<split|bf16>(gm, b g, W, w_transposed = 0, bias = NULL, ca = co, co = dim), into the
+ *                              workspace, and one store pass moves its rows behind the leading rows.  W is not padded.
+ * workspace: ftx_vit_tap_stem_bwd_<split|bf16>_workspace_bytes(b, g, dim, co).  Refusals as the forward, and b < 1. */
+size_t ftx_vit_patch_embed_bwd_split_workspace_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim);
+size_t ftx_vit_patch_embed_bwd_bf16_workspace_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim);
+int ftx_vit_patch_embed_bwd_split(const float *dtokens, const float *img, const float *W, int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim, int32_t t0, float *dW, float *dbias, float *dcls, float *ddist, float *dpos, float *dimg, void *workspace, size_t workspace_bytes, void *stream);
+int ftx_vit_patch_embed_bwd_bf16(const float *dtokens, const float *img, const float *W, int32_t b, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t dim, int32_t t0, float *dW, float *dbias, float *dcls, float *ddist, float *dpos, float *dimg, void *workspace, size_t workspace_bytes, void *stream);
+int ftx_vit_tap_stem_train_fwd_split(const float *tokens, const float *W, const float *bias, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *rows, void *stream);
+int ftx_vit_tap_stem_train_fwd_bf16(const float *tokens, const float *W, const float *bias, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *rows, void *stream);
+size_t ftx_vit_tap_stem_bwd_split_workspace_bytes(int32_t b, int32_t g, int32_t dim, int32_t co);
+size_t ftx_vit_tap_stem_bwd_bf16_workspace_bytes(int32_t b, int32_t g, int32_t dim, int32_t co);
+int ftx_vit_tap_stem_bwd_split(const float *drows, const float *rows, const float *tokens, const float *W, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *dW, float *dbias, float *dtokens, void *workspace, size_t workspace_bytes, void *stream);
+int ftx_vit_tap_stem_bwd_bf16(const float *drows, const float *rows, const float *tokens, const float *W, int32_t b, int32_t g, int32_t t0, int32_t dim, int32_t co, float *dW, float *dbias, float *dtokens, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ftx_vit_eval: the eval-mode, no-gradient forward of blocks [block_first, block_last] of the trunk, with the tap stems behind the
  * tapped blocks.  Tables: packed little-endian records in HOST memory holding device pointers (float32, contiguous); the library
  * reports each record size (ftx_vit_*_bytes).

@@ -7,6 +7,7 @@ usage: python tools/bench_single.py [--steps 60] [--warmup 15] [--out profiles/s
        python tools/bench_single.py --native-train-ab --dropout [--steps 20]   # LidarSeg with the training executor: torch's Dropout and five
                                                                                # segments against the library's Dropout and three; then the kernel
        python tools/bench_single.py --native-image-train-ab [--steps 20]   # the ViT trunk in training: HIP graphs / eager / the native training executor
+       python tools/bench_single.py --native-stems-ab [--steps 20]         # the patch embedding and tap stems in training: image_native_stems off / on
        python tools/bench_single.py --native-train-steps on|off --steps N     # N untimed batch-1 steps, to count launches under a kernel trace
        python tools/bench_single.py --lidar-split [--steps 20] [--out profiles/spconv_split_steps.json]   # LidarSeg steps, default against lidar_split
 
@@ -88,6 +89,17 @@ def _graph_nodes(t):
             seen.add(f)
             todo += [g for g, _ in f.next_functions]
     return len(seen)
+
+
+def _named_nodes(t, prefixes):
+    """{prefix: how many autograd nodes under tensor t have a name that starts with it}."""
+    seen, todo = set(), [t.grad_fn]
+    while todo:
+        f = todo.pop()
+        if f is not None and f not in seen:
+            seen.add(f)
+            todo += [g for g, _ in f.next_functions]
+    return {p: sum(f.name().startswith(p + "Backward") for f in seen) for p in prefixes}
 
 
 def _switch_ab(switch, batch, steps, warmup, windows=5, model_kind="LidarSeg", both=()):
@@ -314,6 +326,68 @@ def native_image_train_ab(batch, steps, warmup, windows=5, model_kind="ImageSegB
     return out
 
 
+def native_stems_ab(batch, steps, warmup, windows=5, model_kind="ImageSegBilinear"):
+    """Step time of the image branch with the patch embedding and the tap stems on the library's training forms
+    (cfg.MODEL.image_native_stems) against the switch off, vit_linear_impl="ftx_split", the trunk as HIP graphs in both arms (the default
+    path), with the method and the rule of native_image_train_ab: two models from one seed in one process, windows of `steps` steps
+    alternating between them; median (min..max) ms per step, per arm the host-issue time, the stem nodes under the image logits and the peak
+    of torch's allocator above what was resident (the unfold copy and the strip copies go away)."""
+    import time
+    from fusiontransformer_amd import config
+    from fusiontransformer_amd.models.build import build_model
+    from fusiontransformer_amd.trainer import TrainStep
+    _, res = zip(*[_inputs(batch, cycle, "cuda") for cycle in (0, 1)])
+    arms, nets = {}, {}
+    for mode in ("off", "on"):
+        cfg = config.image_cfg() if model_kind == "ImageSegBilinear" else config.fusion_cfg(model_kind)
+        cfg.MODEL.vit_linear_impl = "ftx_split"
+        cfg.MODEL.image_native_stems = mode == "on"
+        torch.manual_seed(0)
+        model = build_model(cfg)[0].cuda().train()
+        nets[mode] = model.image_backbone
+        arms[mode] = TrainStep(cfg, model)
+    info = {m: {} for m in arms}
+
+    def window(mode, n):
+        step = arms[mode]
+        seq = [res[i % 2] for i in range(n + 1)]
+        for x in seq:
+            x["lidar"].prepared = None
+        torch.cuda.synchronize()
+        resident = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        for i in range(n):
+            preds = step(seq[i], next_batch=seq[i + 1])
+        e1.record()
+        host = (time.perf_counter() - t0) * 1e3 / n
+        torch.cuda.synchronize()
+        info[mode].setdefault("host_issue_ms", []).append(host)
+        info[mode]["stem_nodes"] = _named_nodes(preds["img_seg_logit"], ("_VitPatchEmbed", "_VitTapStem"))
+        info[mode]["peak_above_resident_bytes"] = int(torch.cuda.max_memory_allocated() - resident)
+        return e0.elapsed_time(e1) / n
+
+    for mode in arms:
+        window(mode, warmup)
+        info[mode]["host_issue_ms"] = []
+    ms = {m: [] for m in arms}
+    order = list(arms)
+    for w in range(windows):
+        for mode in order[w % 2:] + order[:w % 2]:
+            ms[mode].append(window(mode, steps))
+    spread = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    out = {"model": model_kind, "vit_linear_impl": "ftx_split", "batch": batch, "steps_per_window": steps, "windows": windows,
+           "ms_per_step": {m: spread(v) for m, v in ms.items()}, "ms_per_step_windows": ms}
+    for m in arms:
+        out[m] = dict(info[m], host_issue_ms=spread(info[m]["host_issue_ms"]), reason=nets[m].native_stems_reason(),
+                      graph_state=nets[m].backbone.graph_state())
+    out["every_on_window_beats_every_off_window"] = bool(max(ms["on"]) < min(ms["off"]))
+    out["every_off_window_beats_every_on_window"] = bool(max(ms["off"]) < min(ms["on"]))
+    return out
+
+
 def lidar_split_ab(batch, steps, warmup, windows=5):
     """LidarSeg step time with the default exact-fp32 sparse convolution and with SPVCNN.set_split (the three-piece split kernels): two
     models from one seed in one process, `windows` windows of `steps` steps each, alternating."""
@@ -420,6 +494,9 @@ def main():
     ap.add_argument("--native-image-train-ab", action="store_true",
                     help="only: ImageSegBilinear and middle-fusion step time, vit_linear_impl=ftx_split, trunk as HIP graphs / eager / native training "
                          "executor (Image2DTransformer.set_native_train), batch 1 and 4")
+    ap.add_argument("--native-stems-ab", action="store_true",
+                    help="only: ImageSegBilinear and middle-fusion step time, vit_linear_impl=ftx_split, cfg.MODEL.image_native_stems off / on, "
+                         "batch 1 and 4")
     ap.add_argument("--native-train-steps", choices=["on", "off"], help="only: --steps untimed LidarSeg batch-1 steps with the switch on / off")
     ap.add_argument("--lidar-split", action="store_true", help="only: LidarSeg step time with SPVCNN.set_split off / on, batch 4 and 1; --out writes the JSON")
     args = ap.parse_args()
@@ -438,6 +515,11 @@ def main():
         for kind in ("ImageSegBilinear", "middle"):
             for batch in (1, 4):
                 print(json.dumps(native_image_train_ab(batch, args.steps, args.warmup, model_kind=kind)), flush=True)
+        return
+    if args.native_stems_ab:
+        for kind in ("ImageSegBilinear", "middle"):
+            for batch in (1, 4):
+                print(json.dumps(native_stems_ab(batch, args.steps, args.warmup, model_kind=kind)), flush=True)
         return
     if args.native_train_steps:
         print(json.dumps(native_train_steps(args.native_train_steps, args.steps)), flush=True)
